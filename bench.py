@@ -1,6 +1,6 @@
 """bench.py -- env-steps/s of the native batched step on the BASELINE.json workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload humanoid|humanoid32k|ant|mesh|cartpole]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload humanoid|humanoid32k|ant|mesh|cartpole] [--dump-outputs DIR]
 
 One process per GPU.  The driver launches N > 1 with torch.distributed.run; `python bench.py --gpus N` run directly spawns
 that launch itself (as a child process, BEFORE this process touches the GPU) and relays rank 0's line.  Independent
@@ -14,6 +14,9 @@ loop; `out_buffers` reports the `step(..., out=)` ping-pong extension beside it.
 Before the W warm-up steps the step loop runs 100 untimed steps on a SCRATCH copy of the inputs (clocks, allocator pools, plan caches);
 the warm-up and the timed steps then start from the original state.  Early steps of the trajectory are the expensive ones (all contacts
 active, longer line searches): --steps 20 --warmup 5 reads ~18.3 M env-steps/s where the default 200 / 20 reads ~19 M.
+
+`--dump-outputs DIR` (e.g. bench_outputs/, git-ignored) writes the Data the last timed step returned, one .npy per non-empty array,
+after the timed region: the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -24,6 +27,8 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
+DUMP_CAP_BYTES = 64 * 10**6  # --dump-outputs: all files together, .npy headers included
+DUMP_SAMPLE_SEED = 0         # which environments a capped dump keeps
 
 
 def parse_args():
@@ -38,7 +43,13 @@ def parse_args():
     ap.add_argument("--no-config4", action="store_true", help="N > 1 humanoid runs also time BASELINE config 4 (32768 envs/GPU); skip it")
     ap.add_argument("--no-other-workloads", action="store_true", help="the default humanoid run also times BASELINE configs 3 (ant) and 5 (mesh scene); skip them")
     ap.add_argument("--no-long-run", action="store_true", help="skip the 1000-step run of the headline workload reported beside `value`")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write every non-empty array of the Data the last timed step returned as DIR/<leaf>.npy (float32 / float64; rank 0's environments, "
+                         f"a seeded sample of them when all would exceed {DUMP_CAP_BYTES // 10**6} MB)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args):
@@ -169,6 +180,42 @@ def build_inputs(mx, B, dtype, device, seed=42):
     if dtype != torch.float64:
         d = d.to(dtype)
     return d.to(device)
+
+
+def data_arrays(d, prefix=""):
+    """{name: tensor}: every per-environment array of a Data as its caller receives it; a nested container's leaves (contact) carry its name as
+    a prefix.  The model constants a Data carries (UnbatchedTensor: ncon, nefc) are not step outputs and are not listed."""
+    out = {}
+    for k, v in d.items():
+        if isinstance(v, mt.MjTensorClass):
+            out.update(data_arrays(v, prefix + k + "_"))
+        elif isinstance(v, torch.Tensor):
+            out[prefix + k] = v
+    return out
+
+
+def dump_outputs(d, out_dir, batch):
+    """--dump-outputs: every non-empty array of `d` as out_dir/<name>.npy, float32 arrays as float32 and all others (float64, integer, bool) as
+    float64.  Zero-size arrays (a model without actuator activations, tendons, contacts, ...) hold no value and are left out.  When the batch's
+    arrays would exceed DUMP_CAP_BYTES, every array keeps the same environments: a sorted sample drawn with DUMP_SAMPLE_SEED, identical from
+    run to run.  Copies leaf by leaf to the host: no device allocation."""
+    leaves = {n: t for n, t in data_arrays(d).items() if t.numel() > 0}
+    kind = {n: np.float32 if t.dtype == torch.float32 else np.float64 for n, t in leaves.items()}
+    per_env = sum(t.numel() // batch * np.dtype(kind[n]).itemsize for n, t in leaves.items())
+    n_env = min(batch, (DUMP_CAP_BYTES - 256 * len(leaves)) // per_env)  # (256: bound on one .npy header)
+    idx = None if n_env == batch else np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(batch, n_env, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in leaves.items():
+        a = t.detach().cpu().numpy()
+        if idx is not None:
+            a = a[idx]
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a.astype(kind[name], copy=False))
+        total += os.path.getsize(path)
+    assert total <= DUMP_CAP_BYTES, f"--dump-outputs wrote {total} bytes"
+    return {"dir": os.path.abspath(out_dir), "files": len(leaves), "bytes": total, "envs": n_env, "of_envs": batch,
+            "sample_seed": None if idx is None else DUMP_SAMPLE_SEED}
 
 
 def usable_cpus():
@@ -590,6 +637,9 @@ def main(args):
     allocs_in_region = LAST_TIMED.get("device_allocs")
     per_rank = LAST_TIMED.get("per_rank_ms_per_step")
     assert torch.isfinite(loop.d.qpos).all(), "non-finite state after the timed steps"
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before anything below steps `loop.d` further
+        dumped = dump_outputs(loop.d, args.dump_outputs, B)
     loop.pingpong(args.warmup)
     elapsed_pp, kernel_ms_pp = timed(loop.pingpong, args.steps, device, world, backend)  # extension: step(mx, a, out=b)
 
@@ -656,6 +706,8 @@ def main(args):
             line["other_workloads"] = others
         if config4 is not None:
             line["config4"] = config4
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         pfile = os.path.join(ROOT, "profiles", PROFILE_ROUND, "parity.json")
         if os.path.exists(pfile):  # "float64 max rel-err" half of BASELINE's metric: written by tests/test_gpu_parity.py::test_parity_report
             with open(pfile) as f:

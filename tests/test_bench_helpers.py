@@ -58,3 +58,33 @@ def test_survey_bytes_table_matches_the_workloads():
     for key, wl in b.WORKLOADS.items():
         d = "f64" if str(wl["dtype"]).endswith("float64") else "f32"
         assert (key, d) in b.SURVEY_8D_BYTES, key
+
+
+def test_dump_outputs_is_capped_seeded_and_float(tmp_path, monkeypatch):
+    """--dump-outputs: every non-empty array of the returned Data as float32 / float64 .npy, the same environments in every array, the same
+    sample from call to call, and under the size cap (checked here on the CPU Data of the ant workload with a cap small enough to force a sample)."""
+    import numpy as np
+    import torch
+
+    b = _bench()
+    wl = b.WORKLOADS["ant"]
+    lite = b.mt.mjcf.from_xml_path(b.mt.test_data_path(wl["xml"] + ".xml"))
+    mx = b.mt.device_put(lite, dtype=torch.float32)
+    B = 64
+    d = b.build_inputs(mx, B, torch.float32, "cpu")
+    whole = b.dump_outputs(d, str(tmp_path / "whole"), B)
+    assert whole["envs"] == B and whole["sample_seed"] is None
+    arrays = b.data_arrays(d)
+    names = sorted(n for n, t in arrays.items() if t.numel() > 0)
+    assert sorted(f[:-4] for f in os.listdir(tmp_path / "whole")) == names and "contact_dist" in names
+    assert arrays["act"].numel() == 0 and "act" not in names  # the ant has no actuator activations: nothing to write
+    qvel = np.load(tmp_path / "whole" / "qvel.npy")
+    assert qvel.dtype == np.float32 and np.array_equal(qvel, d.qvel.numpy())
+    monkeypatch.setattr(b, "DUMP_CAP_BYTES", whole["bytes"] // 4)
+    runs = [b.dump_outputs(d, str(tmp_path / f"s{i}"), B) for i in range(2)]
+    assert 0 < runs[0]["envs"] < B and runs[0]["bytes"] <= b.DUMP_CAP_BYTES and runs[0]["sample_seed"] is not None
+    for n in names:
+        x, y = (np.load(tmp_path / f"s{i}" / f"{n}.npy") for i in range(2))
+        assert x.size > 0 and x.dtype in (np.float32, np.float64) and np.array_equal(x, y) and x.shape[0] == runs[0]["envs"], n
+    idx = np.sort(np.random.RandomState(b.DUMP_SAMPLE_SEED).choice(B, runs[0]["envs"], replace=False))
+    assert np.array_equal(np.load(tmp_path / "s0" / "qvel.npy"), qvel[idx])
