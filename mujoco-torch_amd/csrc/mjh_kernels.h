@@ -207,8 +207,8 @@ struct RkWork {
   REAL *qvel0, *act0, *kqvel, *sum_qvel, *sum_qacc, *sum_actdot;
 };
 
-// All launch parameters travel as ONE by-value kernel argument.  Device code reads them through the kernarg
-// segment pointer (constant address space => scalar loads, nothing is copied to scratch).  That pointer only
+// All launch parameters travel as ONE by-value kernel argument (sizeof(KArgs<double>) = 3,896 B of the 4 KiB kernarg segment; mjhip.hip asserts
+// the bound).  Device code reads them through the kernarg segment pointer (constant address space => scalar loads, nothing is copied to scratch).  That pointer only
 // exists inside the kernel function itself, so everything below must inline into the kernel (build.sh checks
 // the ISA for calls).
 // the state leaves an advance writes (the only leaves of the "next stage" / "returned" Data the kernels touch)
@@ -247,13 +247,9 @@ struct KArgs {
   int hs_reals;
   REAL* cand;           // max_contact_points over convex pairs: candidate contacts of the convex narrow phase, [B, ncand] dist | [B, ncand, 3] pos | [B, ncand, 9] frame (workspace)
   const REAL* warm_src; // [B, nv] warm start of this pass: the caller's, or the previous RK stage's solution
-  int it_cap, ls_cap;   // > 0: the register solver leaves an environment to the fallback launch (LDS solver, one environment per wavefront) once its solve has run it_cap Newton iterations or ls_cap line-search iterations: the long solves of a batch are few, and inside a shared wavefront every one of them holds three other environments' lanes
   int mark_leftover;    // register solver, first tier with a second one behind it: an environment with more active rows than this tier keeps gets mjh_bail_mark in out.qacc
   int scan_marks;       // register solver, second tier: waves scan 64 environments' marks each and serve the marked ones (instead of one wave per environment pair counting rows)
-  int fallback_only;    // LDS solver launch: serve only the environments the register solver flagged (mjh_bail_mark in out.qacc)
   int row_lo, row_hi;   // register solver tiers: this launch serves the environments with row_lo < (dense rows of their active contacts) <= row_hi
-  const int* sol_perm;  // register solver, four environments per wavefront: environment served by each (wave, lane group) slot, sorted by the previous step's iteration counts (NULL: identity)
-  int* sol_key;         // ... and where this step's count of an environment goes (NULL: not recorded)
   unsigned long long* stamps;  // diagnostic builds (-DMJH_STAMPS): [B, 128] s_memtime stamps, else unused
 };
 template <typename REAL>
@@ -267,11 +263,6 @@ __device__ __forceinline__ const KArgs<REAL>& kargs() {
 #define KA (kargs<REAL>())
 // In-kernel stamps (diagnostic build only, never in the shipped library): lane 0 records the shader clock at
 // section boundaries into a buffer of its own; tools/stamps.py turns them into a per-section cycle profile.
-#ifdef MJH_SOL2_CAPS
-#define MJH_SOL2_CAPS_ON 1
-#else
-#define MJH_SOL2_CAPS_ON 0
-#endif
 #ifdef MJH_STAMPS
 #ifdef MJH_STAMPS_STAGE  /* -DMJH_STAMPS_STAGE=2: only the launches of that RK4 stage are recorded */
 #define MJH_STAMPS_STAGE_OK (KA.rk_stage == MJH_STAMPS_STAGE)
@@ -870,8 +861,8 @@ __device__ __forceinline__ REAL dot_seq(const REAL* a, int sa, const REAL* b, in
   return s;
 }
 
-// "left to the fallback launch": a quiet NaN with a payload, written to the first element of the environment's qacc row by the register
-// solver and tested (bit pattern) by the LDS solver's fallback launch.  It lives in the call's own output storage, so concurrent calls on
+// "left to the next tier": a quiet NaN with a payload, written to the first element of the environment's qacc row by the register
+// solver's first tier and tested (bit pattern) by the second tier's launch, which scans the marks.  It lives in the call's own output storage, so concurrent calls on
 // other streams / other Data never see each other's marks; a solve that legitimately ends in NaN never produces this payload.
 __device__ __forceinline__ float mjh_bail_mark(float) { return __builtin_bit_cast(float, 0x7fc5eed5u); }
 __device__ __forceinline__ double mjh_bail_mark(double) { return __builtin_bit_cast(double, 0x7ff80005eed5eed5ull); }
@@ -1030,12 +1021,6 @@ struct Env {
     }
     wave_sync();
     STAMP(8);
-    // Pointer jumping (DevModel::kin_tab; models with one body per lane).  The serial walk below has every lane compose its whole ancestor chain -- ~7 levels and ~10 joints of
-    // dependent float64 rotations for the humanoid, 35 k of the kernel's 309 k cycles, the same chain recomputed by every lane.  Here each lane first composes the frame of ITS body
-    // relative to its parent (body offset, then its own joints: smooth.py:85-120 in the parent's frame), then ceil(log2(depth)) rounds replace "relative to the ancestor 2^r levels
-    // up" by "relative to the ancestor 2^(r+1) levels up" (frame(a) o frame(b), through the xpos / xquat arrays of the arena), and the joints' anchors and axes, formed in the
-    // parent's frame, are carried to the world by one more rotation.  The same compositions as the walk in a different association: results agree to rounding (1e-16 relative),
-    // not bit for bit -- the parity bounds of the leaves upstream of the solver are 1e-9 (float64) / 2e-4 (float32).
     // one joint of a body (smooth.py:85-120): its anchor and axis in the frame (pos, quat) reached so far, then that frame moved by the joint
     auto joint_step = [&](int j, REAL* pos, REAL* quat, bool keep) {
       const int t = M.jnt_type[j], qa = M.jnt_qposadr[j];
@@ -1076,9 +1061,9 @@ struct Env {
     // that dependent chain: 35 k of the humanoid kernel's 278 k cycles for ~10 joints of arithmetic.  Here lane b owns body b: it reads ITS constants once, up front and all at once
     // (nothing of them depends on another lane), then the levels of the tree are swept in order -- at level L the lanes whose body sits L below the world take their parent's
     // finished frame from the arena, apply their own offset and joints, and put their frame down.  Every body's frame is formed by exactly the operations of the walk in exactly its
-    // order (the walk recomputes the parent's frame with the same operations on the same inputs): bit-identical leaves, unlike the pointer-jumping form below.
+    // order (the walk recomputes the parent's frame with the same operations on the same inputs): bit-identical leaves.
     // (Compiled into the whole-pass kernel only -- KEEPG -- for now: in the stand-alone kinematics kernels the constants' registers set the allocation, 80 -> 150 VGPRs in float32.)
-    const bool lvl = KEEPG && M.kin_lvl != 0 && M.nbody <= W && M.kin_tab == nullptr;
+    const bool lvl = KEEPG && M.kin_lvl != 0 && M.nbody <= W;
     if constexpr (KEEPG) if (lvl) {
       const int nb = M.nbody, md = M.max_depth;
       const int b = l;
@@ -1165,69 +1150,11 @@ struct Env {
       }
       STAMP(9);
     }
-    const bool jump = M.kin_tab != nullptr && M.nbody <= W;
-    const int* const kin_anc = M.kin_tab;
-    if (jump) {
-      const int nb = M.nbody, md = M.max_depth;
-      int R = 0;
-      while ((1 << R) < md) R++;
-      const REAL* const kin_start = reinterpret_cast<const REAL*>(reinterpret_cast<const unsigned char*>(M.kin_tab) + 8 * (((size_t)R * nb + 1) / 2));
-      const int b = l;
-      const bool body = b > 0 && b < nb;
-      REAL pos[3] = {0, 0, 0}, quat[4] = {1, 0, 0, 0};
-      int anc_r = 0;
-      if (body) {
-        anc_r = R > 0 ? kin_anc[b] : 0;
-#pragma unroll
-        for (int i = 0; i < 3; i++) pos[i] = kin_start[7 * b + i];
-#pragma unroll
-        for (int i = 0; i < 4; i++) quat[i] = kin_start[7 * b + 3 + i];
-        const int jn = M.body_jntnum[b], j0 = M.body_jntadr[b];
-        for (int jj = 0; jj < jn; jj++) joint_step(j0 + jj, pos, quat, true);  // (anchors / axes in the parent's frame: carried to the world below)
-      }
-      if (b == 0) {  // the world body: the frame the walk starts from
-#pragma unroll
-        for (int i = 0; i < 3; i++) pos[i] = M.body_pos[i];
-#pragma unroll
-        for (int i = 0; i < 4; i++) quat[i] = M.body_quat[i];
-      }
-      if (b < nb) {
-#pragma unroll
-        for (int i = 0; i < 3; i++) S.xpos()[3 * b + i] = pos[i];
-#pragma unroll
-        for (int i = 0; i < 4; i++) S.xquat()[4 * b + i] = quat[i];
-      }
-      wave_sync();
-      for (int r = 0; r < R; r++) {  // (uniform trip count)
-        const int a = anc_r;
-        REAL pa[3] = {0, 0, 0}, qa4[4] = {1, 0, 0, 0};
-        if (a > 0) {
-#pragma unroll
-          for (int i = 0; i < 3; i++) pa[i] = S.xpos()[3 * a + i];
-#pragma unroll
-          for (int i = 0; i < 4; i++) qa4[i] = S.xquat()[4 * a + i];
-        }
-        if (r + 1 < R) anc_r = body ? kin_anc[(r + 1) * nb + b] : 0;
-        wave_sync();  // every lane has read its ancestor's frame of this round
-        if (a > 0) {
-          REAL rr[3];
-          rotate(pos, qa4, rr);
-#pragma unroll
-          for (int i = 0; i < 3; i++) pos[i] = pa[i] + rr[i];
-          quat_mul(qa4, quat, quat);
-#pragma unroll
-          for (int i = 0; i < 3; i++) S.xpos()[3 * b + i] = pos[i];
-#pragma unroll
-          for (int i = 0; i < 4; i++) S.xquat()[4 * b + i] = quat[i];
-        }
-        wave_sync();
-      }
-    }
     for (int b = l; b < M.nbody; b += W) {
       REAL pos[3] = {M.body_pos[0], M.body_pos[1], M.body_pos[2]};
       REAL quat[4] = {M.body_quat[0], M.body_quat[1], M.body_quat[2], M.body_quat[3]};
       const int depth = M.body_depth[b], md = M.max_depth;
-      if (jump || lvl) {
+      if (lvl) {
 #pragma unroll
         for (int i = 0; i < 3; i++) pos[i] = S.xpos()[3 * b + i];
 #pragma unroll
@@ -1295,23 +1222,6 @@ struct Env {
       }
     }
     wave_sync();
-    if (jump) {  // anchors and axes of the joints of bodies below the first level: from the parent's frame to the world (the mocap override above touches no parent: mocap bodies have no children here)
-      for (int j = l; j < M.njnt; j += W) {
-        const int p = kin_anc[M.jnt_bodyid[j]];  // (round 0 of the table: the parent, 0 = the world; one level deep models have no table rows and no such joints)
-        if (M.max_depth > 1 && p > 0) {
-          const REAL* pq = S.xquat() + 4 * p;
-          const REAL* pp = S.xpos() + 3 * p;
-          REAL al[3], xl[3], r[3], x[3];
-#pragma unroll
-          for (int i = 0; i < 3; i++) { al[i] = S.xanchor()[3 * j + i]; xl[i] = S.xaxis()[3 * j + i]; }
-          rotate(al, pq, r);
-          rotate(xl, pq, x);
-#pragma unroll
-          for (int i = 0; i < 3; i++) { S.xanchor()[3 * j + i] = pp[i] + r[i]; S.xaxis()[3 * j + i] = x[i]; }
-        }
-      }
-      wave_sync();
-    }
     STAMP(2);
     // the frames go out now, ahead of the geom / site / camera loops: a phase's leaf stores are bursts of tens of MB issued by every wave at the same
     // moment, and the first table read behind one waits until L2 has taken it (vmcnt is in order) -- several smaller bursts with arithmetic between them drain
@@ -2181,7 +2091,7 @@ struct Env {
           diff[3 + r] = fr[3 * r] * dr[0] + fr[3 * r + 1] * dr[1] + fr[3 * r + 2] * dr[2];
         }
         // RK4 stages 1..3 with a hand-over: the solver reads the compact copy only -- the workspace leaf is not written
-        REAL* const dstA = (hsJ && scratch_stage && !MJH_SOL2_CAPS_ON) ? nullptr : Jdst + row0 * nv + d;  // (a build with the iteration caps hands capped solves to the LDS solver, which reads the leaves)
+        REAL* const dstA = (hsJ && scratch_stage) ? nullptr : Jdst + row0 * nv + d;
         REAL* const dstB = hsJ ? hsJ + (a * M.con_rows) * nv + d : nullptr;
         if (dim == 1) {
           if (dstA) dstA[0] = diff[0];
@@ -2345,7 +2255,7 @@ struct Env {
       else {
         // this wave stored the row above and the barrier drained the stores to L2.  Agent-scope loads read L2 past the CU's L1,
         // where a line shared with a neighbouring environment's rows could have been cached before this wave's stores landed.
-        const REAL* jr = (hs_row >= 0 && !MJH_SOL2_CAPS_ON) ? hsJ + hs_row * nv : out.efc_J + (e * nefc + r) * nv;  // (RK4 stages 1..3 with a hand-over keep the row there only)
+        const REAL* jr = hs_row >= 0 ? hsJ + hs_row * nv : out.efc_J + (e * nefc + r) * nv;  // (RK4 stages 1..3 with a hand-over keep the row there only)
         REAL s = 0;
         int k = 0;
         for (; k + 4 <= nv; k += 4) {
@@ -2358,7 +2268,7 @@ struct Env {
       }
       const REAL aref_r = -b * jv - k * imp * pos, D_r = 1 / rr;
       if (hs_row >= 0) { hs[1 + M.ncon + hs_row] = D_r; hs[1 + M.ncon + (nefc - nl) + hs_row] = aref_r; }
-      if (hs_row >= 0 && KA.rk_stage > 0 && !MJH_SOL2_CAPS_ON) continue;  // (stages 1..3: the solver reads the hand-over, nobody the workspace leaves of a contact row)
+      if (hs_row >= 0 && KA.rk_stage > 0) continue;  // (stages 1..3: the solver reads the hand-over, nobody the workspace leaves of a contact row)
       if (stage_ad) { ad_stage[r] = aref_r; ad_stage[nefc + r] = D_r; }
       else {
         if (out.efc_aref) out.efc_aref[e * nefc + r] = aref_r;  // lane r <-> row r: coalesced, no staging
@@ -4021,10 +3931,6 @@ struct Env {
     const int l = lane_here();
     const int nq = M.nq, nv = M.nv, na = M.na;
     STAMP0();
-    if (KA.fallback_only) {  // second launch behind the iteration-capped register solver: only the environments it flagged (wave-uniform: one environment per wavefront)
-      const REAL q0 = __hip_atomic_load(out.qacc + e * nv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (!mjh_is_bail_mark(q0)) return;
-    }
     load_factor_and_accelerate((KA.stages & 0x40) != 0);
     if (!(KA.stages & 0x40)) return;  // forward() with a stage prefix that ends at _acceleration
     STAMP(53);
@@ -4348,7 +4254,7 @@ struct Env {
     // instantiation picks up the rest (the ant keeps 4 - 8 of its 60 contacts active: almost none).  Each environment is integrated by exactly one.
     STAMP(82);
     if (!(nda > KA.row_lo && nda <= KA.row_hi)) {
-      if (((MJH_SOL2_CAPS_ON && KA.it_cap > 0) || KA.mark_leftover) && nda > KA.row_hi && l == 0) out.qacc[e * nv] = mjh_bail_mark((REAL)0);  // the next launch (wider tier / LDS-solver fallback) finds the environment by this mark
+      if (KA.mark_leftover && nda > KA.row_hi && l == 0) out.qacc[e * nv] = mjh_bail_mark((REAL)0);  // the next launch (the wider tier) finds the environment by this mark
       return;
     }
     if (solving) {
@@ -4743,10 +4649,7 @@ struct Env {
       REAL Mgrad = 0, search = 0;
       bool first_dir = true;
       REAL* pg = S.r_pg();  // previous gradient / M^-1 gradient of the Polak-Ribiere step
-      int it = 0, niter = 0, ls_total = 0;
-      bool bail = false;
-      // (iteration caps: measured slower than letting the packed tier finish its solves, profiles/r03/notes.md -- compiled in only with -DMJH_SOL2_CAPS, so the kernels do not carry their bookkeeping)
-      const int it_cap = MJH_SOL2_CAPS_ON ? KA.it_cap : 0, ls_cap = MJH_SOL2_CAPS_ON ? KA.ls_cap : 0;
+      int it = 0, niter = 0;
       for (;;) {
         if (ONE || M.iterations == 1) { if (it >= 1) break; }  // (ONE: the launch has checked opt.iterations == 1 -- a compile-time trip count of one)
         else if (fixed) { if (it >= M.iterations) break; }
@@ -4759,7 +4662,6 @@ struct Env {
           done |= gradient < (REAL)M.tolerance;
           if (done) break;
         }
-        if (it_cap > 0 && (it >= it_cap || ls_total >= ls_cap)) { bail = true; break; }  // another iteration is due: the fallback launch redoes this solve from its inputs
         const bool need_grad = ONE ? false : !(it + 1 >= M.iterations);
         {  // search direction of this iteration: -H^-1 grad (Newton), -M^-1 grad at the start, Polak-Ribiere afterwards (CG, :519-523)
           const REAL Mg = precondition(grad);
@@ -4891,12 +4793,10 @@ struct Env {
               const bool s6 = ls_swap(hi2.d0, lo_next.d0, nb); if (s6) hi2 = lo_next;
               swap = s1 | s2 | s3 | s4 | s5 | s6;
               ls_iter++;
-              if (it_cap > 0 && ls_total + ls_iter >= ls_cap) { bail = true; break; }
             }
-            if (!bail) {  // (the bracket ends are the same in every lane of the environment: uniform branches around the reductions)
-              if (!lo2.hc) lo2.cost = cost_of(lo2);
-              if (!hi2.hc) hi2.cost = cost_of(hi2);
-            }
+            // (the bracket ends are the same in every lane of the environment: uniform branches around the reductions)
+            if (!lo2.hc) lo2.cost = cost_of(lo2);
+            if (!hi2.hc) hi2.cost = cost_of(hi2);
             lo.alpha = lo2.alpha; lo.cost = lo2.cost; lo.d0 = lo2.d0; lo.d1 = lo2.d1;
             hi.alpha = hi2.alpha; hi.cost = hi2.cost; hi.d0 = hi2.d0; hi.d1 = hi2.d1;
           } else
@@ -4921,10 +4821,7 @@ struct Env {
             const bool s6 = ls_swap(hi.d0, lo_next.d0, nb); if (s6) hi = lo_next;
             swap = s1 | s2 | s3 | s4 | s5 | s6;
             ls_iter++;
-            if (it_cap > 0 && ls_total + ls_iter >= ls_cap) { bail = true; break; }
           }
-          ls_total += ls_iter;
-          if (bail) break;
           const REAL improved = (REAL)((lo.cost < p0.cost) || (hi.cost < p0.cost));
           const REAL alpha = lo.cost < hi.cost ? lo.alpha : hi.alpha;
           qacc = qacc + improved * search * alpha;
@@ -4941,11 +4838,6 @@ struct Env {
         STAMP(78);
         if (need_grad) grad = dof ? (Ma - f) - qfrc : (REAL)0;  // _update_gradient :359-376, the part cond reads (its preconditioned half: next loop head)
         niter++; it++;
-      }
-      if (W == 16 && KA.sol_key && l == 0) { const int k = 6 * niter + ls_total; KA.sol_key[e] = k < 63 ? k : 63; }  // ~ the solve's cost: a Newton iteration (Hessian build + factorisation) weighs about six line-search iterations
-      if (bail) {  // nothing of this environment's solve is kept: the mark hands it to the fallback launch, which writes every output of the phase
-        if (l == 0) out.qacc[e * nv] = mjh_bail_mark((REAL)0);
-        return;
       }
       rebind();
       if (newton) {  // the Hessian weights overwrote the staged forces: stage the final ones for the row-order store below
@@ -5125,10 +5017,7 @@ __global__ void __launch_bounds__(MJH_WAVE, (sizeof(REAL) == 4 && NMAX == 8 && W
   {
     const int64_t idx = blk * NSUB + sub;
     if (idx < K.env_count) {
-      // W = 16: the four environments of a wave run until the slowest has converged.  They are drawn from a list sorted by the previous step's iteration counts
-      // (mjh_sort_kernel), so that long solves share waves; which environments share a wave changes nothing in any of them.
-      const int64_t env = (W == 16 && K.sol_perm) ? (int64_t)K.sol_perm[idx] : idx;
-      Env<REAL, W, false> E(lds, K.env_begin + env, K.flags);
+      Env<REAL, W, false> E(lds, K.env_begin + idx, K.flags);
       if constexpr (ALL) {
         // Out of lockstep (round 6).  A batch of one round of waves starts every wave at the same moment on the same program: all of them are in an arithmetic section, then all of them in
         // a store burst (a lone wave runs the kernel in 108 us, 2048 of them in 142; delaying half of the workgroups by 19 us cost 4 us: profiles/r06/notes.md).  crb / factor and the
@@ -5199,7 +5088,7 @@ __global__ void __launch_bounds__(MJH_WAVE, (sizeof(REAL) == 4 && NMAX == 8 && W
 }
 
 template <typename REAL, int PHASE, int W>
-__global__ void __launch_bounds__((PHASE == 17 ? 2 * MJH_WAVE : MJH_WAVE), ((sizeof(REAL) == 4 && PHASE == 17 && W < 64) ? MJH_KCV2_WAVES : (sizeof(REAL) == 4 && PHASE == 8) ? MJH_CON32D_WAVES : (sizeof(REAL) == 4 && PHASE == 4) ? MJH_SOL32_WAVES : (sizeof(REAL) == 4 && (PHASE == 6 || ((PHASE == 0 || PHASE == 3) && W < 64))) ? 3 : (sizeof(REAL) == 4 && PHASE == 13 && W < 64) ? MJH_KCV32_WAVES : (sizeof(REAL) == 4 && PHASE == 12 && W < 64) ? MJH_KV32_WAVES : ((sizeof(REAL) == 4 && PHASE == 1) ? (W < 64 ? MJH_CRB32P_WAVES : 4) : ((sizeof(REAL) == 8 && PHASE == 2) ? (W < 64 ? 2 : MJH_CON64_WAVES) : ((sizeof(REAL) == 8 && (PHASE == 12 || PHASE == 13)) ? 2 : ((sizeof(REAL) == 8 && PHASE == 1 && W == 64) ? 4 : 1)))))) mjh_phase_kernel(KArgs<REAL> args) {
+__global__ void __launch_bounds__((PHASE == 17 ? 2 * MJH_WAVE : MJH_WAVE), ((sizeof(REAL) == 4 && PHASE == 17 && W < 64) ? MJH_KCV2_WAVES : (sizeof(REAL) == 4 && PHASE == 8) ? MJH_CON32D_WAVES : (sizeof(REAL) == 4 && PHASE == 4) ? MJH_SOL32_WAVES : (sizeof(REAL) == 4 && (PHASE == 6 || ((PHASE == 0 || PHASE == 3) && W < 64))) ? 3 : (sizeof(REAL) == 4 && PHASE == 13 && W < 64) ? MJH_KCV32_WAVES : (sizeof(REAL) == 4 && PHASE == 12 && W < 64) ? MJH_KV32_WAVES : ((sizeof(REAL) == 4 && PHASE == 1) ? (W < 64 ? MJH_CRB32P_WAVES : 4) : ((sizeof(REAL) == 8 && PHASE == 2) ? MJH_CON64_WAVES : ((sizeof(REAL) == 8 && (PHASE == 12 || PHASE == 13)) ? 2 : ((sizeof(REAL) == 8 && PHASE == 1 && W == 64) ? 4 : 1)))))) mjh_phase_kernel(KArgs<REAL> args) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const KArgs<REAL>& K = kargs<REAL>();
   constexpr int NSUB = MJH_WAVE / W;  // environments per wavefront: W lanes each, their own LDS arena each

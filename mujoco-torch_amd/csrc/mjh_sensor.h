@@ -303,18 +303,12 @@ __global__ __launch_bounds__(MJH_WAVE, (sizeof(REAL) == 4 && FULL == 0) ? MJH_SE
     const int64_t e0 = KA.env_begin + (int64_t)blockIdx.x * epw;
     const int here = (int)((KA.env_begin + KA.env_count - e0) < epw ? (KA.env_begin + KA.env_count - e0) : epw);  // environments of this workgroup
     const float inv_nrf = 1.0f / (float)(nrf > 0 ? nrf : 1), inv_nsd = 1.0f / (float)(nsd > 0 ? nsd : 1);
-#ifdef MJH_SENSOR_ABLATE
-    if (!(KA.flags & 0x100))
-#endif
     for (int t = lane_id(); t < here * nrf; t += MJH_WAVE) {
       int k, q;
       split_index(t, nrf, inv_nrf, k, q);
       rf_x[k * (nrf + 1) + q] = rf_task<REAL>(e0 + k, q);
     }
     wave_sync();
-#ifdef MJH_SENSOR_ABLATE
-    if (!(KA.flags & 0x200))
-#endif
     for (int t = lane_id(); t < here * nsd; t += MJH_WAVE) {
       int ke, k;
       split_index(t, nsd, inv_nsd, ke, k);

@@ -8,7 +8,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -40,7 +39,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 static struct {
   bool on = false;
   int n = 0;                          // launches recorded by the last call
-  int id[MJH_TIMING_MAX];             // 0..8 phase-kernel ids, 9 register solver, 10 convex narrow phase, 11 sensors, 12 / 13 fused kinematics (+ crb) + velocity, 14 fused constraint + register solver
+  int id[MJH_TIMING_MAX];             // 0..8 phase-kernel ids, 9 register solver, 10 convex narrow phase, 11 sensors, 12 / 13 / 17 fused kinematics (+ crb) + velocity, 14 fused constraint + register solver, 16 whole pass, 18 / 19 stage kernel (15: unassigned)
   hipEvent_t ev[MJH_TIMING_MAX + 1];  // ev[i] .. ev[i + 1] brackets launch i
 } g_timing;
 static inline void timing_begin(hipStream_t s) { if (g_timing.on) { g_timing.n = 0; (void)hipEventRecord(g_timing.ev[0], s); } }
@@ -71,16 +70,14 @@ struct mjhModel {
   int kcv2 = 0;                            // a step launches the two-wave form instead of kernel 13 ...
   int64_t kcv2_max_envs = 0;               // ... forced on (MJH_KCV2=1): any batch; otherwise 0 and the limit is kcv2_limit() of the LAUNCH's device
   int kcv2_per_wg = 0, kcv2_envs_per_wg = 0; // arena bytes and environments of one of its workgroups
-  int64_t kcv_max_envs = 0;                // ... while the batch is ONE round of that kernel's waves (it needs more registers than either of its parts: two waves per SIMD)
   int sol2_tiers = 0;                      // 1: a first launch with ONE row slot per lane serves the environments whose active contacts fit 32 dense rows
   int sol2_w16_rpl = 0;                    // > 0: that first launch runs FOUR environments per wavefront (16 lanes each, nv <= 16) with this many row slots per lane
   int sol2_w16_nmax = 0;                   // ... instantiated for 8, 12 or 16 dofs
-  int sol2_it_cap = 0, sol2_ls_cap = 0;    // > 0: that launch leaves long solves (Newton iterations / line-search iterations beyond the caps) to a fallback launch of the LDS solver
   LdsOff off_tier;                         // ... from an arena of its own (32 rows of efc_J instead of all of them)
   int lds_tier = 0;
   int fuse_all = 0;                        // ... and the whole pass as ONE kernel (mjh_sol2_kernel<.., 34>, timing id 16): kernel 13's stages in front of kernel 14's, one arena of max(lds_kcv, lds_cs)
   int lds_all = 0;
-  int fuse_stage = 0;                      // RK4 stages 1..3 of a small Newton model run as ONE launch each (mjh_sol2_kernel<.., 18>, timing id 18): kernel 13's stages, the constraint phase (kernel 8) and the register solver's first tier
+  int fuse_stage = 0;                      // every RK4 stage of a small Newton model runs as ONE launch (mjh_sol2_kernel<.., 18>, timing id 18; stage 0 too unless MJH_FUSE_STAGE0=0): kernel 13's stages, the constraint phase (kernel 8) and the register solver's first tier
   int lds_stage = 0;                       // ... dynamic LDS of one of its four-environment workgroups
   int fuse_tail = 0;                       // the tail of a pass -- constraint phase + the solver's first tier + integrator -- as ONE launch of the same kernel (parts 2 | 4): small Newton models whose pass cannot be one launch (convex narrow phase or sensors between the parts, Euler)
   int lds_tail = 0;
@@ -89,27 +86,8 @@ struct mjhModel {
   int lds_cs = 0;
   int pack2[MJH_NPHASE];                   // phase runs two environments per wavefront
   int pack4[MJH_NPHASE];                   // ... or four (16 lanes each): small models only
-  // hipGraph replay: the launch sequence of a (buffers, batch, flags) combination is captured once on a private stream and
-  // replayed with one hipGraphLaunch on the caller's stream -- a step is 6 launches (24 with RK4) with ~3.6 KB of kernel
-  // arguments each, which costs more host time than a small batch takes on the device
-  struct GraphEntry { unsigned long long key; hipGraphExec_t exec; unsigned long long last_use; };
-  mutable std::vector<GraphEntry> graphs;
-  mutable std::mutex graph_mutex;
-  mutable hipStream_t capture_stream = nullptr;
-  mutable unsigned long long graph_clock = 0;
-  mutable std::mutex split_mutex;          // MJH_SPLIT: internal streams the slices of a batch run on, fork / join events
-  mutable bool split_ready = false;
-  mutable hipStream_t split_stream[4] = {nullptr, nullptr, nullptr, nullptr};
-  mutable hipEvent_t split_done[4] = {nullptr, nullptr, nullptr, nullptr};
-  mutable hipEvent_t split_fork = nullptr;
-  mutable std::mutex dag_mutex;            // MJH_DAG=1 (experiment): crb / factor and velocity kernels beside the constraint phase on two internal streams
-  mutable bool dag_ready = false;
-  mutable hipStream_t dag_stream[2] = {nullptr, nullptr};
-  mutable hipEvent_t dag_fork = nullptr, dag_done[2] = {nullptr, nullptr};
-  // the sensor kernel needs nothing of CRB / CON / SOL: it runs on a stream of its own beside them (forked behind the velocity stage, joined at the end of the pass)
   int cvx_lds_bytes;                       // LDS scratch of one (environment, convex pair) wave
   int64_t work_reals;                      // per-environment REALs of workspace: RK4 stage Data and sums + the convex candidates of max_contact_points (0 for most Euler models)
-  int64_t sort_reals = 0;                  // ... of which the register solver's environment list and iteration-count keys (two ints per environment, at the very head)
   int64_t hs_reals = 0;                    // ... of which the constraint phase's hand-over to the register solver (KArgs::hs): small models with one contact condim
   int64_t cand_reals = 0;                  // ... of which the candidate contacts (at the HEAD of the workspace: its first B * cand_reals reals; the RK4 stage Data and sums follow)
   std::vector<int64_t> leaf_count;         // per-env element count of every real Data leaf, ABI order
@@ -369,51 +347,9 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
         }
       }
     M.max_jnt = max_jnt;
-    {  // kinematics by pointer jumping (Env::kinematics): ancestors at distance 2^r and the bodies' start frames
-      // Round 6: OPT-IN.  MJH_KIN_JUMP=1: pointer jumping for every tree of two levels or more; unset / 0: the serial walk, whose association of the
-      // frame compositions is the reference's (smooth.py:85-113) and the oracle's.  The two forms agree to rounding (1e-13 of each leaf's scale), not bit for bit; as round 5's default
-      // for deep trees it bought 2.4 % on the humanoid (142.0 -> 138.7 us) and cost config 2 its parity margin (pre-solver 2.8e-14 -> 6.9e-12, contact_dist element-wise 8.9e-10 against
-      // a 1e-8 bound), and a solver run to convergence amplified the last-bit difference past that bound in one stress case -- which round 5 hid behind a gate on opt.iterations, an
-      // unrelated solver setting.  The selection is now structural only (depth, nbody, no mocap body with children) and never changes with solver options.
-      static const int mode = [] { const char* e = getenv("MJH_KIN_JUMP"); return e ? (e[0] == '0' ? 0 : 1) : 0; }();
-      bool mocap_parent = false;  // a mocap body with a child: the reference overrides mocap frames AFTER its scan (smooth.py:85-113), so children hang off the STATIC body_pos /
-      //                             body_quat chain; the jump form's anchor / axis pass reads the parent's frame after the override -- such models keep the walk
-      for (int b = 1; b < nb; b++) if (d->body_parentid[b] > 0 && d->body_mocapid[d->body_parentid[b]] >= 0) mocap_parent = true;
-      const bool on = mode == 1 && max_depth >= 2 && !mocap_parent;
-      M.kin_tab = nullptr;
-      {  // the level sweep (Env::kinematics): same operations per body as the walk, bit-identical; MJH_KIN_LEVEL=0 keeps the walk (A / B runs)
-        static const int lv = [] { const char* e = getenv("MJH_KIN_LEVEL"); return e ? (e[0] != '0') : 1; }();
-        M.kin_lvl = (lv && nb > 1 && nb <= 32 && !on) ? 1 : 0;  // (nb <= 32: one body per lane in EVERY instantiation the model can run at, as for the jump form below)
-      }
-      int R = 0;
-      while ((1 << R) < max_depth) R++;
-      if (on && nb > 1 && nb <= 32) {  // (one body per lane in EVERY instantiation the model can run at -- 16 lanes per environment only with nbody <= 16, else 32 or 64 -- so that which kernel a batch size or an odd tail selects never changes a bit)
-        const size_t anc_bytes = 8 * (((size_t)R * nb + 1) / 2);
-        std::vector<unsigned char> tab(anc_bytes + sizeof(REAL) * (size_t)nb * 7, 0);
-        int* anc = reinterpret_cast<int*>(tab.data());
-        REAL* start = reinterpret_cast<REAL*>(tab.data() + anc_bytes);
-        const double wq[4] = {d->body_quat[0], d->body_quat[1], d->body_quat[2], d->body_quat[3]}, wp[3] = {d->body_pos[0], d->body_pos[1], d->body_pos[2]};
-        const bool world_identity = wq[0] == 1 && wq[1] == 0 && wq[2] == 0 && wq[3] == 0 && wp[0] == 0 && wp[1] == 0 && wp[2] == 0;
-        for (int b = 1; b < nb; b++) {
-          for (int r = 0; r < R; r++) { const int k = depth[b] - 1 - (1 << r); anc[(size_t)r * nb + b] = k >= 0 ? chain[(size_t)b * max_depth + k] : 0; }
-          for (int i = 0; i < 3; i++) start[(size_t)b * 7 + i] = (REAL)d->body_pos[3 * b + i];
-          for (int i = 0; i < 4; i++) start[(size_t)b * 7 + 3 + i] = (REAL)d->body_quat[4 * b + i];
-          if (depth[b] == 1 && !world_identity) {  // (never the case for a compiled MuJoCo model; kept equal to the walk's arithmetic, in REAL)
-            REAL p[3] = {(REAL)wp[0], (REAL)wp[1], (REAL)wp[2]}, q[4] = {(REAL)wq[0], (REAL)wq[1], (REAL)wq[2], (REAL)wq[3]};
-            const REAL bp[3] = {(REAL)d->body_pos[3 * b], (REAL)d->body_pos[3 * b + 1], (REAL)d->body_pos[3 * b + 2]};
-            const REAL bq[4] = {(REAL)d->body_quat[4 * b], (REAL)d->body_quat[4 * b + 1], (REAL)d->body_quat[4 * b + 2], (REAL)d->body_quat[4 * b + 3]};
-            const REAL sc = q[0], *u = q + 1;
-            const REAL uv = u[0] * bp[0] + u[1] * bp[1] + u[2] * bp[2], uu = u[0] * u[0] + u[1] * u[1] + u[2] * u[2];
-            const REAL c[3] = {u[1] * bp[2] - u[2] * bp[1], u[2] * bp[0] - u[0] * bp[2], u[0] * bp[1] - u[1] * bp[0]};
-            for (int i = 0; i < 3; i++) start[(size_t)b * 7 + i] = p[i] + ((2 * (uv * u[i]) + (sc * sc - uu) * bp[i]) + 2 * sc * c[i]);
-            start[(size_t)b * 7 + 3] = q[0] * bq[0] - q[1] * bq[1] - q[2] * bq[2] - q[3] * bq[3];
-            start[(size_t)b * 7 + 4] = q[0] * bq[1] + q[1] * bq[0] + q[2] * bq[3] - q[3] * bq[2];
-            start[(size_t)b * 7 + 5] = q[0] * bq[2] - q[1] * bq[3] + q[2] * bq[0] + q[3] * bq[1];
-            start[(size_t)b * 7 + 6] = q[0] * bq[3] + q[1] * bq[2] - q[2] * bq[1] + q[3] * bq[0];
-          }
-        }
-        fix.push_back({(const void**)&M.kin_tab, bb.add(tab.data(), tab.size())});
-      }
+    {  // the level sweep (Env::kinematics): same operations per body as the walk, bit-identical; MJH_KIN_LEVEL=0 keeps the walk (A / B runs)
+      static const int lv = [] { const char* e = getenv("MJH_KIN_LEVEL"); return e ? (e[0] != '0') : 1; }();
+      M.kin_lvl = (lv && nb > 1 && nb <= 32) ? 1 : 0;  // (nb <= 32: one body per lane in EVERY instantiation the model can run at -- 16 lanes per environment only with nbody <= 16, else 32 or 64 -- so that which kernel a batch size or an odd tail selects never changes a bit)
     }
     fix.push_back({(const void**)&M.chain_dof, bb.add(chain_dof.data(), sizeof(int) * chain_dof.size())});
     fix.push_back({(const void**)&M.chain_jnt, bb.add(chain_jnt.data(), sizeof(int) * chain_jnt.size())});
@@ -621,16 +557,6 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
         if (4 * out->lds_tier <= 64 * 1024) {
           out->sol2_tiers = 1; out->sol2_w16_rpl = w16_rpl;
           out->sol2_w16_nmax = d->nv <= 8 ? 8 : (d->nv <= 12 ? 12 : 16);
-          // Opt-in (MJH_SOL2_ITCAP / MJH_SOL2_LSCAP > 0): long Newton solves leave the packed tier once they pass the caps and are redone by the LDS
-          // solver, which gives ONE environment all 64 lanes.  Measured on the mesh scene (B = 8192, profiles/r03/notes.md): solver
-          // phase 257 us without caps, 323 / 346 / 377 / 407 us with caps of 2/6, 3/8, 4/12, 5/20 iterations / line-search iterations -- redoing a long
-          // solve from its inputs at one environment per wavefront costs more than the three lane groups it frees, so the default is no caps.
-          static const int it_env = [] { const char* e = getenv("MJH_SOL2_ITCAP"); return e ? atoi(e) : -1; }();
-          static const int ls_env = [] { const char* e = getenv("MJH_SOL2_LSCAP"); return e ? atoi(e) : -1; }();
-          if (it_env >= 0) out->sol2_it_cap = it_env;
-          if (ls_env >= 0) out->sol2_ls_cap = ls_env;
-          if (out->sol2_it_cap <= 0 || out->sol2_ls_cap <= 0) out->sol2_it_cap = out->sol2_ls_cap = 0;
-          if (d->solver != SOL_NEWTON || (d->nf > 0 || d->nft > 0 || d->ne > 0 || d->nlb > 0 || d->nlt > 0)) out->sol2_it_cap = out->sol2_ls_cap = 0;  // the fallback is kernel 4
         }
       }
       if (!out->sol2_tiers && rpl > 1 && !tiers_off) {
@@ -675,21 +601,11 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
     const int64_t nd = (int64_t)d->nefc - d->nl;
     // Measured (MI355X, profiles/r05/notes.md): ant (RK4: stages 1..3 write the hand-over INSTEAD of their workspace leaves) solver phase 44.7 -> 42.3 us per stage, constraint phase unchanged;
     // mesh scene (Euler: the leaves AND the hand-over) solver 197.9 -> 194.4 us but constraint phase 47.2 -> 52.0: RK4 models only.
-    // (a -DMJH_SOL2_CAPS build bypasses the hand-over in the solver: it is not written there either -- ADVICE r05)
-    out->hs_reals = (!off && !MJH_SOL2_CAPS_ON && d->integrator == INT_RK4 && M.con_direct && M.crow_by_con && out->sol2_nmax && !out->fuse_cs && nd > 0) ? ((1 + (int64_t)d->ncon + 2 * nd + nd * d->nv + 3) & ~(int64_t)3) : 0;
+    out->hs_reals = (!off && d->integrator == INT_RK4 && M.con_direct && M.crow_by_con && out->sol2_nmax && !out->fuse_cs && nd > 0) ? ((1 + (int64_t)d->ncon + 2 * nd + nd * d->nv + 3) & ~(int64_t)3) : 0;
     out->work_reals += out->hs_reals;
   }
   out->cand_reals = (d->topk && M.ncvxpair > 0) ? 13 * (int64_t)d->ncand : 0;  // candidate contacts of the convex narrow phase (dist, pos, frame)
   out->work_reals += out->cand_reals;
-  {  // register solver at four environments per wavefront with solves of uneven length (Newton): two ints per environment at the head of the workspace -- the solver's
-     // slot -> environment list of this step and the iteration-count key each environment leaves for the next one.
-    // Measured (MI355X, profiles/r04/notes.md): the mesh scene's solver phase 203.1 us with the list against 203.9 us without -- last step's counts do not predict this
-    // step's (which environments take the long line searches changes from step to step) -- and the one-workgroup sort costs 14.6 us at B = 8192, 30.7 us at B = 16384:
-    // opt-in (MJH_SOL2_SORT=1), off by default.
-    static const bool on = [] { const char* e = getenv("MJH_SOL2_SORT"); return e && e[0] == '1'; }();
-    out->sort_reals = (on && out->sol2_w16_rpl && d->solver == SOL_NEWTON) ? (int64_t)(8 / sizeof(REAL)) : 0;
-    out->work_reals += out->sort_reals;
-  }
 
   void* dev = nullptr;
   HIP_TRY(hipMalloc(&dev, bb.host.size() + 16));
@@ -727,13 +643,6 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, 8, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * out->lds_bytes[2]));
     out->pack2[2] = 1;
   }
-  {  // experiment (MJH_CON2_PACK=1): the plain constraint phase of a mid-size model at two environments per wavefront
-    static const bool con2 = [] { const char* e = getenv("MJH_CON2_PACK"); return e && e[0] == '1'; }();
-    if (con2 && !M.con_direct && !M.con_general && 2 * out->lds_bytes[2] <= 64 * 1024) {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, 2, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * out->lds_bytes[2]));
-      out->pack2[2] = 1;
-    }
-  }
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, 8, MJH_WAVE>), hipFuncAttributeMaxDynamicSharedMemorySize, out->lds_bytes[2]));  // plain constraint phase: its contact rows go straight to the leaf, the arena is small enough for two per wavefront
   // CRB: the register Cholesky keeps one matrix row per lane, so nv <= 32 would fit a 32-lane half too; measured on the float64
   // humanoid (nv 27) two per wavefront is SLOWER, 50.2 vs 39.9 us (132 VGPRs: 3 waves / SIMD instead of 4, and every broadcast of the
@@ -763,14 +672,8 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
     const bool same_pack = out->pack2[1] == (out->pack2[0] && out->pack2[3] && 2 * out->lds_kv <= 64 * 1024) && out->pack4[1] == (out->pack4[0] && out->pack4[3] && 4 * out->lds_kv <= 64 * 1024);
     out->fuse_kcv = (!off && out->fuse_kv && same_pack && out->pack2[1] && out->lds_kcv <= 160 * 1024 && 2 * out->lds_kcv <= 64 * 1024 && (!out->pack4[1] || 4 * out->lds_kcv <= 64 * 1024)) ? 1 : 0;
     if (out->fuse_kcv) {
-      // measured (MI355X, profiles/r03/notes.md): mesh scene, B = 8192 = one round of 2048 four-environment waves at two per SIMD: 45.3 us against 33.7 + 20.4 in two launches;
-      // ant, B = 16384 = two rounds: 95.7 us against 76.4 + 20.9 -- the separate kernels fit four waves per SIMD.  Larger batches keep the separate launches.
-      int dev = 0, cus = 256;
-      if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      out->kcv_max_envs = (int64_t)cus * 4 /* SIMDs */ * 2 /* waves per SIMD */ * (out->pack4[1] ? 4 : 2);
-      out->kcv_max_envs = (int64_t)1 << 62;  // round 4: at every batch size -- the humanoid (two per wavefront) at B = 32768: 652 us against 452 + 218; the ant (four per wavefront) at B = 16384, two rounds: 93.6 us against 75.8 + 21.8 (profiles/r04/notes.md)
-      static const long long kcv_env = [] { const char* e = getenv("MJH_KCV_MAX_ENVS"); return e ? atoll(e) : -1ll; }();  // experiments: the batch bound of kernel 13
-      if (kcv_env >= 0) out->kcv_max_envs = kcv_env;
+      // at every batch size (round 4; round 3 had kept the separate launches past one round of waves): the humanoid (two per wavefront) at B = 32768: 652 us against 452 + 218;
+      // the ant (four per wavefront) at B = 16384, two rounds: 93.6 us against 75.8 + 21.8 (profiles/r04/notes.md)
       HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, 13, MJH_WAVE>), hipFuncAttributeMaxDynamicSharedMemorySize, out->lds_kcv));
       HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, 13, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * out->lds_kcv));
       if (out->pack4[1]) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, 13, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * out->lds_kcv));
@@ -832,12 +735,12 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
       }
     }
   }
-  {  // One launch per RK4 stage (stages 1..3) for small Newton models: kernel 13 at four environments per wavefront, the direct constraint phase (kernel 8, two per wavefront: run twice
-     // per wave) and the solver's packed Newton tier at four, behind one another in mjh_sol2_kernel<.., 18>.  MJH_FUSE_STAGE=0: the three launches.
+  {  // One launch per RK4 stage (stage 0 too, unless MJH_FUSE_STAGE0=0) for small Newton models: kernel 13 at four environments per wavefront, the direct constraint phase (kernel 8, two
+     // per wavefront: run twice per wave) and the solver's packed Newton tier at four, behind one another in mjh_sol2_kernel<.., 18>.  MJH_FUSE_STAGE=0: the three launches.
     static const bool off = [] { const char* e = getenv("MJH_FUSE_STAGE"); return e && e[0] == '0'; }();
     out->fuse_stage = 0;
     if (!off && d->integrator == INT_RK4 && d->solver == SOL_NEWTON && out->fuse_kcv && out->pack4[1] && M.con_direct && out->pack2[2] && out->sol2_tiers && out->sol2_w16_nmax == 8 &&
-        (out->sol2_w16_rpl == 2 || out->sol2_w16_rpl == 5) && M.ncvxpair == 0 && out->sort_reals == 0 && d->nefc > 0 && !(MJH_SOL2_CAPS_ON && out->sol2_it_cap > 0)) {
+        (out->sol2_w16_rpl == 2 || out->sol2_w16_rpl == 5) && M.ncvxpair == 0 && d->nefc > 0) {
       int need = 4 * out->lds_kcv;
       if (2 * out->lds_bytes[2] > need) need = 2 * out->lds_bytes[2];
       if (4 * out->lds_tier > need) need = 4 * out->lds_tier;
@@ -848,12 +751,10 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
     }
     // ... and the tail of a pass alone (MJH_FUSE_TAIL=0: the two launches)
     // Measured (MI355X, profiles/r06/notes.md): mesh scene (12 dofs: the tier's instantiation takes 227 VGPRs, two waves per SIMD, and the constraint phase inherits that) 219.6 us
-    // against 167.9 + 49.2 in two launches -- default for 8-dof tiers only, whose kernel sits at the constraint phase's own four waves per SIMD; MJH_FUSE_TAIL=1 / 0 forces it on / off.
-    static const int tail_sw = [] { const char* e = getenv("MJH_FUSE_TAIL"); return !e ? -1 : (e[0] == '0' ? 0 : 1); }();
-    const bool tail_off = tail_sw == 0 || (tail_sw < 0 && out->sol2_w16_nmax != 8);
+    // against 167.9 + 49.2 in two launches -- 8-dof tiers only (the one instantiation that is built), whose kernel sits at the constraint phase's own four waves per SIMD.
+    static const bool tail_off = [] { const char* e = getenv("MJH_FUSE_TAIL"); return e && e[0] == '0'; }();
     out->fuse_tail = 0;
-    if (!tail_off && d->solver == SOL_NEWTON && M.con_direct && out->pack2[2] && out->sol2_tiers && out->sol2_w16_rpl > 0 && out->sort_reals == 0 && d->nefc > 0 && !M.topk &&
-        !(MJH_SOL2_CAPS_ON && out->sol2_it_cap > 0)) {
+    if (!tail_off && d->solver == SOL_NEWTON && M.con_direct && out->pack2[2] && out->sol2_tiers && out->sol2_w16_nmax == 8 && d->nefc > 0 && !M.topk) {
       int need = 2 * out->lds_bytes[2];
       if (4 * out->lds_tier > need) need = 4 * out->lds_tier;
       if (need <= 64 * 1024) { out->fuse_tail = 1; out->lds_tail = need; }
@@ -861,7 +762,7 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
     if (out->fuse_stage || out->fuse_tail) {
       const int need = out->lds_stage > out->lds_tail ? out->lds_stage : out->lds_tail;
 #define SET_ST(N, R) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_sol2_kernel<REAL, N, R, 18>), hipFuncAttributeMaxDynamicSharedMemorySize, need));
-      SET_ST(8, 2) SET_ST(8, 5) SET_ST(12, 2) SET_ST(12, 5) SET_ST(16, 2) SET_ST(16, 5)
+      SET_ST(8, 2) SET_ST(8, 5)
 #undef SET_ST
     }
   }
@@ -896,16 +797,16 @@ int launch_range(const mjhModel* m, KArgs<REAL>& a, int64_t begin, int64_t count
 }
 template <typename REAL, int P>
 int launch_phase(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
-  constexpr bool PACKABLE = (P == 0 || P == 1 || P == 2 || P == 3 || P == 5 || P == 8 || P == 12 || P == 13 || P == 17);
+  constexpr bool PACKABLE = (P == 0 || P == 1 || P == 3 || P == 5 || P == 8 || P == 12 || P == 13 || P == 17);
   constexpr int PI = !PACKABLE ? 0 : (P == 5 ? 3 : (P == 8 ? 2 : ((P == 12 || P == 13 || P == 17) ? 0 : P)));  // index into the per-phase packing flags
   const bool can2 = !PACKABLE ? false : ((P == 13 || P == 17) ? (bool)m->pack2[1] : (P == 12 ? (m->pack2[0] && m->pack2[3] && 2 * m->lds_kv <= 64 * 1024) : (bool)m->pack2[PI]));  // (13: fuse_kcv holds only when the crb stage packs like the other two)
-  const bool can4 = !PACKABLE ? false : ((P == 13 || P == 17) ? (bool)m->pack4[1] : (P == 12 ? (m->pack4[0] && m->pack4[3] && 4 * m->lds_kv <= 64 * 1024) : (P != 8 && P != 2 && m->pack4[PI])));
+  const bool can4 = !PACKABLE ? false : ((P == 13 || P == 17) ? (bool)m->pack4[1] : (P == 12 ? (m->pack4[0] && m->pack4[3] && 4 * m->lds_kv <= 64 * 1024) : (P != 8 && m->pack4[PI])));
   if (PACKABLE && can2 && a.B >= 2) {  // groups of four / pairs of environments, then the odd one on its own
     int64_t done = 0;
     int rc = 0;
     if (can4 && a.B >= 4) {
       done = a.B & ~(int64_t)3;
-      if ((rc = launch_range<REAL, P, ((PACKABLE && P != 8 && P != 2) ? 16 : MJH_WAVE)>(m, a, 0, done, stream))) return rc;
+      if ((rc = launch_range<REAL, P, ((PACKABLE && P != 8) ? 16 : MJH_WAVE)>(m, a, 0, done, stream))) return rc;
     }
     const int64_t even = (a.B - done) & ~(int64_t)1;
     if ((rc = launch_range<REAL, P, (PACKABLE ? 32 : MJH_WAVE)>(m, a, done, even, stream))) return rc;
@@ -954,24 +855,11 @@ int launch_sol2(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream, bool firs
       const int64_t grid4 = blocks4 < (int64_t)1 << 20 ? blocks4 : (int64_t)1 << 20;
       a.row_lo = -1; a.row_hi = 16 * m->sol2_w16_rpl;
       const size_t lds = (size_t)(4 * m->lds_tier);
-      const bool capped = MJH_SOL2_CAPS_ON && m->sol2_it_cap > 0 && !(a.flags & MJH_FLAG_FIXED_ITERATIONS) && a.cur.qacc;  // (a build with -DMJH_SOL2_CAPS; MJH_SOL2_ITCAP / MJH_SOL2_LSCAP then set the caps)
-      a.it_cap = capped ? m->sol2_it_cap : 0; a.ls_cap = capped ? m->sol2_ls_cap : 0;
       if (first_done) {}
       else if (m->sol2_w16_nmax == 8) { if (m->sol2_w16_rpl == 2) GOW(8, 2); else GOW(8, 5); }
       else if (m->sol2_w16_nmax == 12) { if (m->sol2_w16_rpl == 2) GOW(12, 2); else GOW(12, 5); }
       else { if (m->sol2_w16_rpl == 2) GOW(16, 2); else GOW(16, 5); }
-      a.it_cap = a.ls_cap = 0;
-      if (capped) {  // the LDS solver takes what the packed tier left: more rows than it keeps, or a solve past the caps
-        HIP_TRY(hipGetLastError());
-        a.fallback_only = 1;
-        const int rc = launch_phase<REAL, 4>(m, a, stream);
-        a.fallback_only = 0;
-        if (rc) return rc;
-        g_timing.n -= (g_timing.on && g_timing.n > 0) ? 1 : 0;  // (launch_phase marked kernel 4: both launches belong under the solver phase's one mark below)
-        second = false;
-      } else {
-        second = nd > a.row_hi;  // every environment fits the first tier otherwise
-      }
+      second = nd > a.row_hi;  // every environment fits the first tier otherwise
     } else {
       a.row_lo = -1; a.row_hi = 32;
       const size_t lds = (size_t)(2 * m->lds_tier);
@@ -1019,17 +907,14 @@ int launch_stage(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream, int part
   a.off3 = m->off_tier; a.lds_reals3 = m->lds_tier / (int)sizeof(REAL);
   a.row_lo = -1; a.row_hi = 16 * m->sol2_w16_rpl;
   a.mark_leftover = (m->sol2_tiers && a.cur.qacc != nullptr) ? 1 : 0;
-  a.scan_marks = 0; a.it_cap = a.ls_cap = 0; a.fallback_only = 0;
+  a.scan_marks = 0;
   for (int64_t e0 = 0; e0 < a.B; e0 += 4 * max_grid()) {  // (no grid-stride loop in the kernels: one launch per 2^20 workgroups)
     const int64_t n = a.B - e0 < 4 * max_grid() ? a.B - e0 : 4 * max_grid();
     a.env_begin = e0; a.env_count = n;
     const size_t lds = (size_t)(parts == 7 ? m->lds_stage : m->lds_tail);
     const dim3 g((unsigned)(n / 4)), b(MJH_WAVE);
-#define GOS(N, R) hipLaunchKernelGGL((mjh_sol2_kernel<REAL, N, R, 18>), g, b, lds, stream, a)
-    if (m->sol2_w16_nmax == 8) { if (m->sol2_w16_rpl == 2) GOS(8, 2); else GOS(8, 5); }
-    else if (m->sol2_w16_nmax == 12) { if (m->sol2_w16_rpl == 2) GOS(12, 2); else GOS(12, 5); }
-    else { if (m->sol2_w16_rpl == 2) GOS(16, 2); else GOS(16, 5); }
-#undef GOS
+    if (m->sol2_w16_rpl == 2) hipLaunchKernelGGL((mjh_sol2_kernel<REAL, 8, 2, 18>), g, b, lds, stream, a);  // (fuse_stage / fuse_tail: 8-dof tiers only)
+    else hipLaunchKernelGGL((mjh_sol2_kernel<REAL, 8, 5, 18>), g, b, lds, stream, a);
     HIP_TRY(hipGetLastError());
   }
   a.env_begin = 0; a.env_count = a.B;
@@ -1044,7 +929,7 @@ int launch_cs(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
   a.off = m->off_cs;
   a.lds_reals = m->lds_cs / (int)sizeof(REAL);
   a.row_lo = -1; a.row_hi = 0x7fffffff;
-  a.mark_leftover = 0; a.scan_marks = 0; a.it_cap = a.ls_cap = 0;
+  a.mark_leftover = 0; a.scan_marks = 0;
   static const bool one_off = [] { const char* e = getenv("MJH_CS_ONE"); return e && e[0] == '0'; }();  // (A / B switch: MJH_CS_ONE=0 launches the generic instantiation for one-iteration models too)
   for (int64_t e0 = 0; e0 < a.B; e0 += 2 * max_grid()) {  // (no grid-stride loop in the kernels: one launch per 2^20 workgroups)
     const int64_t n = a.B - e0 < 2 * max_grid() ? a.B - e0 : 2 * max_grid(), grid = (n + 1) / 2;
@@ -1065,7 +950,7 @@ int launch_all(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
   a.off = m->off_kcv; a.off2 = m->off_cs;
   a.lds_reals = m->lds_all / (int)sizeof(REAL);
   a.row_lo = -1; a.row_hi = 0x7fffffff;
-  a.mark_leftover = 0; a.scan_marks = 0; a.it_cap = a.ls_cap = 0;
+  a.mark_leftover = 0; a.scan_marks = 0;
   const int64_t blocks = (a.B + 1) / 2;
   const int64_t grid = blocks < (int64_t)1 << 20 ? blocks : (int64_t)1 << 20;
   const int keep_flags_ = a.flags;
@@ -1140,12 +1025,10 @@ int forward_pass(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
   int rc = 0;
   const int st = a.stages;
   if (m->fuse_all && (st & 0x7f) == 0x7f && a.B >= 2 && (a.B & 1) == 0 && a.B <= 2 * max_grid() /* one workgroup per pair: the kernel has no grid-stride loop */ && a.cur.efc_J && a.cur.efc_D && a.cur.efc_aref && a.cur.qM && a.cur.qLD) return launch_all<REAL>(m, a, stream);
-  // MJH_DAG=1 (experiment): kinematics -> {crb / factor || velocity (+ sensors) || convex + constraint phase} -> solver, the two side branches on internal
-  // streams forked from and joined into the caller's.  Needs the stand-alone kernels: run with MJH_FUSE_KV=0 (and so no kernel 13 / whole-pass kernel).  profiles/r05/notes.md has the numbers.
   // MJH_FUSE_STAGE0=0: stage 0 (which writes the returned Data in full) keeps its three launches.  Its sensors (they read leaves of the kinematics and velocity stages only) follow the
   // stage kernel: in an RK4 step nothing of stage 0 writes the returned state -- the final advance is stage 3's -- so the jointpos / ballquat readers of out.qpos race nothing.
   static const bool stage0_off = [] { const char* e = getenv("MJH_FUSE_STAGE0"); return e && e[0] == '0'; }();
-  if (m->fuse_stage && a.rk_stage >= (stage0_off ? 1 : 0) && (st & 0x7f) == 0x7f && a.B >= 4 && (a.B & 3) == 0 && !a.sol_perm && a.cur.qM && a.cur.qLD && a.cur.qfrc_smooth && a.cur.contact_dist &&
+  if (m->fuse_stage && a.rk_stage >= (stage0_off ? 1 : 0) && (st & 0x7f) == 0x7f && a.B >= 4 && (a.B & 3) == 0 && a.cur.qM && a.cur.qLD && a.cur.qfrc_smooth && a.cur.contact_dist &&
       a.cur.efc_J && a.cur.efc_D && a.cur.efc_aref) {
     if ((rc = launch_stage<REAL>(m, a, stream))) return rc;
     if (a.M.nsensor > 0 && a.rk_stage == 0 && a.cur.sensordata) {
@@ -1154,38 +1037,8 @@ int forward_pass(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
     }
     return 0;
   }
-  static const bool dag = [] { const char* e = getenv("MJH_DAG"); return e && e[0] == '1'; }();
-  if (dag && !m->fuse_kv && (st & 0x7f) == 0x7f && !g_timing.on && !g_stamps) {
-    {
-      std::lock_guard<std::mutex> lock(m->dag_mutex);
-      if (!m->dag_ready) {
-        for (int k = 0; k < 2; k++) { HIP_TRY(hipStreamCreateWithFlags(&m->dag_stream[k], hipStreamNonBlocking)); HIP_TRY(hipEventCreateWithFlags(&m->dag_done[k], hipEventDisableTiming)); }
-        HIP_TRY(hipEventCreateWithFlags(&m->dag_fork, hipEventDisableTiming));
-        m->dag_ready = true;
-      }
-    }
-    if ((rc = launch_phase<REAL, 0>(m, a, stream))) return rc;
-    HIP_TRY(hipEventRecord(m->dag_fork, stream));
-    HIP_TRY(hipStreamWaitEvent(m->dag_stream[0], m->dag_fork, 0));
-    HIP_TRY(hipStreamWaitEvent(m->dag_stream[1], m->dag_fork, 0));
-    if ((rc = launch_phase<REAL, 1>(m, a, m->dag_stream[0]))) return rc;
-    HIP_TRY(hipEventRecord(m->dag_done[0], m->dag_stream[0]));
-    if ((rc = (a.M.has_fluid || a.M.has_gravcomp || a.M.ntendon > 0 || a.M.big) ? launch_phase<REAL, 5>(m, a, m->dag_stream[1]) : launch_phase<REAL, 3>(m, a, m->dag_stream[1]))) return rc;
-    if (a.M.nsensor > 0 && a.rk_stage <= 0 && a.cur.sensordata) {
-      if ((rc = launch_sensor_kernel<REAL>(m, a, m->dag_stream[1]))) return rc;
-    }
-    HIP_TRY(hipEventRecord(m->dag_done[1], m->dag_stream[1]));
-    if (a.M.ncvxpair > 0) {
-      if ((rc = launch_convex<REAL>(m, a, stream))) return rc;
-    }
-    if ((a.M.ncon > 0 || a.M.nefc > 0) && (rc = a.M.con_general ? launch_phase<REAL, 7>(m, a, stream) : (a.M.con_direct ? launch_phase<REAL, 8>(m, a, stream) : launch_phase<REAL, 2>(m, a, stream)))) return rc;
-    HIP_TRY(hipStreamWaitEvent(stream, m->dag_done[0], 0));
-    HIP_TRY(hipStreamWaitEvent(stream, m->dag_done[1], 0));
-    if (m->sol2_nmax) return launch_sol2<REAL>(m, a, stream);
-    return (a.M.nf > 0 || a.M.nft > 0 || a.M.ne > 0 || a.M.nlb > 0 || a.M.nlt > 0) ? launch_phase<REAL, 6>(m, a, stream) : launch_phase<REAL, 4>(m, a, stream);
-  }
   const bool fused_kv = m->fuse_kv && (st & 0x70);  // the velocity phase is asked for: it rides with the kinematics (it needs nothing of CRB / CON)
-  const bool fused_kcv = fused_kv && m->fuse_kcv && (st & 0x7e) && a.B <= m->kcv_max_envs;  // ... and so does the crb / factor stage (small models)
+  const bool fused_kcv = fused_kv && m->fuse_kcv && (st & 0x7e);  // ... and so does the crb / factor stage (small models)
   if ((st & 0x7f) && (rc = fused_kcv ? ((m->kcv2 && a.B <= kcv2_limit(m, stream)) ? launch_phase<REAL, 17>(m, a, stream) : launch_phase<REAL, 13>(m, a, stream)) : (fused_kv ? launch_phase<REAL, 12>(m, a, stream) : launch_phase<REAL, 0>(m, a, stream)))) return rc;
   if ((st & 0x7c) && a.M.ncvxpair > 0) {  // convex narrow phase: one wave per (environment, pair); needs only the geom frames of PH_KIN
     if ((rc = launch_convex<REAL>(m, a, stream))) return rc;
@@ -1193,7 +1046,7 @@ int forward_pass(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
   }
   if ((st & 0x7e) && !fused_kcv && (rc = launch_phase<REAL, 1>(m, a, stream))) return rc;
   const bool fused_cs = m->fuse_cs && (st & 0x7c) && (st & 0x40) && a.cur.efc_J && a.cur.efc_D && a.cur.efc_aref;  // the whole tail of the pass is asked for: constraint stage and solve share a kernel
-  const bool fused_tail = !fused_cs && m->fuse_tail && (st & 0x7c) == 0x7c && a.B >= 4 && (a.B & 3) == 0 && !a.sol_perm && a.cur.qM && a.cur.qLD && a.cur.qfrc_smooth && a.cur.contact_dist &&
+  const bool fused_tail = !fused_cs && m->fuse_tail && (st & 0x7c) == 0x7c && a.B >= 4 && (a.B & 3) == 0 && a.cur.qM && a.cur.qLD && a.cur.qfrc_smooth && a.cur.contact_dist &&
                           a.cur.efc_J && a.cur.efc_D && a.cur.efc_aref && !(a.M.has_fluid || a.M.has_gravcomp || a.M.ntendon > 0 || a.M.big) && fused_kv;  // (the velocity stage has run: it rode with the kinematics)
   if (fused_tail) {  // small Newton models: constraint phase + first solver tier + integrator in one launch (their sensors read leaves of the kinematics / velocity stages only: first)
     if ((st & 0x40) && a.M.nsensor > 0 && a.rk_stage <= 0 && a.cur.sensordata) {
@@ -1206,17 +1059,8 @@ int forward_pass(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
       (rc = a.M.con_general ? launch_phase<REAL, 7>(m, a, stream) : (a.M.con_direct ? launch_phase<REAL, 8>(m, a, stream) : launch_phase<REAL, 2>(m, a, stream)))) return rc;
   if ((st & 0x70) && !fused_kv && (rc = (a.M.has_fluid || a.M.has_gravcomp || a.M.ntendon > 0 || a.M.big) ? launch_phase<REAL, 5>(m, a, stream) : launch_phase<REAL, 3>(m, a, stream))) return rc;
   const bool want_sensors = (st & 0x40) && a.M.nsensor > 0 && a.rk_stage <= 0 && a.cur.sensordata;  // needs only the leaves of KIN and VEL
-  auto launch_sensors = [&](hipStream_t s_) -> int {
-#ifdef MJH_SENSOR_ABLATE
-    static const int abl = [] { const char* e = getenv("MJH_SENSOR_ABLATE"); return e ? atoi(e) : 0; }();
-    const int keep_flags = a.flags;
-    a.flags |= abl << 8;
-    struct Restore { KArgs<REAL>& a; int f; ~Restore() { a.flags = f; } } restore_{a, keep_flags};
-#endif
-    return launch_sensor_kernel<REAL>(m, a, s_);
-  };
   if (want_sensors) {  // (round 4's opt-in side stream for this launch is gone: it raced the integrator tail's write of out.qpos, which jointpos / ballquat sensors read, and measured no gain -- profiles/r04/notes.md)
-    if ((rc = launch_sensors(stream))) return rc;
+    if ((rc = launch_sensor_kernel<REAL>(m, a, stream))) return rc;
     timing_mark(stream, 11);
   }
   if (fused_cs) return launch_cs<REAL>(m, a, stream);
@@ -1226,7 +1070,7 @@ int forward_pass(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
 }
 
 template <typename REAL>
-int run_launches_one(const mjhModel* m, const DevModel<REAL>& M, const mjhData* in, mjhData* out, void* work, int64_t B, int flags, int do_step, int stages, void* stream) {
+int run(const mjhModel* m, const DevModel<REAL>& M, const mjhData* in, mjhData* out, void* work, int64_t B, int flags, int do_step, int stages, void* stream) {
   if (B <= 0) return 0;
   static_assert(sizeof(DevData<REAL>) == sizeof(mjhData), "DevData must mirror mjhData");
   static_assert(sizeof(KArgs<REAL>) <= 4096, "kernel arguments exceed the 4 KiB kernarg segment");
@@ -1250,19 +1094,6 @@ int run_launches_one(const mjhModel* m, const DevModel<REAL>& M, const mjhData* 
     return fail(-22, "models with convex pairs need out.geom_xpos/geom_xmat and out.contact_dist/pos/frame");
   hipStream_t s = (hipStream_t)stream;
   REAL* w = (REAL*)work;
-  if (m->sort_reals > 0) {
-    if (work) {
-      int* perm = (int*)work;
-      int* key = perm + B;
-      if ((a.stages & 0x40) && B >= 8) {  // this step's list from last step's keys (a forward pass without a solve leaves both alone)
-        hipLaunchKernelGGL(mjh_sort_kernel, dim3(1), dim3(1024), 0, s, (const int*)key, perm, (long long)B);
-        HIP_TRY(hipGetLastError());
-        timing_mark(s, 15);
-        if (B <= 4 * max_grid()) { a.sol_perm = perm; a.sol_key = key; }  // (the list indexes the whole batch: one launch of the packed tier)
-      }
-    }
-    w += m->sort_reals * B;
-  }
   if (m->hs_reals > 0) {  // (without a workspace the solver reads the leaves, as it always did)
     if (work) { a.hs = w; a.hs_reals = (int)m->hs_reals; }
     w += m->hs_reals * B;
@@ -1288,7 +1119,7 @@ int run_launches_one(const mjhModel* m, const DevModel<REAL>& M, const mjhData* 
     for (size_t i = 0; i < m->leaf_count.size(); i++)
       if (is_stage_leaf(names[i], M.ncvxpair > 0, M.has_fluid != 0, M.ne > 0, M.topk != 0)) {
         // (kernel 13 keeps cinert / xipos in its arena from the kinematics to the crb and velocity stages: no later LAUNCH of a stage reads their workspace copies -- left NULL, the stores are skipped)
-        if (!(m->fuse_kcv && B <= m->kcv_max_envs && (!strcmp(names[i], "cinert") || !strcmp(names[i], "xipos")))) slots[i] = w;
+        if (!(m->fuse_kcv && (!strcmp(names[i], "cinert") || !strcmp(names[i], "xipos")))) slots[i] = w;
         w += m->leaf_count[i] * B;
       }
   }
@@ -1313,124 +1144,6 @@ int run_launches_one(const mjhModel* m, const DevModel<REAL>& M, const mjhData* 
   return 0;
 }
 
-int split_ways() {
-  // MJH_SPLIT=n: the batch is cut into n contiguous slices whose launch sequences run on n internal streams, forked from and
-  // joined back into the caller's stream with events.  The phases of different slices then overlap on the CUs (a register-bound
-  // phase of one slice fills the wave slots an LDS-bound phase of another leaves idle).  Default 1 (profiles/r01/notes.md).
-  static const int n = [] { const char* e = getenv("MJH_SPLIT"); int v = e ? atoi(e) : 1; return v < 1 ? 1 : (v > 4 ? 4 : v); }();
-  return n;
-}
-
-// the Data view of environments [begin, ...): every non-null leaf pointer advanced by begin * (elements per environment)
-template <typename REAL>
-void offset_data(const mjhModel* m, const DevModel<REAL>& M, const mjhData* src, mjhData* dst, int64_t begin) {
-  memcpy(dst, src, sizeof(*dst));
-  unsigned char** p = reinterpret_cast<unsigned char**>(dst);
-  const size_t nreal = m->leaf_count.size();
-  for (size_t i = 0; i < nreal; i++) if (p[i]) p[i] += (size_t)begin * (size_t)m->leaf_count[i] * sizeof(REAL);
-  const int64_t ncon = M.ncon, neq = M.neq;
-  const int64_t int_bytes[] = {4 * ncon, 4 * neq, 8 * ncon, 8 * ncon, 16 * ncon, 8 * ncon};  // contact_dim, eq_active | geom1, geom2, geom, efc_address
-  for (size_t k = 0; k < 6; k++) if (p[nreal + k]) p[nreal + k] += (size_t)begin * (size_t)int_bytes[k];
-  const int64_t extra_reals[] = {6 * (int64_t)M.nbody, 6 * (int64_t)M.nbody, 3 * (int64_t)M.nbody, 3 * (int64_t)M.nbody};  // MJH_DATA_EXTRA_IN: cacc, cfrc_int, subtree_linvel, subtree_angmom (input-only, may be NULL)
-  static_assert(sizeof(mjhData) / sizeof(void*) >= 10, "mjhData: leaves + six integer leaves + four input-only leaves");
-  for (size_t k = 0; k < 4; k++) if (p[nreal + 6 + k]) p[nreal + 6 + k] += (size_t)begin * (size_t)extra_reals[k] * sizeof(REAL);
-}
-
-template <typename REAL>
-int run_launches(const mjhModel* m, const DevModel<REAL>& M, const mjhData* in, mjhData* out, void* work, int64_t B, int flags, int do_step, int stages, void* stream) {
-  const int ways = split_ways();
-  hipStream_t s = (hipStream_t)stream;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  const bool capturing = s && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-  if (ways <= 1 || B < 64 * ways || capturing) return run_launches_one<REAL>(m, M, in, out, work, B, flags, do_step, stages, stream);
-  std::lock_guard<std::mutex> lock(m->split_mutex);
-  if (!m->split_ready) {
-    for (int k = 0; k < 4; k++) {
-      HIP_TRY(hipStreamCreateWithFlags(&m->split_stream[k], hipStreamNonBlocking));
-      HIP_TRY(hipEventCreateWithFlags(&m->split_done[k], hipEventDisableTiming));
-    }
-    HIP_TRY(hipEventCreateWithFlags(&m->split_fork, hipEventDisableTiming));
-    m->split_ready = true;
-  }
-  HIP_TRY(hipEventRecord(m->split_fork, s));
-  const int64_t per = ((B + ways - 1) / ways + 1) & ~(int64_t)1;  // even slices keep the two-environments-per-wave phases paired
-  const size_t work_env_bytes = (size_t)m->work_reals * sizeof(REAL);
-  int rc = 0;
-  for (int k = 0; k < ways; k++) {
-    const int64_t begin = (int64_t)k * per, count = (begin + per <= B) ? per : B - begin;
-    if (count <= 0) break;
-    mjhData in_k, out_k;
-    offset_data<REAL>(m, M, in, &in_k, begin);
-    offset_data<REAL>(m, M, out, &out_k, begin);
-    HIP_TRY(hipStreamWaitEvent(m->split_stream[k], m->split_fork, 0));
-    void* work_k = work ? (void*)((unsigned char*)work + (size_t)begin * work_env_bytes) : nullptr;
-    if ((rc = run_launches_one<REAL>(m, M, &in_k, &out_k, work_k, count, flags, do_step, stages, (void*)m->split_stream[k]))) break;
-    HIP_TRY(hipEventRecord(m->split_done[k], m->split_stream[k]));
-    HIP_TRY(hipStreamWaitEvent(s, m->split_done[k], 0));
-  }
-  return rc;
-}
-
-unsigned long long fnv1a(unsigned long long h, const void* p, size_t n) {
-  const unsigned char* b = (const unsigned char*)p;
-  for (size_t i = 0; i < n; i++) { h ^= b[i]; h *= 1099511628211ull; }
-  return h;
-}
-
-bool graphs_enabled() {
-  // opt-in (MJH_GRAPHS=1): measured on MI355X the replay saves ~3 % of wall time at B <= 1024 (the step is bound by the
-  // latency of its dependent kernels there, not by the host) and costs 1-2 % at B = 4096 (profiles/r01/notes.md)
-  static const bool on = [] { const char* e = getenv("MJH_GRAPHS"); return e && e[0] == '1'; }();
-  return on && !g_stamps && !g_timing.on;  // per-launch events cannot be recorded into a replayed graph
-}
-
-template <typename REAL>
-int run(const mjhModel* m, const DevModel<REAL>& M, const mjhData* in, mjhData* out, void* work, int64_t B, int flags, int do_step, int stages, void* stream) {
-  if (B <= 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (!graphs_enabled() || (s && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone))
-    return run_launches<REAL>(m, M, in, out, work, B, flags, do_step, stages, stream);  // the caller is capturing a graph of their own
-  unsigned long long key = 1469598103934665603ull;
-  key = fnv1a(key, in, sizeof(*in));
-  key = fnv1a(key, out, sizeof(*out));
-  key = fnv1a(key, &work, sizeof(work));
-  const long long scal[4] = {(long long)B, flags, do_step, stages};
-  key = fnv1a(key, scal, sizeof(scal));
-  std::lock_guard<std::mutex> lock(m->graph_mutex);
-  for (auto& g : m->graphs)
-    if (g.key == key) {
-      g.last_use = ++m->graph_clock;
-      HIP_TRY(hipGraphLaunch(g.exec, s));
-      return 0;
-    }
-  if (!m->capture_stream) HIP_TRY(hipStreamCreateWithFlags(&m->capture_stream, hipStreamNonBlocking));
-  if (hipStreamBeginCapture(m->capture_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-    (void)hipGetLastError();
-    return run_launches<REAL>(m, M, in, out, work, B, flags, do_step, stages, stream);
-  }
-  const int rc = run_launches<REAL>(m, M, in, out, work, B, flags, do_step, stages, (void*)m->capture_stream);
-  hipGraph_t graph = nullptr;
-  const hipError_t ec = hipStreamEndCapture(m->capture_stream, &graph);
-  if (rc != 0) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-  hipGraphExec_t exec = nullptr;
-  if (ec != hipSuccess || !graph || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-    (void)hipGetLastError();
-    if (graph) (void)hipGraphDestroy(graph);
-    return run_launches<REAL>(m, M, in, out, work, B, flags, do_step, stages, stream);
-  }
-  (void)hipGraphDestroy(graph);
-  if (m->graphs.size() >= 16) {  // ping-pong loops need two entries; keep a handful and evict the least recently used
-    size_t lru = 0;
-    for (size_t i = 1; i < m->graphs.size(); i++) if (m->graphs[i].last_use < m->graphs[lru].last_use) lru = i;
-    (void)hipGraphExecDestroy(m->graphs[lru].exec);
-    m->graphs.erase(m->graphs.begin() + (long)lru);
-  }
-  m->graphs.push_back({key, exec, ++m->graph_clock});
-  HIP_TRY(hipGraphLaunch(exec, s));
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1451,13 +1164,6 @@ int mjh_model_create(const mjhModelDesc* desc, int dtype, mjhModel** out) {
 
 void mjh_model_destroy(mjhModel* m) {
   if (!m) return;
-  for (auto& g : m->graphs) (void)hipGraphExecDestroy(g.exec);
-  if (m->capture_stream) (void)hipStreamDestroy(m->capture_stream);
-  if (m->dag_ready) { for (int k = 0; k < 2; k++) { (void)hipStreamDestroy(m->dag_stream[k]); (void)hipEventDestroy(m->dag_done[k]); } (void)hipEventDestroy(m->dag_fork); }
-  if (m->split_ready) {
-    for (int k = 0; k < 4; k++) { (void)hipStreamDestroy(m->split_stream[k]); (void)hipEventDestroy(m->split_done[k]); }
-    (void)hipEventDestroy(m->split_fork);
-  }
   if (m->blob) (void)hipFree(m->blob);
   delete m;
 }

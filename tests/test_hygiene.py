@@ -46,3 +46,26 @@ def test_the_product_tree_never_touches_the_oracle():
                 if isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and n.func.attr in ("CDLL", "LoadLibrary", "PyDLL", "dlopen"):
                     loaders.setdefault(f, []).append(n.lineno)
     assert set(loaders) == {"native.py"} and len(loaders["native.py"]) == 1, loaders
+
+
+def test_switch_table_matches_the_library():
+    """INTEGRATION.md §4 documents the library's environment switches: every `getenv("MJH_...")` under csrc/ has a row, and every runtime MJH_* row is read by some
+    getenv there -- a switch that is taken out of the code leaves the table with it.  (Rows for `build.sh -D...` options, MJH_LIB and MJH_BUILD_* are not read by the library.)"""
+    read = set()
+    csrc = os.path.join(ROOT, "mujoco-torch_amd", "csrc")
+    for f in os.listdir(csrc):
+        if f.endswith((".h", ".hip")):
+            read |= set(re.findall(r'getenv\("(MJH_[A-Z0-9_]+)"\)', open(os.path.join(csrc, f)).read()))
+    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = text[text.index("## 4. Environment switches"):]
+    section = section[:section.index("\n## ")] if "\n## " in section else section
+    documented = set()
+    for line in section.splitlines():
+        if line.startswith("| `"):
+            first = line.split("|")[1]
+            if "build.sh" not in first:
+                documented |= set(re.findall(r"MJH_[A-Z0-9_]+", first))
+    documented = {n for n in documented if n != "MJH_LIB" and not n.startswith("MJH_BUILD_")}
+    assert read, "no getenv(\"MJH_...\") found under csrc/"
+    assert not read - documented, f"read by the library but missing from INTEGRATION.md's switch table: {sorted(read - documented)}"
+    assert not documented - read, f"in INTEGRATION.md's switch table but read by no getenv under csrc/: {sorted(documented - read)}"
