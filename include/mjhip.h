@@ -8,6 +8,7 @@
  *   mjh_model_create   <- Model.to(device) + _build_device_precomp   (_src/types.py:949-1013)
  *   mjh_forward        <- forward.forward(m, d)                       (_src/forward.py:373-401)
  *   mjh_step           <- forward.step(m, d, fixed_iterations)        (_src/forward.py:463-496)
+ *   mjh_inverse        <- inverse.inverse(m, d)                       (_src/inverse.py:86-102)
  *
  * Conventions
  *  - every Data leaf is batch-major contiguous: shape [B, ...] exactly as
@@ -40,6 +41,7 @@ extern "C" {
 #define MJH_F32 1
 
 #define MJH_FLAG_FIXED_ITERATIONS 1 /* step(..., fixed_iterations=True), forward.py:463 */
+#define MJH_FLAG_INV_DISCRETE 2     /* mjh_inverse: opt.enableflags & mjENBL_INVDISCRETE (discrete_acc, inverse.py:92-93) */
 
 /* stage bits for mjh_forward(stages): run the pipeline up to and including the highest bit */
 #define MJH_STAGE_KINEMATICS 0x001 /* smooth.kinematics + com_pos        smooth.py:34-288   */
@@ -377,6 +379,16 @@ int mjh_forward(const mjhModel* m, const mjhData* in, mjhData* out, void* work, 
 int mjh_step(const mjhModel* m, const mjhData* in, mjhData* out, void* work, int64_t B, int flags, void* hip_stream);
 int64_t mjh_model_work_bytes(const mjhModel* m);
 
+/* inverse dynamics for B environments (inverse.py:86-102): the forward pass up to and including the velocity stage (stages 0x1F of
+ * mjh_forward: _position + _velocity), then -- with the caller's in.qacc -- discrete_acc when MJH_FLAG_INV_DISCRETE is set (Euler with eulerdamp
+ * and some dof damping: qacc <- solve_m(M qacc + h * dof_damping o qacc); RK4 returns an error), inv_constraint and
+ *   qfrc_inverse = qfrc_bias + M qacc - qfrc_passive - qfrc_constraint,
+ * then the sensors when the model has some and out.sensordata is given.  Writes the leaves of those stages, efc_force (nefc > 0), qfrc_constraint
+ * (zeros when nefc == 0) and `qfrc_inverse` ([B, nv], a pointer of its own: qfrc_inverse is not one of the mjhData leaves).  It does NOT write
+ * actuator_force, qfrc_actuator, qfrc_smooth, qacc_smooth, qacc, act_dot or qacc_warmstart (NULL in `out` is fine); sensors that read
+ * actuator_force / qfrc_actuator read the caller's (in).  `work`: as for mjh_forward. */
+int mjh_inverse(const mjhModel* m, const mjhData* in, mjhData* out, void* qfrc_inverse, void* work, int64_t B, int flags, void* hip_stream);
+
 /* per-environment ELEMENT count of every mjhData leaf in ABI order (reals, then int32, then int64 leaves): a leaf handed to
  * mjh_forward / mjh_step / mjh_reset_where must hold exactly B * count elements.  The binding validates tensor sizes against
  * this before it passes raw pointers (the kernels index `ptr + env * count` unchecked).  Writes min(n, max) entries, returns n. */
@@ -402,7 +414,7 @@ int mjh_model_lds_bytes(const mjhModel* m, int phase);
  * 10 convex narrow phase, 11 sensors, 12 kinematics + velocity phases as one kernel -- then 0 and 3 do not appear --, 13 kinematics + crb / factor + velocity as one kernel
  * (models whose crb stage packs like the other two), then 12 and 1 do not appear; 14 constraint stage + register solver + integrator as one kernel, 16 the whole pass as
  * one kernel (humanoid-class models), 17 kernel 13 on two wavefronts per workgroup, 18 one RK4 stage of a small Newton model as one kernel, 19 that kernel running the
- * constraint phase + first solver tier only; 15 is unassigned).  Returns the number of launches (<= max) or a negative code. */
+ * constraint phase + first solver tier only, 20 the inverse-dynamics tail of mjh_inverse; 15 is unassigned).  Returns the number of launches (<= max) or a negative code. */
 int mjh_debug_phase_timing(int enable);
 int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
 
@@ -410,7 +422,7 @@ int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
  * them off.  The shipped library is built without MJH_STAMPS: the pointer is stored and nothing reads it. */
 void mjh_debug_set_stamps(void* dev_ptr);
 
-/* global-memory bytes ONE launch of kernel `kernel` (ids as above) reads and writes per environment in a step: the library's own
+/* global-memory bytes ONE launch of kernel `kernel` (ids as above) reads and writes per environment in a step (20: in an mjh_inverse call): the library's own
  * account of its loads / stores through the Data leaves (csrc/mjh_io.h) -- the per-kernel "algorithmic bytes" of the roofline.
  * read_write_bytes[0] = read, [1] = written.  RK4 models: the mean over the four stage launches of a step (stages 1..3 write a private
  * workspace holding only the leaves a later phase reads).  Returns 0, or -2 when this model's step does not launch that kernel. */

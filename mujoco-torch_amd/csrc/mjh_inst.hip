@@ -5,6 +5,7 @@
 #include "mjh_kernels.h"
 #include "mjh_convex.h"
 #include "mjh_sensor.h"
+#include "mjh_inverse.h"
 #include "mjh_instances.h"
 
 #define MJH_CAT_(a, b) a##b
@@ -14,3 +15,6 @@
 #define C_(R) template __global__ void mjh_convex_kernel<R>(KArgs<R>);
 #define N_(R) template __global__ void mjh_sensor_kernel<R, 0>(KArgs<R>); template __global__ void mjh_sensor_kernel<R, 1>(KArgs<R>);
 MJH_CAT(MJH_INST_G, MJH_INST_GROUP)(X_, S_, C_, N_, MJH_INST_REAL)
+#if MJH_INST_GROUP == 19
+template __global__ void mjh_inverse_kernel<MJH_INST_REAL>(InvArgs<MJH_INST_REAL>);
+#endif

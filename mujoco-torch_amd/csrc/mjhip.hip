@@ -16,6 +16,7 @@
 #include "mjh_sensor.h"
 #include "mjh_reset.h"
 #include "mjh_io.h"
+#include "mjh_inverse.h"
 #include "mjh_instances.h"
 
 // the kernels are compiled in their own translation units (mjh_inst.hip, one per build group): this file is the host side only
@@ -25,6 +26,8 @@
 #define N_(R) extern template __global__ void mjh_sensor_kernel<R, 0>(KArgs<R>); extern template __global__ void mjh_sensor_kernel<R, 1>(KArgs<R>);
 MJH_INST_ALL(X_, S_, C_, N_, double)
 MJH_INST_ALL(X_, S_, C_, N_, float)
+extern template __global__ void mjh_inverse_kernel<double>(InvArgs<double>);  // (build group 19)
+extern template __global__ void mjh_inverse_kernel<float>(InvArgs<float>);
 #undef X_
 #undef S_
 #undef C_
@@ -39,7 +42,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 static struct {
   bool on = false;
   int n = 0;                          // launches recorded by the last call
-  int id[MJH_TIMING_MAX];             // 0..8 phase-kernel ids, 9 register solver, 10 convex narrow phase, 11 sensors, 12 / 13 / 17 fused kinematics (+ crb) + velocity, 14 fused constraint + register solver, 16 whole pass, 18 / 19 stage kernel (15: unassigned)
+  int id[MJH_TIMING_MAX];             // 0..8 phase-kernel ids, 9 register solver, 10 convex narrow phase, 11 sensors, 12 / 13 / 17 fused kinematics (+ crb) + velocity, 14 fused constraint + register solver, 16 whole pass, 18 / 19 stage kernel, 20 inverse-dynamics tail (15: unassigned)
   hipEvent_t ev[MJH_TIMING_MAX + 1];  // ev[i] .. ev[i + 1] brackets launch i
 } g_timing;
 static inline void timing_begin(hipStream_t s) { if (g_timing.on) { g_timing.n = 0; (void)hipEventRecord(g_timing.ev[0], s); } }
@@ -77,6 +80,8 @@ struct mjhModel {
   int lds_tier = 0;
   int fuse_all = 0;                        // ... and the whole pass as ONE kernel (mjh_sol2_kernel<.., 34>, timing id 16): kernel 13's stages in front of kernel 14's, one arena of max(lds_kcv, lds_cs)
   int lds_all = 0;
+  int inv_lanes = 0, inv_envs = 0, inv_chunk = 0, inv_lds_env = 0;  // inverse-dynamics tail (mjh_inverse_kernel): lanes per environment, environments per workgroup, rows per LDS chunk, REALs per environment
+  int any_damping = 0;                     // some dof_damping != 0 (discrete_acc's eulerdamp re-solve applies)
   int fuse_stage = 0;                      // every RK4 stage of a small Newton model runs as ONE launch (mjh_sol2_kernel<.., 18>, timing id 18; stage 0 too unless MJH_FUSE_STAGE0=0): kernel 13's stages, the constraint phase (kernel 8) and the register solver's first tier
   int lds_stage = 0;                       // ... dynamic LDS of one of its four-environment workgroups
   int fuse_tail = 0;                       // the tail of a pass -- constraint phase + the solver's first tier + integrator -- as ONE launch of the same kernel (parts 2 | 4): small Newton models whose pass cannot be one launch (convex narrow phase or sensors between the parts, Euler)
@@ -583,6 +588,22 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_sol2_kernel<REAL, 28, 1, 35>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * out->lds_cs));
       }
     }
+  }
+  {  // inverse-dynamics tail (mjh_inverse.h): one environment per 16 / 32 / 64 lanes, 256 lanes per workgroup, LDS_BUDGET bytes per workgroup shared by its environments.
+     // The chunk of matrix rows an environment streams through LDS is what is left of its share after qacc, M qacc, qfrc_constraint and the chunk's forces.
+    constexpr int LDS_BUDGET = 52 * 1024;  // three workgroups per CU (160 KB)
+    out->inv_lanes = nv <= 16 ? 16 : (nv <= 32 ? 32 : 64);
+    out->inv_envs = 256 / out->inv_lanes;
+    const int reals = LDS_BUDGET / out->inv_envs / (int)sizeof(REAL);
+    const int rows_max = d->nefc > nv ? d->nefc : (nv > 0 ? nv : 1);
+    int chunk = (reals - 3 * nv) / (nv + 1);
+    if (chunk > rows_max) chunk = rows_max;
+    if (chunk < 1) return fail(-12, "inverse dynamics: nv too large for the LDS chunk of one environment");
+    out->inv_chunk = chunk;
+    out->inv_lds_env = (3 * nv + chunk + chunk * nv + 1) & ~1;
+    out->any_damping = 0;
+    for (int i = 0; i < nv; i++) if (d->dof_damping[i] != 0) out->any_damping = 1;
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_inverse_kernel<REAL>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));  // (the budget plus the rounding of lds_env)
   }
   out->leaf_count = leaf_counts(d);
   out->work_reals = 0;
@@ -1144,6 +1165,56 @@ int run(const mjhModel* m, const DevModel<REAL>& M, const mjhData* in, mjhData* 
   return 0;
 }
 
+// inverse dynamics (inverse.py:86-102): the forward pass up to and including the velocity stage, the inverse tail, then the sensors
+template <typename REAL>
+int run_inverse(const mjhModel* m, const DevModel<REAL>& M, const mjhData* in, mjhData* out, void* qfrc_inverse, void* work, int64_t B, int flags, void* stream) {
+  if (B <= 0) return 0;
+  const bool discrete = (flags & MJH_FLAG_INV_DISCRETE) != 0;
+  if (discrete && M.integrator == INT_RK4) return fail(-22, "discrete inverse dynamics is not supported by RK4 integrator");
+  DevData<REAL> o;
+  memcpy(&o, out, sizeof(o));
+  const REAL* qacc = reinterpret_cast<const REAL*>(in->qacc);
+  if (!qacc) return fail(-22, "in.qacc is required");
+  if (!qfrc_inverse || !o.qfrc_constraint || !o.qM || !o.qLD || !o.qfrc_bias || !o.qfrc_passive) return fail(-22, "inverse: qfrc_inverse and out.qfrc_constraint / qM / qLD / qfrc_bias / qfrc_passive are required");
+  if (M.nefc > 0 && !(o.efc_J && o.efc_D && o.efc_aref && o.efc_force)) return fail(-22, "inverse: out.efc_J / efc_D / efc_aref / efc_force are required");
+  // (the hand-over workspace of the register solver is not used: no solver runs.  A workspace is needed only for the max_contact_points candidates, which it holds at its head)
+  int rc = run<REAL>(m, M, in, out, m->cand_reals > 0 ? work : nullptr, B, flags & MJH_FLAG_FIXED_ITERATIONS, 0, 0x1F, stream);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  InvArgs<REAL> ia;
+  memset(&ia, 0, sizeof(ia));
+  ia.efc_J = o.efc_J; ia.efc_D = o.efc_D; ia.efc_aref = o.efc_aref; ia.qM = o.qM; ia.qLD = o.qLD; ia.qfrc_bias = o.qfrc_bias; ia.qfrc_passive = o.qfrc_passive;
+  ia.qacc = qacc; ia.dof_damping = M.dof_damping;
+  ia.efc_force = o.efc_force; ia.qfrc_constraint = o.qfrc_constraint; ia.qfrc_inverse = reinterpret_cast<REAL*>(qfrc_inverse);
+  ia.timestep = M.timestep;
+  ia.nv = M.nv; ia.nefc = M.nefc; ia.nalways = M.ne + M.nf + M.nft;
+  ia.discrete = (discrete && M.integrator == INT_EULER && !(M.disableflags & DSBL_EULERDAMP) && m->any_damping) ? 1 : 0;
+  ia.lanes = m->inv_lanes; ia.envs = m->inv_envs; ia.chunk = m->inv_chunk; ia.lds_env = m->inv_lds_env;
+  const size_t lds = (size_t)ia.envs * ia.lds_env * sizeof(REAL);
+  for (int64_t e0 = 0; e0 < B; e0 += ia.envs * max_grid()) {  // (no grid-stride loop: one launch per 2^20 workgroups)
+    const int64_t n = B - e0 < ia.envs * max_grid() ? B - e0 : ia.envs * max_grid();
+    ia.env_begin = e0; ia.env_count = n;
+    hipLaunchKernelGGL((mjh_inverse_kernel<REAL>), dim3((unsigned)((n + ia.envs - 1) / ia.envs)), dim3(256), lds, s, ia);
+    HIP_TRY(hipGetLastError());
+  }
+  timing_mark(s, 20);
+  if (M.nsensor > 0 && o.sensordata) {  // sensor_pos / sensor_vel / sensor_acc: leaves this call does not write (actuator_force, qfrc_actuator) are the caller's
+    KArgs<REAL> a;
+    memset(&a, 0, sizeof(a));
+    a.M = M;
+    memcpy(&a.in, in, sizeof(a.in));
+    a.cur = o;
+    if (!a.cur.actuator_force) a.cur.actuator_force = a.in.actuator_force;
+    if (!a.cur.qfrc_actuator) a.cur.qfrc_actuator = a.in.qfrc_actuator;
+    a.fin = state_of(o);
+    a.B = B; a.flags = flags; a.do_step = 0; a.stages = 0x1F; a.rk_stage = -1; a.state_from_cur = 0;
+    a.warm_src = a.in.qacc_warmstart;
+    if ((rc = launch_sensor_kernel<REAL>(m, a, s))) return rc;
+    timing_mark(s, 11);
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1178,6 +1249,12 @@ int mjh_step(const mjhModel* m, const mjhData* in, mjhData* out, void* work, int
   if (!m || !in || !out) return fail(-22, "null argument");
   return m->dtype == MJH_F64 ? run<double>(m, m->m64, in, out, work, B, flags, 1, MJH_STAGE_ALL, stream)
                              : run<float>(m, m->m32, in, out, work, B, flags, 1, MJH_STAGE_ALL, stream);
+}
+
+int mjh_inverse(const mjhModel* m, const mjhData* in, mjhData* out, void* qfrc_inverse, void* work, int64_t B, int flags, void* stream) {
+  if (!m || !in || !out) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_inverse<double>(m, m->m64, in, out, qfrc_inverse, work, B, flags, stream)
+                             : run_inverse<float>(m, m->m32, in, out, qfrc_inverse, work, B, flags, stream);
 }
 
 int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsigned char* mask, const void* qpos_rows,
@@ -1279,6 +1356,13 @@ int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes
     return rc;
   };
   int64_t a[2] = {0, 0};
+  if (kernel == 20) {  // the inverse-dynamics tail (mjh_inverse): efc_J and qM once, efc_D / efc_aref, qacc, qfrc_bias / passive in; efc_force, qfrc_constraint, qfrc_inverse out.
+    // (the discrete branch reads qM a second time and the factor's lower triangle: not counted, it depends on the call's flags)
+    const int64_t R = f64 ? 8 : 4, nv = f64 ? m->m64.nv : m->m32.nv, nefc = f64 ? m->m64.nefc : m->m32.nefc;
+    read_write_bytes[0] = (nefc * nv + 2 * nefc + nv * nv + 3 * nv) * R;
+    read_write_bytes[1] = (nefc + 2 * nv) * R;
+    return 0;
+  }
   if (kernel == 16) {  // the whole pass in one launch: the accounts of kernels 13 and 14 (what the second half reads of the first it still reads from the leaves)
     if (!m->fuse_all) return -2;
     int64_t a13[2] = {0, 0}, a14[2] = {0, 0};

@@ -16,6 +16,9 @@ Why: the reference's published batched mode is ``torch.compile(torch.vmap(lambda
   broadcast, outputs carry the mapped dimension first.  No private functorch call is involved.
 
 The fast path of a direct ``step(mx, d)`` on plain tensors does not go through the operator (forward.py).
+
+``inverse`` has an operator of its own, ``torch.ops.mujoco_torch_amd.inverse_leaves``: the same leaves in, the leaves an inverse call writes
+(``forward._inverse_names``) and then ``qfrc_inverse`` out, with the same fake and vmap rules.
 """
 
 from __future__ import annotations
@@ -78,14 +81,19 @@ def out_names(m, do_step: bool, stages: int):
     return names
 
 
-@torch.library.custom_op("mujoco_torch_amd::step_leaves", mutates_args=())
-def step_leaves(leaves: list[torch.Tensor], model_key: torch.Tensor, struct_uid: str, fixed_iterations: bool, do_step: bool, stages: int) -> list[torch.Tensor]:
-    from .forward import _run_native
+def inverse_out_names(m):
+    """The leaves one inverse call writes, then qfrc_inverse (what ``inverse_leaves`` returns, in this order)."""
+    from .forward import _inverse_names
 
-    m = _model(model_key)
-    if m._struct_uid != struct_uid:
-        raise RuntimeError("mujoco_torch_amd::step_leaves: the Model handed to the traced step has another structure than the one it was traced with "
-                           "(different XML / cone / disabled constraints): trace a step of its own for it")
+    return _inverse_names(m) + ["qfrc_inverse"]
+
+
+def _leaf_of(tmpl, n):
+    return tmpl.qfrc_inverse if n == "qfrc_inverse" else native.data_field_tensor(tmpl, n)
+
+
+def _data_of_leaves(m, leaves):
+    """The Data the operator's eager implementation runs on: the template with the caller's leaves put in."""
     tmpl = _template(m)
     top, con = {n: None for n in _XNAMES}, {}  # an absent input-only leaf is NULL (zeros) for the kernels -- never the template's unbatched copy
     for n, t in zip(_XNAMES, leaves[len(_NAMES):]):
@@ -100,21 +108,45 @@ def step_leaves(leaves: list[torch.Tensor], model_key: torch.Tensor, struct_uid:
     d = tmpl.replace(contact=tmpl.contact.replace(**con), **top)
     object.__setattr__(d, "_bs", batch)
     object.__setattr__(d.contact, "_bs", batch)
+    return d
+
+
+def _destination(m, d, leaves, names):
+    """(fresh output tensors in `names` order, the destination Data carrying the ABI ones)."""
     # an operator's outputs may not share storage with each other: every written leaf gets an allocation of its own and the native call
     # fills them through its `out=` path (the direct call carves its leaves from two slabs instead)
+    tmpl = _template(m)
     qpos = leaves[_QPOS]
-    names = out_names(m, do_step, stages)
+    batch = tuple(qpos.shape[:-1])
     outs, otop, ocon = [], {}, {}
     for n in names:
-        ref = native.data_field_tensor(tmpl, n)
-        t = torch.empty(batch + tuple(ref.shape), dtype=qpos.dtype if _NAMES.index(n) < _NREAL else _INT_DTYPE[n], device=qpos.device)
+        ref = _leaf_of(tmpl, n)
+        t = torch.empty(batch + tuple(ref.shape), dtype=qpos.dtype if n not in _INT_DTYPE else _INT_DTYPE[n], device=qpos.device)
         outs.append(t)
-        path = native.DATA_PATH[n]
-        (ocon if len(path) == 2 else otop)[path[-1]] = t
+        if n in native.DATA_PATH:
+            path = native.DATA_PATH[n]
+            (ocon if len(path) == 2 else otop)[path[-1]] = t
     for n in _NAMES:  # the destination container carries the written leaves only (an expanded, stride-0 input leaf is not a valid destination)
         path = native.DATA_PATH[n]
         (ocon if len(path) == 2 else otop).setdefault(path[-1], None)
-    dout = d.replace(contact=d.contact.replace(**ocon), **otop)
+    return outs, d.replace(contact=d.contact.replace(**ocon), **otop)
+
+
+def _checked_model(model_key, struct_uid, op, what):
+    m = _model(model_key)
+    if m._struct_uid != struct_uid:
+        raise RuntimeError(f"mujoco_torch_amd::{op}: the Model handed to the traced {what} has another structure than the one it was traced with "
+                           f"(different XML / cone / disabled constraints): trace a {what} of its own for it")
+    return m
+
+
+@torch.library.custom_op("mujoco_torch_amd::step_leaves", mutates_args=())
+def step_leaves(leaves: list[torch.Tensor], model_key: torch.Tensor, struct_uid: str, fixed_iterations: bool, do_step: bool, stages: int) -> list[torch.Tensor]:
+    from .forward import _run_native
+
+    m = _checked_model(model_key, struct_uid, "step_leaves", "step")
+    d = _data_of_leaves(m, leaves)
+    outs, dout = _destination(m, d, leaves, out_names(m, do_step, stages))
     _run_native(m, d, fixed_iterations, do_step, dout, stages)
     return outs
 
@@ -144,11 +176,40 @@ def _step_leaves_vmap(info, in_dims, leaves, model_key, struct_uid, fixed_iterat
 
 torch.library.register_vmap(step_leaves, _step_leaves_vmap)
 
+
+@torch.library.custom_op("mujoco_torch_amd::inverse_leaves", mutates_args=())
+def inverse_leaves(leaves: list[torch.Tensor], model_key: torch.Tensor, struct_uid: str) -> list[torch.Tensor]:
+    from .forward import _run_native
+
+    m = _checked_model(model_key, struct_uid, "inverse_leaves", "inverse")
+    d = _data_of_leaves(m, leaves)
+    outs, dout = _destination(m, d, leaves, inverse_out_names(m))
+    _run_native(m, d, False, False, dout, 0x1F, inverse=True, qfrc_inverse=outs[-1])
+    return outs
+
+
+@inverse_leaves.register_fake
+def _(leaves, model_key, struct_uid):
+    m = _structure(struct_uid)
+    tmpl = _template(m)
+    qpos = leaves[_QPOS]
+    batch = tuple(qpos.shape[:-1])
+    return [qpos.new_empty(batch + tuple(_leaf_of(tmpl, n).shape), dtype=_INT_DTYPE.get(n, qpos.dtype)) for n in inverse_out_names(m)]
+
+
+def _inverse_leaves_vmap(info, in_dims, leaves, model_key, struct_uid):
+    B = info.batch_size
+    moved = [t.unsqueeze(0).expand(B, *t.shape) if bd is None else t.movedim(bd, 0) for t, bd in zip(leaves, in_dims[0])]
+    outs = inverse_leaves(moved, model_key, struct_uid)
+    return outs, [0] * len(outs)
+
+
+torch.library.register_vmap(inverse_leaves, _inverse_leaves_vmap)
+
 _ABSENT = torch.empty(0)
 
 
-def run_through_op(m, d, fixed_iterations: bool, do_step: bool, stages: int):
-    """``_run`` for calls that are being traced or vmapped: Dynamo-traceable Python around one operator call."""
+def _leaves_of(d):
     con = d.contact
     leaves = []
     for n in _NAMES:
@@ -158,10 +219,16 @@ def run_through_op(m, d, fixed_iterations: bool, do_step: bool, stages: int):
     for n in _XNAMES:
         t = getattr(d, n, None)
         leaves.append(t if isinstance(t, torch.Tensor) else _ABSENT)
-    outs = torch.ops.mujoco_torch_amd.step_leaves(leaves, m._op_key_t, m._struct_uid, fixed_iterations, do_step, stages)
+    return leaves
+
+
+def _result(d, names, outs):
+    con = d.contact
     top, cn = {}, {}
-    names = out_names(m, do_step, stages)
     for i in range(len(names)):
+        if names[i] not in native.DATA_PATH:  # qfrc_inverse
+            top[names[i]] = outs[i]
+            continue
         path = native.DATA_PATH[names[i]]
         if len(path) == 2:
             cn[path[-1]] = outs[i]
@@ -170,3 +237,15 @@ def run_through_op(m, d, fixed_iterations: bool, do_step: bool, stages: int):
     if cn:
         top["contact"] = con.replace(**cn)
     return d.replace(**top)
+
+
+def run_through_op(m, d, fixed_iterations: bool, do_step: bool, stages: int):
+    """``_run`` for calls that are being traced or vmapped: Dynamo-traceable Python around one operator call."""
+    outs = torch.ops.mujoco_torch_amd.step_leaves(_leaves_of(d), m._op_key_t, m._struct_uid, fixed_iterations, do_step, stages)
+    return _result(d, out_names(m, do_step, stages), outs)
+
+
+def run_inverse_through_op(m, d):
+    """``inverse`` under tracing / vmap: one ``inverse_leaves`` call."""
+    outs = torch.ops.mujoco_torch_amd.inverse_leaves(_leaves_of(d), m._op_key_t, m._struct_uid)
+    return _result(d, inverse_out_names(m), outs)

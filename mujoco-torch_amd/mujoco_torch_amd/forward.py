@@ -1,7 +1,7 @@
-"""``step`` / ``forward``: the reference's public hot-path API on top of the native library.
+"""``step`` / ``forward`` / ``inverse``: the reference's public hot-path API on top of the native library.
 
 Signatures and ownership rules follow reference ``_src/forward.py``: ``step(m, d,
-fixed_iterations=False) -> Data`` (:463-496) and ``forward`` (:373-401).  The caller's ``Data``
+fixed_iterations=False) -> Data`` (:463-496) and ``forward`` (:373-401); ``inverse(m, d)`` follows ``_src/inverse.py:86-102``.  The caller's ``Data``
 is never mutated; every leaf the step writes is fresh storage, untouched leaves alias the
 input (forward.py:473-475, dataclasses.py:112-120).  Unlike the reference, a *batched* ``Data``
 (leading dims on every leaf, exactly what ``make_data(mx).expand(B).clone()`` produces) is
@@ -31,6 +31,7 @@ import torch
 
 from . import native
 from .container import UnbatchedTensor
+from ._enums import EnableBit
 from .types import Data, Model
 
 # leaves the native step writes (reference Appendix: "Data leaves written by one step")
@@ -76,6 +77,19 @@ def _written_names(m: Model, step: bool):
         names += ["ten_length", "ten_J", "ten_velocity"]
     if step:
         names += _WRITTEN_STEP
+    return names
+
+
+# what an inverse call does not write (inverse.py runs neither _actuation nor _acceleration nor the solver): those leaves stay the caller's
+_NOT_WRITTEN_INVERSE = frozenset("actuator_force qfrc_actuator qfrc_smooth qacc_smooth qacc act_dot qacc_warmstart".split())
+
+
+def _inverse_names(m: Model):
+    """The ABI leaves ``inverse`` writes: the position / velocity stages, contacts, the constraint rows with their forces, sensors,
+    and qfrc_constraint (zeros without constraint rows, inverse.py:66-67).  ``qfrc_inverse`` is not an ABI leaf: it travels on its own."""
+    names = [n for n in _written_names(m, False) if n not in _NOT_WRITTEN_INVERSE]
+    if "qfrc_constraint" not in names:
+        names.append("qfrc_constraint")
     return names
 
 
@@ -329,7 +343,9 @@ def _run(m: Model, d: Data, fixed_iterations: bool, step: bool, out: Data | None
     return _run_native(m, d, fixed_iterations, step, out, stages)
 
 
-def _run_native(m: Model, d: Data, fixed_iterations: bool, step: bool, out: Data | None = None, stages: int = native.STAGE_ALL) -> Data:
+def _run_native(m: Model, d: Data, fixed_iterations: bool, step: bool, out: Data | None = None, stages: int = native.STAGE_ALL,
+                inverse: bool = False, qfrc_inverse: torch.Tensor | None = None) -> Data:
+    """``inverse=True``: an inverse-dynamics call (mjh_inverse); ``qfrc_inverse`` is then its destination when ``out`` is given."""
     qpos = d.qpos
     _require_device(qpos.device)
     dtype = qpos.dtype
@@ -342,12 +358,15 @@ def _run_native(m: Model, d: Data, fixed_iterations: bool, step: bool, out: Data
     T = m.tables
     sig = (T.uid, dtype, device, B)
     tab = _table(d, sig, nm.leaf_counts, B, dtype, device)
-    plan_key = (T.uid, step, stages, batch, dtype, device)
+    plan_key = (T.uid, "inverse" if inverse else step, stages, batch, dtype, device)
     plan = _PLANS.get(plan_key)
     if plan is None:
-        names = _written_names(m, step)
-        if not step and not (stages & 0x40):
-            names = [n for n in names if n != "sensordata"]  # sensors belong to complete forward passes
+        if inverse:
+            names = _inverse_names(m)
+        else:
+            names = _written_names(m, step)
+            if not step and not (stages & 0x40):
+                names = [n for n in names if n != "sensordata"]  # sensors belong to complete forward passes
         plan = _plan(m, d, names, batch, dtype, device, plan_key)
     out_struct = native.DataPtrs()
     out_arr = np.frombuffer(out_struct, dtype=np.uint64)[:_NLEAF]
@@ -369,13 +388,23 @@ def _run_native(m: Model, d: Data, fixed_iterations: bool, step: bool, out: Data
             raise ValueError("out= shares storage with the input on leaves the step writes: the phases read the caller's state "
                              "after the first outputs are written (and RK4 reads it in every stage); use distinct buffers")
     flags = native.FLAG_FIXED_ITERATIONS if fixed_iterations else 0
+    if inverse:
+        if int(m.opt.enableflags) & int(EnableBit.INVDISCRETE):  # read from the Model of THIS call (not part of the cached blob)
+            flags |= native.FLAG_INV_DISCRETE
+        if qfrc_inverse is None:
+            qfrc_inverse = torch.empty(batch + (int(m.nv),), dtype=dtype, device=device)
+        elif qfrc_inverse.dtype != dtype or qfrc_inverse.device != device or qfrc_inverse.numel() != B * int(m.nv) or not qfrc_inverse.is_contiguous():
+            raise ValueError(f"qfrc_inverse destination must be a contiguous {dtype} tensor of {B} x {int(m.nv)} elements on {device}")
     extra = T.sensors["extra_leaves"]
     if extra:  # Data leaves no stage writes but a sensor of this model reads (cacc, cfrc_int, subtree_linvel / angmom: include/mjhip.h MJH_DATA_EXTRA_IN)
         keep = _extra_inputs(tab, d, extra, B, int(m.nbody), dtype, device)
     stream, prev = _stream_and_guard(device)
     try:
         work = nm.workspace(B, stream)  # RK4 stages; candidate contacts of max_contact_points over box / mesh pairs; None for most Euler models
-        if step:
+        if inverse:
+            rc = nm.lib.mjh_inverse(nm.handle, ctypes.byref(tab.struct), ctypes.byref(out_struct), ctypes.c_void_p(qfrc_inverse.data_ptr()),
+                                    ctypes.c_void_p(work.data_ptr() if work is not None else None), B, flags, ctypes.c_void_p(stream))
+        elif step:
             rc = nm.lib.mjh_step(nm.handle, ctypes.byref(tab.struct), ctypes.byref(out_struct),
                                  ctypes.c_void_p(work.data_ptr() if work is not None else None), B, flags, ctypes.c_void_p(stream))
         else:
@@ -385,7 +414,7 @@ def _run_native(m: Model, d: Data, fixed_iterations: bool, step: bool, out: Data
         if prev is not None:
             torch.cuda.set_device(prev)
     if rc != 0:
-        raise RuntimeError(f"native step failed ({rc}): {nm.lib.mjh_last_error().decode()}")
+        raise RuntimeError(f"native {'inverse' if inverse else 'step'} failed ({rc}): {nm.lib.mjh_last_error().decode()}")
     if out is not None:
         return out
     # ---- the returned Data: the caller's container with the written leaves swapped for (lazy) views of the slab ----
@@ -419,6 +448,8 @@ def _run_native(m: Model, d: Data, fixed_iterations: bool, step: bool, out: Data
     for n, t in plan.empties.items():
         (con._fields if _IN_CONTACT[_IDX[n]] else f)[_KEY[n]] = t
     f["ncon"], f["nefc"] = _counts(m, device)
+    if inverse:
+        f["qfrc_inverse"] = qfrc_inverse
     rt = _PtrTab.__new__(_PtrTab)
     rt.struct = native.DataPtrs()
     full = np.frombuffer(rt.struct, dtype=np.uint64)
@@ -444,6 +475,21 @@ def step(m: Model, d: Data, fixed_iterations: bool = False, *, out: Data | None 
 def forward(m: Model, d: Data, fixed_iterations: bool = False, *, stages: int = native.STAGE_ALL) -> Data:
     """Forward dynamics (reference forward.py:373-401)."""
     return _run(m, d, fixed_iterations, step=False, stages=stages)
+
+
+def inverse(m: Model, d: Data) -> Data:
+    """Inverse dynamics (reference inverse.py:86-102): the generalized force ``qfrc_inverse`` that produces ``d.qacc``.
+
+    Runs the position and velocity stages and the sensors, then -- with ``opt.enableflags & EnableBit.INVDISCRETE`` -- converts the
+    discrete-time ``qacc`` of an Euler step to continuous time, computes the constraint forces the given ``qacc`` implies (``efc_force``,
+    ``qfrc_constraint``) and ``qfrc_inverse = qfrc_bias + M qacc - qfrc_passive - qfrc_constraint``.  The actuation, acceleration and
+    solver leaves (``actuator_force``, ``qfrc_actuator``, ``qfrc_smooth``, ``qacc_smooth``, ``act_dot``, ``qacc_warmstart``) and ``qacc``
+    itself are the caller's.  Batched like ``step``; ``torch.vmap`` / ``torch.compile`` go through the ``inverse_leaves`` operator."""
+    if torch.compiler.is_compiling() or not _plain(d.qpos):
+        from . import compile_op
+
+        return compile_op.run_inverse_through_op(m, d)
+    return _run_native(m, d, False, False, None, 0x1F, inverse=True)
 
 
 def reset_where(m: Model, d: Data, d0: Data, mask: torch.Tensor, qpos: torch.Tensor | None = None,

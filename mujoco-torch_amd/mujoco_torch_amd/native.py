@@ -28,6 +28,7 @@ LIB_PATH = os.environ.get("MJH_LIB") or os.path.join(os.path.dirname(_PKG_DIR), 
 
 MJH_F64, MJH_F32 = 0, 1
 FLAG_FIXED_ITERATIONS = 1
+FLAG_INV_DISCRETE = 2  # mjh_inverse: discrete_acc (opt.enableflags & INVDISCRETE)
 STAGE_ALL = 0x7F
 
 
@@ -230,6 +231,8 @@ def load_library(path: str | None = None):
     lib.mjh_forward.restype = ctypes.c_int
     lib.mjh_step.argtypes = [ctypes.c_void_p, ctypes.POINTER(DataPtrs), ctypes.POINTER(DataPtrs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]
     lib.mjh_step.restype = ctypes.c_int
+    lib.mjh_inverse.argtypes = [ctypes.c_void_p, ctypes.POINTER(DataPtrs), ctypes.POINTER(DataPtrs), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]
+    lib.mjh_inverse.restype = ctypes.c_int
     lib.mjh_reset_where.argtypes = [ctypes.c_void_p, ctypes.POINTER(DataPtrs), ctypes.POINTER(DataPtrs), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
     lib.mjh_reset_where.restype = ctypes.c_int
     lib.mjh_debug_phase_timing.argtypes = [ctypes.c_int]
