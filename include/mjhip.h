@@ -9,6 +9,7 @@
  *   mjh_forward        <- forward.forward(m, d)                       (_src/forward.py:373-401)
  *   mjh_step           <- forward.step(m, d, fixed_iterations)        (_src/forward.py:463-496)
  *   mjh_inverse        <- inverse.inverse(m, d)                       (_src/inverse.py:86-102)
+ *   mjh_ray            <- ray.ray(m, d, pnt, vec, ...)               (_src/ray.py:375-452)
  *
  * Conventions
  *  - every Data leaf is batch-major contiguous: shape [B, ...] exactly as
@@ -389,6 +390,28 @@ int64_t mjh_model_work_bytes(const mjhModel* m);
  * actuator_force / qfrc_actuator read the caller's (in).  `work`: as for mjh_forward. */
 int mjh_inverse(const mjhModel* m, const mjhData* in, mjhData* out, void* qfrc_inverse, void* work, int64_t B, int flags, void* hip_stream);
 
+/* the geoms one mjh_ray call tests, built by the caller from the model and its filters (ray.py:400-415: flg_static, bodyexclude, geomgroup, alpha).
+ * Every pointer is device memory.  `cand` holds ncand rows of four int32: geom id, geom type (mjtGeom: plane 0, sphere 2, capsule 3, ellipsoid 4,
+ * cylinder 5, box 6, mesh 7), first and end triangle in `tri` (meshes; anything for the primitives).  The rows are in tie-break order -- the reference's
+ * type-major order (plane, sphere, capsule, ellipsoid, cylinder, box, mesh), ascending geom id within a type -- and the first minimum wins.
+ * `tri`: [ntri][9] reals of the call's dtype, a triangle's three vertices in the geom frame.  `geom_size`: [ngeom][3] reals, the sizes to use (read
+ * on the device by every call, so value edits of the Model need no new table).  The library does not validate the rows: ids must be < ngeom and
+ * triangle ranges inside `tri`. */
+typedef struct mjhRayCands {
+  int64_t ncand;
+  const int32_t* cand;
+  const void* tri;
+  const void* geom_size;
+} mjhRayCands;
+
+/* batched ray casting (ray.py:375-452): R rays in each of B environments against the candidate geoms.  geom_xpos [B, ngeom, 3] / geom_xmat
+ * [B, ngeom, 9] are the environments' geom frames (a forward pass's leaves).  Ray r of environment e starts at pnt[e * pnt_env + r * pnt_ray + k]
+ * and runs along vec[e * vec_env + r * vec_ray + k], k = 0..2, in element strides (0: shared); vec is not normalised.  Writes
+ * dist [B * R] (the ray parameter of the nearest hit, -1 for none; the model's dtype) and geomid [B * R] (int64, -1 for none), environment-major.
+ * Returns 0 or a negative code; B == 0 is a no-op. */
+int mjh_ray(const mjhModel* m, const void* geom_xpos, const void* geom_xmat, const void* pnt, int64_t pnt_env, int64_t pnt_ray, const void* vec,
+            int64_t vec_env, int64_t vec_ray, int64_t B, int64_t R, const mjhRayCands* cands, void* dist, int64_t* geomid, void* hip_stream);
+
 /* per-environment ELEMENT count of every mjhData leaf in ABI order (reals, then int32, then int64 leaves): a leaf handed to
  * mjh_forward / mjh_step / mjh_reset_where must hold exactly B * count elements.  The binding validates tensor sizes against
  * this before it passes raw pointers (the kernels index `ptr + env * count` unchecked).  Writes min(n, max) entries, returns n. */
@@ -407,14 +430,14 @@ int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsi
 int mjh_model_lds_bytes(const mjhModel* m, int phase);
 
 /* measurement aid used by bench.py for the per-kernel roofline: while enabled, every kernel launch of mjh_step / mjh_forward is
- * bracketed by HIP events on the launch stream; mjh_debug_phase_times() waits for the most recent call and returns, per launch,
+ * bracketed by HIP events on the launch stream (mjh_inverse and mjh_ray too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
  * the elapsed milliseconds and the kernel id (0..4 pipeline phases, 5 velocity phase with fluid / gravcomp / tendons, 6 solver phase
  * with frictionloss / equality / dense limit rows, 7 constraint phase with those rows or max_contact_points, 8 constraint phase of small
  * models (contact rows straight to the leaf), 9 solver phase as the register solver (mjh_sol2_kernel: two environments per wavefront),
  * 10 convex narrow phase, 11 sensors, 12 kinematics + velocity phases as one kernel -- then 0 and 3 do not appear --, 13 kinematics + crb / factor + velocity as one kernel
  * (models whose crb stage packs like the other two), then 12 and 1 do not appear; 14 constraint stage + register solver + integrator as one kernel, 16 the whole pass as
  * one kernel (humanoid-class models), 17 kernel 13 on two wavefronts per workgroup, 18 one RK4 stage of a small Newton model as one kernel, 19 that kernel running the
- * constraint phase + first solver tier only, 20 the inverse-dynamics tail of mjh_inverse; 15 is unassigned).  Returns the number of launches (<= max) or a negative code. */
+ * constraint phase + first solver tier only, 20 the inverse-dynamics tail of mjh_inverse, 21 the ray kernel of mjh_ray; 15 is unassigned).  Returns the number of launches (<= max) or a negative code. */
 int mjh_debug_phase_timing(int enable);
 int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
 

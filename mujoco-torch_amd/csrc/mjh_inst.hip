@@ -6,6 +6,7 @@
 #include "mjh_convex.h"
 #include "mjh_sensor.h"
 #include "mjh_inverse.h"
+#include "mjh_ray.h"
 #include "mjh_instances.h"
 
 #define MJH_CAT_(a, b) a##b
@@ -17,4 +18,7 @@
 MJH_CAT(MJH_INST_G, MJH_INST_GROUP)(X_, S_, C_, N_, MJH_INST_REAL)
 #if MJH_INST_GROUP == 19
 template __global__ void mjh_inverse_kernel<MJH_INST_REAL>(InvArgs<MJH_INST_REAL>);
+#endif
+#if MJH_INST_GROUP == 20
+template __global__ void mjh_ray_kernel<MJH_INST_REAL>(RayArgs<MJH_INST_REAL>);
 #endif

@@ -13,82 +13,12 @@
 // intersected in double and rounded: the float64 square roots and divisions made the ant's kernel VALU-bound, profiles/r04/notes.md).
 #pragma once
 #include "mjh_kernels.h"
+#include "mjh_ray.h"
 
 #define M (kargs<REAL>().M)
 #define in (kargs<REAL>().in)
 #define out (kargs<REAL>().cur)
 #define KA (kargs<REAL>())
-
-// RT: the type the intersections run in = the Data dtype (see the header comment)
-template <typename RT> __device__ __forceinline__ RT ray_safe_div(RT num, RT den) { return num / (den + (den == 0 ? (RT)(float)mjMINVAL : (RT)0)); }
-template <typename RT>
-__device__ __forceinline__ void ray_quad(RT a, RT b, RT c, RT& x0, RT& x1) {  // ray.py:28-40
-  const RT det = b * b - a * c, det2 = r_sqrt<RT>(det);
-  const RT r0 = ray_safe_div<RT>(-b - det2, a), r1 = ray_safe_div<RT>(-b + det2, a);
-  const RT inf = (RT)__builtin_inf();
-  x0 = ((det < (RT)mjMINVAL) || (r0 < 0)) ? inf : r0;
-  x1 = ((det < (RT)mjMINVAL) || (r1 < 0)) ? inf : r1;
-}
-template <typename RT> __device__ __forceinline__ RT ray_dot3(const RT* a, const RT* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-template <typename RT>
-__device__ __forceinline__ RT ray_geom(int type, const RT* size, const RT* pnt, const RT* vec) {
-  const RT inf = (RT)__builtin_inf();
-  if (type == 0) {  // plane :43-57
-    const RT x = -ray_safe_div<RT>(pnt[2], vec[2]);
-    bool valid = (vec[2] <= -(RT)mjMINVAL) && (x >= 0);
-    for (int i = 0; i < 2; i++) { const RT p = pnt[i] + x * vec[i]; valid = valid && ((size[i] <= 0) || (r_abs(p) <= size[i])); }
-    return valid ? x : inf;
-  }
-  if (type == 2) {  // sphere :60-69
-    RT x0, x1;
-    ray_quad<RT>(ray_dot3(vec, vec), ray_dot3(vec, pnt), ray_dot3(pnt, pnt) - size[0] * size[0], x0, x1);
-    return isinf(x0) ? x1 : x0;
-  }
-  if (type == 3 || type == 5) {  // capsule :72-106, cylinder :235-268: the round side first
-    const RT a = vec[0] * vec[0] + vec[1] * vec[1], b = vec[0] * pnt[0] + vec[1] * pnt[1], c = (pnt[0] * pnt[0] + pnt[1] * pnt[1]) - size[0] * size[0];
-    RT x0, x1;
-    ray_quad<RT>(a, b, c, x0, x1);
-    RT x = isinf(x0) ? x1 : x0;
-    x = (r_abs(pnt[2] + x * vec[2]) <= size[1]) ? x : inf;
-    for (int cap = 0; cap < 2; cap++) {
-      if (type == 3) {  // spherical caps
-        const RT dif[3] = {pnt[0], pnt[1], cap == 0 ? pnt[2] - size[1] : pnt[2] + size[1]};
-        ray_quad<RT>(ray_dot3(vec, vec), ray_dot3(vec, dif), ray_dot3(dif, dif) - size[0] * size[0], x0, x1);
-        if (cap == 0) {
-          if ((pnt[2] + x0 * vec[2] >= size[1]) && (x0 < x)) x = x0;
-          if ((pnt[2] + x1 * vec[2] >= size[1]) && (x1 < x)) x = x1;
-        } else {
-          if ((pnt[2] + x0 * vec[2] <= -size[1]) && (x0 < x)) x = x0;
-          if ((pnt[2] + x1 * vec[2] <= -size[1]) && (x1 < x)) x = x1;
-        }
-      } else {  // flat caps
-        const RT t = ray_safe_div<RT>((cap == 0 ? size[1] : -size[1]) - pnt[2], vec[2]);
-        const RT p0 = pnt[0] + t * vec[0], p1 = pnt[1] + t * vec[1];
-        if ((t >= 0) && (p0 * p0 + p1 * p1 <= size[0] * size[0]) && (t < x)) x = t;
-      }
-    }
-    return x;
-  }
-  if (type == 4) {  // ellipsoid :109-129
-    RT s[3], sv[3], sp[3];
-    for (int i = 0; i < 3; i++) { s[i] = ray_safe_div<RT>((RT)1, size[i] * size[i]); sv[i] = s[i] * vec[i]; sp[i] = s[i] * pnt[i]; }
-    RT x0, x1;
-    ray_quad<RT>(ray_dot3(sv, vec), ray_dot3(sv, pnt), ray_dot3(sp, pnt) - 1, x0, x1);
-    return isinf(x0) ? x1 : x0;
-  }
-  if (type == 6) {  // box :132-161
-    RT best = inf;
-    for (int f = 0; f < 6; f++) {
-      const int ax = f % 3, i0 = ax == 0 ? 1 : 0, i1 = ax == 2 ? 1 : 2;
-      const RT x = f < 3 ? ray_safe_div<RT>(size[ax] - pnt[ax], vec[ax]) : -ray_safe_div<RT>(size[ax] + pnt[ax], vec[ax]);
-      const RT p0 = pnt[i0] + x * vec[i0], p1 = pnt[i1] + x * vec[i1];
-      const bool valid = (r_abs(p0) <= size[i0]) && (r_abs(p1) <= size[i1]) && (x >= 0);
-      if (valid && x < best) best = x;
-    }
-    return best;
-  }
-  return inf;
-}
 
 // one ray test: rangefinder M.rf_sensor[q] against geom M.rf_geom[q].  The ray starts at the site and runs along its z axis
 // (sensor.py:94-108); it is moved into the geom frame and intersected (ray.py:28-290) in the Data dtype.
@@ -100,13 +30,8 @@ __device__ __forceinline__ double rf_task(int64_t e, int q) {
   const REAL pos[3] = {posp[0], posp[1], posp[2]};
   const REAL vec[3] = {rot[2], rot[5], rot[8]};
   const REAL *gm = out.geom_xmat + (e * M.ngeom + g) * 9, *gp = out.geom_xpos + (e * M.ngeom + g) * 3;
-  const REAL d3[3] = {pos[0] - gp[0], pos[1] - gp[1], pos[2] - gp[2]};
   REAL dp[3], dv[3];
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    dp[i] = gm[i] * d3[0] + gm[3 + i] * d3[1] + gm[6 + i] * d3[2];
-    dv[i] = gm[i] * vec[0] + gm[3 + i] * vec[1] + gm[6 + i] * vec[2];
-  }
+  ray_to_geom<REAL>(gm, gp, pos, vec, dp, dv);
   const REAL size[3] = {M.rf_gsize[3 * q], M.rf_gsize[3 * q + 1], M.rf_gsize[3 * q + 2]};
   return (double)ray_geom<REAL>(M.rf_gtype[q], size, dp, dv);
 }

@@ -17,6 +17,7 @@
 #include "mjh_reset.h"
 #include "mjh_io.h"
 #include "mjh_inverse.h"
+#include "mjh_ray.h"
 #include "mjh_instances.h"
 
 // the kernels are compiled in their own translation units (mjh_inst.hip, one per build group): this file is the host side only
@@ -28,6 +29,8 @@ MJH_INST_ALL(X_, S_, C_, N_, double)
 MJH_INST_ALL(X_, S_, C_, N_, float)
 extern template __global__ void mjh_inverse_kernel<double>(InvArgs<double>);  // (build group 19)
 extern template __global__ void mjh_inverse_kernel<float>(InvArgs<float>);
+extern template __global__ void mjh_ray_kernel<double>(RayArgs<double>);  // (build group 20)
+extern template __global__ void mjh_ray_kernel<float>(RayArgs<float>);
 #undef X_
 #undef S_
 #undef C_
@@ -42,7 +45,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 static struct {
   bool on = false;
   int n = 0;                          // launches recorded by the last call
-  int id[MJH_TIMING_MAX];             // 0..8 phase-kernel ids, 9 register solver, 10 convex narrow phase, 11 sensors, 12 / 13 / 17 fused kinematics (+ crb) + velocity, 14 fused constraint + register solver, 16 whole pass, 18 / 19 stage kernel, 20 inverse-dynamics tail (15: unassigned)
+  int id[MJH_TIMING_MAX];             // 0..8 phase-kernel ids, 9 register solver, 10 convex narrow phase, 11 sensors, 12 / 13 / 17 fused kinematics (+ crb) + velocity, 14 fused constraint + register solver, 16 whole pass, 18 / 19 stage kernel, 20 inverse-dynamics tail, 21 ray kernel (15: unassigned)
   hipEvent_t ev[MJH_TIMING_MAX + 1];  // ev[i] .. ev[i + 1] brackets launch i
 } g_timing;
 static inline void timing_begin(hipStream_t s) { if (g_timing.on) { g_timing.n = 0; (void)hipEventRecord(g_timing.ev[0], s); } }
@@ -1215,6 +1218,45 @@ int run_inverse(const mjhModel* m, const DevModel<REAL>& M, const mjhData* in, m
   return 0;
 }
 
+// ray casting (ray.py:375-452): one lane per (environment, ray) pair, the candidates' geom frames staged in LDS chunk by chunk (mjh_ray.h)
+template <typename REAL>
+int run_ray(const mjhModel* m, const DevModel<REAL>& M, const void* geom_xpos, const void* geom_xmat, const void* pnt, int64_t pnt_env, int64_t pnt_ray,
+            const void* vec, int64_t vec_env, int64_t vec_ray, int64_t B, int64_t R, const mjhRayCands* c, void* dist, int64_t* geomid, void* stream) {
+  (void)m;
+  if (B <= 0 || R <= 0) return B < 0 || R < 0 ? fail(-22, "ray: B and R must be >= 0") : 0;
+  if (R > (1 << 30)) return fail(-22, "ray: more than 2^30 rays per environment");
+  if (c->ncand < 0 || c->ncand > (1 << 30)) return fail(-22, "ray: bad candidate count");
+  if (!geom_xpos || !geom_xmat || !pnt || !vec || !dist || !geomid || (c->ncand > 0 && (!c->cand || !c->geom_size))) return fail(-22, "ray: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  timing_begin(s);
+  RayArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+  a.geom_xpos = reinterpret_cast<const REAL*>(geom_xpos); a.geom_xmat = reinterpret_cast<const REAL*>(geom_xmat);
+  a.pnt = reinterpret_cast<const REAL*>(pnt); a.vec = reinterpret_cast<const REAL*>(vec);
+  a.pnt_env = pnt_env; a.pnt_ray = pnt_ray; a.vec_env = vec_env; a.vec_ray = vec_ray;
+  a.cand = c->cand; a.tri = reinterpret_cast<const REAL*>(c->tri); a.geom_size = reinterpret_cast<const REAL*>(c->geom_size);
+  a.dist = reinterpret_cast<REAL*>(dist); a.geomid = geomid;
+  a.ngeom = M.ngeom; a.ncand = (int)c->ncand; a.R = (int)R;
+  // LDS: the environments one workgroup's 256 consecutive pairs can touch (<= 255 / R + 2, at most 256) x a chunk of candidates x 12 reals, within
+  // LDS_BUDGET per workgroup (three workgroups per CU at the worst); a chunk never holds more candidates than there are
+  constexpr int LDS_BUDGET = 48 * 1024;
+  const int64_t span = R >= 256 ? 2 : (255 / R + 2 < 256 ? 255 / R + 2 : 256);
+  int64_t chunk = LDS_BUDGET / (span * 12 * (int64_t)sizeof(REAL));
+  if (chunk > c->ncand) chunk = c->ncand;
+  if (chunk < 1) chunk = 1;
+  a.chunk = (int)chunk;
+  const size_t lds = c->ncand > 0 ? (size_t)(span * chunk * 12 * (int64_t)sizeof(REAL)) : 0;
+  const int64_t total = B * R, cap = (int64_t)MJH_RAY_WG * max_grid();
+  for (int64_t q0 = 0; q0 < total; q0 += cap) {  // (no grid-stride loop: one launch per 2^20 workgroups)
+    const int64_t n = total - q0 < cap ? total - q0 : cap;
+    a.env_base = q0 / R; a.r_base = (int)(q0 % R); a.npairs = (int)n;
+    hipLaunchKernelGGL((mjh_ray_kernel<REAL>), dim3((unsigned)((n + MJH_RAY_WG - 1) / MJH_RAY_WG)), dim3(MJH_RAY_WG), lds, s, a);
+    HIP_TRY(hipGetLastError());
+  }
+  timing_mark(s, 21);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1255,6 +1297,13 @@ int mjh_inverse(const mjhModel* m, const mjhData* in, mjhData* out, void* qfrc_i
   if (!m || !in || !out) return fail(-22, "null argument");
   return m->dtype == MJH_F64 ? run_inverse<double>(m, m->m64, in, out, qfrc_inverse, work, B, flags, stream)
                              : run_inverse<float>(m, m->m32, in, out, qfrc_inverse, work, B, flags, stream);
+}
+
+int mjh_ray(const mjhModel* m, const void* geom_xpos, const void* geom_xmat, const void* pnt, int64_t pnt_env, int64_t pnt_ray, const void* vec,
+            int64_t vec_env, int64_t vec_ray, int64_t B, int64_t R, const mjhRayCands* cands, void* dist, int64_t* geomid, void* stream) {
+  if (!m || !cands) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_ray<double>(m, m->m64, geom_xpos, geom_xmat, pnt, pnt_env, pnt_ray, vec, vec_env, vec_ray, B, R, cands, dist, geomid, stream)
+                             : run_ray<float>(m, m->m32, geom_xpos, geom_xmat, pnt, pnt_env, pnt_ray, vec, vec_env, vec_ray, B, R, cands, dist, geomid, stream);
 }
 
 int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsigned char* mask, const void* qpos_rows,

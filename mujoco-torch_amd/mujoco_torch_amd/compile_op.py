@@ -249,3 +249,43 @@ def run_inverse_through_op(m, d):
     """``inverse`` under tracing / vmap: one ``inverse_leaves`` call."""
     outs = torch.ops.mujoco_torch_amd.inverse_leaves(_leaves_of(d), m._op_key_t, m._struct_uid)
     return _result(d, inverse_out_names(m), outs)
+
+
+# ---- ray casting (ray.py): its own operator over the two geom-frame leaves and the rays ----------------------------------------
+
+@torch.library.custom_op("mujoco_torch_amd::ray_leaves", mutates_args=())
+def ray_leaves(geom_xpos: torch.Tensor, geom_xmat: torch.Tensor, pnt: torch.Tensor, vec: torch.Tensor, model_key: torch.Tensor, struct_uid: str,
+               geomgroup: list[int], flg_static: bool, bodyexclude: list[int]) -> tuple[torch.Tensor, torch.Tensor]:
+    from .ray import ray_native
+
+    m = _checked_model(model_key, struct_uid, "ray_leaves", "ray")
+    return ray_native(m, geom_xpos, geom_xmat, pnt, vec, (flg_static, bodyexclude, geomgroup))
+
+
+@ray_leaves.register_fake
+def _(geom_xpos, geom_xmat, pnt, vec, model_key, struct_uid, geomgroup, flg_static, bodyexclude):
+    from .ray import check_args, filter_key
+
+    filter_key(_structure(struct_uid).tables.ray, geomgroup, flg_static, bodyexclude)
+    shape = check_args(geom_xpos, geom_xmat, pnt, vec)[0]
+    return geom_xpos.new_empty(shape), geom_xpos.new_empty(shape, dtype=torch.int64)
+
+
+def _ray_leaves_vmap(info, in_dims, geom_xpos, geom_xmat, pnt, vec, model_key, struct_uid, geomgroup, flg_static, bodyexclude):
+    # the mapped dimension becomes the leading batch dimension of the Data; an unmapped frame leaf is broadcast, an unmapped ray keeps its
+    # meaning: (3,) stays shared, anything else is the same for every mapped environment
+    B = info.batch_size
+    args = []
+    for i, t in enumerate((geom_xpos, geom_xmat, pnt, vec)):
+        bd = in_dims[i]
+        if bd is not None:
+            args.append(t.movedim(bd, 0))
+        elif i >= 2 and t.dim() == 1:
+            args.append(t)
+        else:
+            args.append(t.unsqueeze(0).expand(B, *t.shape))
+    dist, geomid = ray_leaves(*args, model_key, struct_uid, geomgroup, flg_static, bodyexclude)
+    return (dist, geomid), (0, 0)
+
+
+torch.library.register_vmap(ray_leaves, _ray_leaves_vmap)

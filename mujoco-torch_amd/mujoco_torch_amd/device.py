@@ -40,6 +40,7 @@ from ._enums import (
     SUPPORTED_CONDIM,
 )
 from .container import UnbatchedTensor
+from .ray import host_tables as ray_tables
 from .types import MODEL_FIELDS, Model, Option, Statistic
 
 _cache_id_counter = itertools.count(1)
@@ -327,6 +328,7 @@ def _build_tables(m, dtype) -> StaticTables:
     T.tendon = _tendon_tables(m, flags)
     T.nlt = len(T.tendon["lim"])  # tendon limit rows
     assert len(lim) + len(lim_ball) + T.nlt == nl, (len(lim), len(lim_ball), nl)
+    T.ray = ray_tables(m)  # ray casting (ray.py): what its candidate tables are built from
     return T
 
 

@@ -211,6 +211,12 @@ def data_field_tensor(d, name):
 _lib = None
 
 
+class RayCands(ctypes.Structure):
+    """include/mjhip.h mjhRayCands: the candidate geoms of one mjh_ray call (device pointers)."""
+
+    _fields_ = [("ncand", ctypes.c_int64), ("cand", ctypes.c_void_p), ("tri", ctypes.c_void_p), ("geom_size", ctypes.c_void_p)]
+
+
 def load_library(path: str | None = None):
     """Loads libmjhip.so (once). Raises if it has not been built: no fallback path exists."""
     global _lib
@@ -233,6 +239,11 @@ def load_library(path: str | None = None):
     lib.mjh_step.restype = ctypes.c_int
     lib.mjh_inverse.argtypes = [ctypes.c_void_p, ctypes.POINTER(DataPtrs), ctypes.POINTER(DataPtrs), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]
     lib.mjh_inverse.restype = ctypes.c_int
+    if hasattr(lib, "mjh_ray"):  # (a build from before ray casting still binds everything else: tools/bitcmp.py steps a parent's library)
+        lib.mjh_ray.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(RayCands), ctypes.c_void_p, ctypes.c_void_p,
+                                ctypes.c_void_p]
+        lib.mjh_ray.restype = ctypes.c_int
     lib.mjh_reset_where.argtypes = [ctypes.c_void_p, ctypes.POINTER(DataPtrs), ctypes.POINTER(DataPtrs), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
     lib.mjh_reset_where.restype = ctypes.c_int
     lib.mjh_debug_phase_timing.argtypes = [ctypes.c_int]

@@ -1,0 +1,244 @@
+"""Generate tests/golden/ray/<case>.npz from the REFERENCE's own ray casting (mujoco_torch/_src/ray.py), in the build container.
+
+TEST INFRASTRUCTURE, container-only (needs the reference tree; see oracle/ref_harness.py, which this script imports unchanged, as it does
+oracle/gen_golden.make_inputs).  For each case and environment:
+  1. the seeded inputs of ``make_inputs(recipe)``, one reference ``forward`` in the case's dtype: ``geom_xpos`` / ``geom_xmat`` are recorded;
+  2. R rays (``RAY_MIX``): aimed at geom centres, random, a downward height-scan grid, from inside a sphere / capsule / box, parallel to the
+     plane, and rays that miss everything -- recorded in the case's dtype;
+  3. ``dist`` / ``geomid``: the reference ``ray.ray`` (float64 model, the recorded frames and rays widened to float64) on the primitives.
+The reference's ``_ray_mesh`` does not run under current torch (``torch.tensor`` inside ``torch.vmap``), so for models with meshes the
+mesh geoms are excluded from that call (their bodies carry no other geom: checked) and each candidate mesh is tested with the reference's
+``_ray_triangle`` over its triangles, the basis from the reference's ``math.orthogonals(math.normalize(vec))`` built outside ``vmap``;
+the two are combined in the tie-break order (primitives before meshes, ascending geom id, first minimum wins).  Every candidate's own
+distance (the reference's ``ray_geom`` / triangle minimum) gives the runner-up distance of each ray, recorded so that a test can accept
+either id of a tie.  Rays whose mesh hit lies within 1e-7 (barycentric) of a triangle edge are dropped before R are kept.
+
+``ray_geom.npz`` holds a table of single-primitive cases against the reference ``ray.ray_geom``.
+The files live in a directory of their own: tests/golden/*.npz are the step recordings the oracle suites iterate over.
+
+Run:  python tools/gen_ray_golden.py [case ...]
+"""
+
+import json
+import os
+import sys
+import types
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(HERE)
+for p in (os.path.join(REPO, "oracle"), os.path.join(REPO, "mujoco-torch_amd"), HERE):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import ref_harness  # noqa: E402
+from gen_golden import make_inputs  # noqa: E402
+from gen_inverse_golden import load_lite, put  # noqa: E402
+
+GOLD = os.path.join(REPO, "tests", "golden", "ray")
+MESH = 7
+EDGE_TOL = 1e-7
+
+# case: (xml, dtype, environments, make_inputs recipe, rays kept per environment, filters (flg_static, bodyexclude, geomgroup))
+CASES = {
+    "humanoid_f64": ("humanoid", "float64", 4, "perturbed", 48, (True, -1, ())),
+    "humanoid_nostatic_f64": ("humanoid", "float64", 4, "perturbed", 48, (False, [1], ())),   # no floor, torso excluded
+    "ant_f64": ("ant", "float64", 4, "bench_ctrl", 48, (True, -1, ())),
+    "ant_f32": ("ant", "float32", 4, "bench_ctrl", 48, (True, -1, ())),
+    "mesh_contact_f64": ("mesh_contact", "float64", 4, "convex", 48, (True, -1, ())),
+    "mesh_contact_f32": ("mesh_contact", "float32", 4, "convex", 48, (True, -1, ())),
+    "sensor_rig_f64": ("sensor_rig", "float64", 4, "sensor_rig", 48, (True, -1, ())),        # cylinder, ellipsoid
+    "satellite_small_f64": ("satellite_small", "float64", 4, "generic", 48, (True, -1, ())),  # cylinders
+    "ray_scene_f64": ("ray_scene", "float64", 4, "convex", 64, (True, -1, ())),              # every type, a transparent box
+    "ray_scene_group_f64": ("ray_scene", "float64", 4, "convex", 64, (True, [2], (1, 0, 1, 1, 0, 0))),  # geomgroup, bodyexclude
+    "ray_scene_f32": ("ray_scene", "float32", 4, "convex", 64, (False, -1, ())),
+}
+RAY_MIX = "per environment, RandomState(500 + env): 1/4 aimed at geom centres, 1/8 random, a 4 x 4 downward height scan, 1/8 from inside spheres / capsules / boxes, 1/16 parallel to the plane, 1/16 missing upward, the rest random from above"
+
+
+def make_rays(rng, xpos, gtype, n):
+    """n candidate rays (float64): origins and unnormalised directions."""
+    ng = len(gtype)
+    P, V = [], []
+    inside = [g for g in range(ng) if int(gtype[g]) in (2, 3, 6)]
+    grid = [(x, y) for x in np.linspace(-0.9, 0.9, 4) for y in np.linspace(-0.9, 0.9, 4)]
+    for i in range(n):
+        k = i % 16
+        if k < 4:  # aimed at a geom centre
+            g = rng.randint(ng)
+            p = xpos[g] + rng.uniform(0.5, 2.0) * _unit(rng)
+            v = (xpos[g] - p) * rng.uniform(0.3, 3.0)
+        elif k < 6:  # random
+            p, v = rng.uniform(-1.5, 1.5, 3) + [0, 0, 0.5], _unit(rng) * rng.uniform(0.2, 2.0)
+        elif k < 8 and inside:  # from inside a sphere / capsule / box: the far root
+            g = inside[rng.randint(len(inside))]
+            p, v = xpos[g] + 0.01 * rng.randn(3), _unit(rng)
+        elif k < 10:  # height scan
+            x, y = grid[(i // 16 * 2 + k - 8) % 16]
+            p, v = np.array([x, y, 2.0]), np.array([0.0, 0.0, -rng.uniform(0.5, 2.0)])
+        elif k == 10:  # parallel to the plane
+            p, v = np.array([rng.uniform(-1, 1), rng.uniform(-1, 1), rng.uniform(0.05, 0.6)]), np.r_[_unit(rng)[:2], 0.0]
+        elif k == 11:  # misses everything
+            p, v = np.array([rng.uniform(-1, 1), rng.uniform(-1, 1), 20.0]), np.array([0.1 * rng.randn(), 0.1 * rng.randn(), 1.0])
+        else:  # random from above
+            p = np.array([rng.uniform(-1.5, 1.5), rng.uniform(-1.5, 1.5), rng.uniform(0.8, 2.5)])
+            v = np.array([rng.randn(), rng.randn(), -abs(rng.randn()) - 0.3])
+        P.append(p)
+        V.append(v)
+    return np.array(P), np.array(V)
+
+
+def _unit(rng):
+    u = rng.randn(3)
+    return u / np.linalg.norm(u)
+
+
+def candidate_ids(ref, mj, filters):
+    """The candidates in tie-break order: the reference's precompute_ray_data (primitives), then the mesh geoms under the same filters."""
+    flg_static, bodyexclude, geomgroup = filters
+    ids = [int(g) for e in ref.ray.precompute_ray_data(mj, flg_static, bodyexclude, geomgroup) for g, ok in zip(e[1]._cpu.tolist(), e[3]._cpu.tolist()) if ok]
+    be = bodyexclude if isinstance(bodyexclude, (list, tuple)) else [bodyexclude]
+    gtype, gbody = np.asarray(mj.geom_type), np.asarray(mj.geom_bodyid)
+    for g in np.nonzero(gtype == MESH)[0]:
+        keep = flg_static or int(np.asarray(mj.body_weldid)[gbody[g]]) != 0
+        keep = keep and int(gbody[g]) not in be
+        if geomgroup:
+            keep = keep and bool(geomgroup[int(np.asarray(mj.geom_group)[g])])
+        keep = keep and (np.asarray(mj.geom_rgba)[g, 3] != 0 or int(np.asarray(mj.geom_matid)[g]) != -1)
+        if keep:
+            ids.append(int(g))
+    return ids
+
+
+def main(only=None, out_dir=GOLD):
+    ref = ref_harness.load()
+    os.makedirs(out_dir, exist_ok=True)
+    for case, (xml, dtype_s, nenv, recipe, nray, filters) in CASES.items():
+        if only and case not in only:
+            continue
+        dtype = getattr(torch, dtype_s)
+        lite = load_lite(xml, {})
+        mref, _ = put(ref, lite, dtype)
+        m64, _ = put(ref, lite, torch.float64)
+        mj = ref.mujoco.MjModel(lite)
+        cand = candidate_ids(ref, mj, filters)
+        flg_static, bodyexclude, geomgroup = filters
+        gtype = np.asarray(lite.geom_type)
+        gbody = np.asarray(lite.geom_bodyid)
+        mesh_geoms = [g for g in range(int(lite.ngeom)) if gtype[g] == MESH]
+        for g in mesh_geoms:
+            assert np.sum(gbody == gbody[g]) == 1, "a mesh body carries other geoms: the primitive call cannot exclude the mesh alone"
+        be_prim = (list(bodyexclude) if isinstance(bodyexclude, (list, tuple)) else [bodyexclude]) + [int(gbody[g]) for g in mesh_geoms]
+        store = {}
+        for env in range(nenv):
+            inp = make_inputs(recipe, lite, env)
+            d = ref.io.make_data(mref)
+            d = d.replace(**{k: torch.tensor(np.asarray(v, dtype=np.float64)) for k, v in inp.items()})
+            if dtype != torch.float64:
+                d = d.to(dtype)
+            d = ref.forward.forward(mref, d)
+            xpos, xmat = d.geom_xpos.detach().clone(), d.geom_xmat.detach().clone()
+            x64 = types.SimpleNamespace(geom_xpos=xpos.double(), geom_xmat=xmat.double())
+            rng = np.random.RandomState(500 + env)
+            P, V = make_rays(rng, xpos.double().numpy(), gtype, 4 * nray)
+            P, V = P.astype(dtype_s).astype(np.float64), V.astype(dtype_s).astype(np.float64)
+            kept = []
+            for i in range(len(P)):
+                res = one_ray(ref, m64, x64, P[i], V[i], cand, filters, be_prim, gtype, lite)
+                if res is not None:
+                    kept.append((P[i], V[i]) + res)
+                if len(kept) == nray:
+                    break
+            assert len(kept) == nray, f"{case} env {env}: only {len(kept)} usable rays"
+            store[f"{env}/geom_xpos"] = xpos.numpy()
+            store[f"{env}/geom_xmat"] = xmat.numpy()
+            store[f"{env}/pnt"] = np.array([k[0] for k in kept]).astype(dtype_s)
+            store[f"{env}/vec"] = np.array([k[1] for k in kept]).astype(dtype_s)
+            store[f"{env}/dist"] = np.array([k[2] for k in kept])
+            store[f"{env}/geomid"] = np.array([k[3] for k in kept], dtype=np.int64)
+            store[f"{env}/runner_up"] = np.array([k[4] for k in kept])
+        hits = np.concatenate([store[f"{e}/geomid"] for e in range(nenv)])
+        meta = dict(xml=xml, dtype=dtype_s, nenv=nenv, recipe=recipe, nray=nray, flg_static=flg_static,
+                    bodyexclude=bodyexclude, geomgroup=list(geomgroup), candidates=cand, rays=RAY_MIX,
+                    reference="ray.ray (float64 model, recorded frames / rays widened to float64) on the primitives; meshes: _ray_triangle over "
+                              "mesh_face / mesh_vert with math.orthogonals(math.normalize(vec)) outside vmap, combined in tie-break order "
+                              "(primitives first, ascending geom id, first minimum wins); rays within 1e-7 of a triangle edge dropped",
+                    torch=torch.__version__)
+        store["meta"] = np.array(json.dumps(meta))
+        path = os.path.join(out_dir, case + ".npz")
+        np.savez_compressed(path, **store)
+        print(f"{case}: {os.path.getsize(path) / 1024:.0f} KB, candidates {cand}, hit ids {np.unique(hits).tolist()}, misses {int(np.sum(hits < 0))}")
+    geom_table(ref, out_dir)
+
+
+def one_ray(ref, m64, x64, p, v, cand, filters, be_prim, gtype, lite):
+    """(dist, geomid, runner-up distance) of one ray, or None when its mesh hit lies on a triangle edge."""
+    flg_static, _, geomgroup = filters
+    pt, vt = torch.tensor(p), torch.tensor(v)
+    dist, gid = ref.ray.ray(m64, x64, pt, vt, geomgroup=geomgroup, flg_static=flg_static, bodyexclude=be_prim)
+    if isinstance(dist, torch.Tensor) and dist.dtype == torch.long:  # the reference's no-candidate return is (id, dist)
+        dist, gid = gid, dist
+    best, bid = float(dist), int(gid)
+    best = np.inf if bid < 0 else best
+    per = {}
+    for g in cand:  # every candidate's own distance: the reference's single-geom functions in its local frame
+        R = x64.geom_xmat[g]
+        lp, lv = R.T @ (pt - x64.geom_xpos[g]), R.T @ vt
+        if gtype[g] == MESH:
+            x, edge = mesh_dist(ref, lite, g, lp, lv)
+            if edge < EDGE_TOL:
+                return None
+            per[g] = x
+            if x < best:
+                best, bid = x, g
+        else:
+            per[g] = float(ref.ray.ray_geom(m64.geom_size[g], lp, lv, int(gtype[g])))
+    if bid >= 0 and gtype[bid] != MESH:
+        assert abs(per[bid] - best) <= 1e-12 * max(1.0, abs(best)), (per[bid], best)
+    others = [x for g, x in per.items() if g != bid]
+    runner = min(others) if others else np.inf
+    return (best if bid >= 0 else -1.0), bid, (runner if np.isfinite(runner) else -1.0)
+
+
+def mesh_dist(ref, lite, g, lp, lv):
+    """Nearest triangle hit of mesh geom g (reference _ray_triangle), and the barycentric distance of that hit from an edge."""
+    mid = int(lite.geom_dataid[g])
+    fa, fn, va = int(lite.mesh_faceadr[mid]), int(lite.mesh_facenum[mid]), int(lite.mesh_vertadr[mid])
+    vert = np.asarray(lite.mesh_vert, dtype=np.float32).astype(np.float64)[np.asarray(lite.mesh_face)[fa : fa + fn] + va]
+    b, c = ref.math.orthogonals(ref.math.normalize(lv))
+    basis = torch.stack([b, c]).T
+    best, edge = np.inf, np.inf
+    for t in range(fn):
+        vt = torch.tensor(vert[t])
+        x = float(ref.ray._ray_triangle(vt, lp, lv, basis))
+        if x < best:
+            best = x
+            pl = ((vt - lp) @ basis).numpy()
+            A, rhs = pl[0:2] - pl[2], -pl[2]
+            det = A[0, 0] * A[1, 1] - A[1, 0] * A[0, 1]
+            t0 = (A[1, 1] * rhs[0] - A[1, 0] * rhs[1]) / det
+            t1 = (-A[0, 1] * rhs[0] + A[0, 0] * rhs[1]) / det
+            edge = min(t0, t1, 1 - t0 - t1)
+    return best, (edge if np.isfinite(best) else np.inf)
+
+
+def geom_table(ref, out_dir):
+    """Single-primitive cases against the reference ray.ray_geom: every primitive type, random sizes and rays in its frame."""
+    rng = np.random.RandomState(77)
+    S, P, V, T, D = [], [], [], [], []
+    for t in (0, 2, 3, 4, 5, 6):
+        for i in range(24):
+            size = rng.uniform(0.1, 1.0, 3) if t else np.r_[rng.uniform(0.5, 3.0, 2) * (i % 3 != 0), 0.1]
+            p = rng.uniform(-2, 2, 3) * (0.2 if i % 6 == 5 else 1.0)
+            v = rng.randn(3) if i % 4 else -p + 0.1 * rng.randn(3)
+            S.append(size); P.append(p); V.append(v); T.append(t)
+            D.append(float(ref.ray.ray_geom(torch.tensor(size), torch.tensor(p), torch.tensor(v), t)))
+    np.savez_compressed(os.path.join(out_dir, "ray_geom.npz"), size=np.array(S), pnt=np.array(P), vec=np.array(V), type=np.array(T),
+                        dist=np.array(D), meta=np.array(json.dumps(dict(reference="ray.ray_geom, float64", torch=torch.__version__))))
+    print(f"ray_geom: {len(D)} cases, {int(np.sum(np.isinf(D)))} misses")
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:] or None)
