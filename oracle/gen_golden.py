@@ -139,6 +139,16 @@ CASES = {
     "humanoid_cg_fixed_f64": ("humanoid", {"solver": 1}, "float64", 3, 3, "bench", True),
     "ant_newton_fixed_f64": ("ant", {}, "float64", 2, 2, "bench_ctrl", True),
     "ant_rk4_newton_ell_fixed_f32": ("ant", {"integrator": 1, "solver": 2, "cone": 1, "iterations": 8, "ls_iterations": 6}, "float32", 2, 2, "bench_ctrl", True),
+    # dense models past 64 dofs (multi-word dof masks, the general constraint kernel, the in-LDS Cholesky with several rows per lane, the
+    # solver reading qM from global memory): centipede (72 dofs) and the largest members of tools/gen_big_models.py's family that build
+    # in float64 (83 dofs) and in float32 (121 dofs) with the Hessian images in the solver arena; legs bent through the floor and past their joint limits
+    "centipede_f64": ("centipede", {}, "float64", 2, 2, "centipede"),
+    "centipede_83_f64": ("centipede_83", {}, "float64", 2, 2, "centipede"),
+    "centipede_121_f32": ("centipede_121", {}, "float32", 2, 2, "centipede"),
+    # ... Newton in float32 (the reference's own Newton needs nv < 100: solver.py keeps no dense M past that and fails), and the first
+    # model with three 64-bit mask words (129 dofs, dof 128 alone on word 2: CG without eulerdamp, the only solver setting that fits it)
+    "centipede_84_newton_f32": ("centipede_84", {}, "float32", 2, 2, "centipede"),
+    "centipede_129_f32": ("centipede_129", {}, "float32", 2, 2, "centipede"),
 }
 
 INPUT_LEAVES = ["time", "qpos", "qvel", "act", "qacc_warmstart", "ctrl", "qfrc_applied", "xfrc_applied", "qacc", "subtree_com", "mocap_pos", "mocap_quat"]
@@ -239,6 +249,10 @@ def make_inputs(recipe, lite, env):
         out["ctrl"] = np.clip(0.5 * rng.randn(nu), -1, 1)
         out["mocap_pos"] = lite.body_pos[lite.body_mocapid >= 0] + 0.1 * rng.randn(lite.nmocap, 3)
         out["mocap_quat"] = lite.body_quat[lite.body_mocapid >= 0] + 0.2 * rng.randn(lite.nmocap, 4)
+    elif recipe == "centipede":  # every joint bent (tips through the floor, limited joints past their ranges), velocities, controls
+        out["qpos"] = lite.qpos0 + 0.5 * rng.randn(nq)
+        out["qvel"] = 0.5 * rng.randn(nv)
+        out["ctrl"] = np.clip(0.5 * rng.randn(nu), -1, 1)
     elif recipe == "generic":  # any model: jittered qpos (env 0 keeps qpos0), velocities, clipped controls
         out["qpos"] = lite.qpos0 + 0.05 * rng.randn(nq) * (env > 0)
         out["qvel"] = 0.3 * rng.randn(nv)

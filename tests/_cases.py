@@ -67,6 +67,21 @@ SEEDED_CASES = [
     ("capsules_topk", {"solver": 1, "iterations": 100, "ls_iterations": 50}, F64, 33, dict(tol_sol=1e-5)),  # ... through the register solver (CG stall accuracy)
     ("centipede", {}, F64, 24, dict(max_alt=0.0)),                                # 72 dofs / 74 bodies (jacobian=dense): multi-word dof masks, more dofs than lanes in the LDS solver
     ("centipede", {"integrator": 1}, F32, 17, dict(tol_sol=6e-5)),                # measured 5.5e-6
+    # the largest members of tools/gen_big_models.py's family that build with the Hessian images in the solver arena (Newton, or CG with eulerdamp;
+    # tests/test_big_models.py pins the envelope and the paths they take): 83 dofs in float64 and 121 in float32 (the solver arena within 1 KB of 160 KiB, qM read from global memory, a chunk of 16 / 24 rows in the
+    # inverse tail), and 84 dofs -- refused in float64 -- in float32 with RK4
+    ("centipede_83", {}, F64, 9, dict(max_alt=0.0)),                              # Newton (measured 1.3e-14)
+    # CG: stall accuracy (see above): measured 3.6e-7 in the max norm, 2.3e-5 on the element-wise check of the state leaves (qpos / qvel / qacc); Newton one line up: 1.3e-14
+    ("centipede_83", {"solver": 1}, F64, 9, dict(tol_sol=1e-4)),
+    ("centipede_121", {}, F32, 7, dict(tol_sol=2e-2)),                            # float32 CG stall (measured 1.8e-3, the humanoid's float32 CG case above: 2.2e-3)
+    ("centipede_121", {"solver": 2}, F32, 7, dict(tol_sol=8e-5)),                 # measured 7.8e-6
+    ("centipede_84", {"integrator": 1}, F32, 5, dict(tol_sol=5e-5)),              # measured 4.7e-6
+    # CG without eulerdamp (no Hessian images in the solver arena): the crb arena binds, at 106 dofs in float64 and 154 in float32; 128 / 129 dofs
+    # straddle the 2 -> 3 mask-word boundary (dof 128 alone on word 2), 154 runs three rows per lane in the LDS Cholesky
+    ("centipede_106", {}, F64, 7, dict(max_alt=0.0)),                             # measured 1.2e-14
+    ("centipede_128", {}, F32, 5, dict(tol_sol=1.5e-2)),                          # float32 CG stall, as centipede_121 above (measured 1.4e-3)
+    ("centipede_129", {}, F32, 5, dict(tol_sol=2e-2)),                            # ... (measured 1.8e-3)
+    ("centipede_154", {}, F32, 5, dict(tol_sol=1.5e-2)),                          # ... (measured 1.35e-3)
     ("muscle_arm", {}, F64, 64, dict(max_alt=0.0)),                               # muscle actuators: activation dynamics, force-length-velocity gain, passive bias
     ("muscle_arm", {"integrator": 1}, F32, 33, dict(tol_sol=2e-5)),              # measured 2.0e-6
     ("tendon_friction", {}, F64, 64, dict(max_alt=0.0)),                         # tendon + dof frictionloss rows, Newton
@@ -119,7 +134,7 @@ def seeded_batch(xml, overrides, dtype, B):
     if xml == "muscle_arm":  # activations and controls across (and beyond) [0, 1], joint angles and speeds across the force-length-velocity curves
         d = d.replace(qpos=d.qpos + torch.tensor(np.array([0.6, 0.9]) * rng.randn(B, mx.nq)), qvel=torch.tensor(3.0 * rng.randn(B, mx.nv)),
                       ctrl=torch.tensor(rng.uniform(-0.3, 1.3, (B, mx.nu))), act=torch.tensor(rng.uniform(-0.1, 1.1, (B, mx.na))))
-    if xml == "centipede":  # bend the legs so that tips reach the floor and limited joints pass their ranges
+    if xml.startswith("centipede"):  # bend the legs so that tips reach the floor and limited joints pass their ranges
         d = d.replace(qpos=d.qpos + torch.tensor(0.5 * rng.randn(B, mx.nq)), qvel=torch.tensor(0.5 * rng.randn(B, mx.nv)))
     if xml == "sensor_rig":  # move and spin the rover so every sensor reads something different per environment
         q = d.qpos.clone()

@@ -24,8 +24,11 @@ TRAJECTORY_CASES = sorted(f[5:-4] for f in os.listdir(GOLD) if f.endswith(".npz"
 
 # solver-output tolerance of goldens whose solve is ill-conditioned enough to amplify summation-order rounding beyond the default:
 # CG (100 iterations) on the stiff always-active equality rows of a closed loop -- the pre-solver leaves of these cases agree
-# at the default tolerance
-CASE_TOL_SOL = {"equality_loops_cg_f64": 1e-5}
+# at the default tolerance.  Float32 CG on the 121-dof centipede_121 stalls where float32 rounding of its 50 iterations leaves it: the oracle
+# and the reference's own float32 step end 1.7e-3 / 5.2e-3 apart on one of the two environments (2.6e-6 on the other; pre-solver leaves
+# 7.8e-6), the float32 CG stall accuracy the humanoid's seeded float32
+# CG case also states (tests/_cases.py).  Float32 at the default bound: centipede_84_newton_f32 (Newton) and centipede_129_f32 (CG, converged).
+CASE_TOL_SOL = {"equality_loops_cg_f64": 1e-5, "centipede_121_f32": 2e-2}
 
 
 _MODEL_RECIPE = {}  # tables uid -> (xml, overrides, keep_sensors) of the models load_model built: the float64 twin of a float32 model

@@ -273,3 +273,44 @@ print("ran")
     for case in res["one"]:
         for n, t in res["one"][case].items():
             assert torch.equal(t, res["cut"][case][n]) or (t.is_floating_point() and torch.equal(torch.nan_to_num(t), torch.nan_to_num(res["cut"][case][n]))), (case, n)
+
+
+LARGE_INV = [("centipede_83", torch.float64, False), ("centipede_83", torch.float64, True), ("centipede_121", torch.float32, False), ("centipede_121", torch.float32, True),
+             ("centipede_106", torch.float64, False), ("centipede_154", torch.float32, False)]
+
+
+@pytest.mark.parametrize("xml,dtype,discrete", LARGE_INV, ids=[f"{x[10:]}-{str(t)[6:]}-{'discrete' if dc else 'continuous'}" for x, t, dc in LARGE_INV])
+def test_large_models_against_the_oracle_and_the_tail_formulas(xml, dtype, discrete, oracle_lib):
+    """The largest dense models that build (tests/test_big_models.py): 64 lanes per environment and an LDS chunk of far fewer rows than nv
+    (16 of 83 and 12 of 106 in float64, 24 of 121 and 18 of 154 in float32).  The forward prefix (stages 0x1F) against the oracle; efc_force,
+    qfrc_constraint and qfrc_inverse against inverse.py's formulas in float64 on the kernel's own leaves, with and without the discrete re-solve
+    (Euler, eulerdamp on, damped joints: the two largest models disable eulerdamp, the discrete case runs on their eulerdamp twins)."""
+    import pyoracle
+
+    mx = load_model(xml, {"enableflags": INVDISCRETE} if discrete else {}, dtype)
+    assert int(mx.opt.integrator) == 0 and float(mx.dof_damping.abs().min()) > 0
+    assert not discrete or not (int(mx.opt.disableflags) & (1 << 15))
+    B = 5
+    rng = np.random.RandomState(7)
+    d = mt.make_data(mx).expand(B).clone().replace(
+        qpos=torch.tensor(mx.qpos0.cpu().numpy() + 0.5 * rng.randn(B, mx.nq)), qvel=torch.tensor(0.5 * rng.randn(B, mx.nv)),
+        qacc=torch.tensor(5.0 * rng.randn(B, mx.nv)), ctrl=torch.tensor(np.clip(0.5 * rng.randn(B, mx.nu), -1, 1)))
+    d = d.to(dtype)
+    out = mt.inverse(mx.to("cuda"), d.to("cuda"))
+    written = _inverse_names(mx) + ["qfrc_inverse"]
+    tol = TOL_PRE[dtype]
+    ne, nf, nl = mx.constraint_sizes_py[:3]
+    active = 0
+    for e in range(B):
+        got = {n: _leaf(out, n)[e].cpu().numpy() for n in written}
+        hint = {k: got[k] for k in ("contact_dist", "contact_pos", "contact_frame")}
+        o = pyoracle.run(mx, d[e], step=False, stages=0x1F, contact_hint=hint)
+        pre = [n for n in written if n not in TAIL and n not in INT_LEAVES and n != "sensordata"]
+        worst = max(rel_err(got[n], o[n]) for n in pre)
+        assert worst <= tol, (xml, e, worst, max(pre, key=lambda n: rel_err(got[n], o[n])))
+        tail = _tail_of(mx, got, d[e].qacc.cpu().numpy(), discrete)
+        for n in TAIL:
+            err = _err(n, got[n], tail[n], got["efc_force"])
+            assert err <= tol, (xml, e, n, err)
+        active += int(np.count_nonzero(got["efc_force"][ne + nf + nl:]))
+    assert active > 0  # contact rows take part
