@@ -54,6 +54,30 @@ extern "C" {
 #define MJH_STAGE_SOLVE 0x040      /* solver.solve                       solver.py:244-553  */
 #define MJH_STAGE_ALL 0x07f
 
+/* kernel ids: the kernels a call launches, as mjh_debug_phase_times() reports them and mjh_model_kernel_io() accounts for them */
+#define MJH_KERNEL_KIN 0         /* kinematics + com_pos                                                              */
+#define MJH_KERNEL_CRB 1         /* crb + factor_m                                                                    */
+#define MJH_KERNEL_CON 2         /* collision + constraint rows                                                       */
+#define MJH_KERNEL_VEL 3         /* transmission, velocity, passive, rne, actuation                                   */
+#define MJH_KERNEL_SOL 4         /* solve + integrator                                                                */
+#define MJH_KERNEL_VEL_OPT 5     /* MJH_KERNEL_VEL with fluid forces, gravity compensation, tendons or nv > 64         */
+#define MJH_KERNEL_SOL_GEN 6     /* MJH_KERNEL_SOL with frictionloss / equality / dense limit rows                     */
+#define MJH_KERNEL_CON_GEN 7     /* MJH_KERNEL_CON with those rows, max_contact_points or nv > 64                      */
+#define MJH_KERNEL_CON_DIRECT 8  /* MJH_KERNEL_CON of small models: contact rows straight to the leaf                  */
+#define MJH_KERNEL_SOL2 9        /* the solver phase as the register solver (two or four environments per wavefront)   */
+#define MJH_KERNEL_CONVEX 10     /* convex narrow phase                                                               */
+#define MJH_KERNEL_SENSOR 11     /* sensors                                                                           */
+#define MJH_KERNEL_KV 12         /* kinematics + velocity as one kernel: then 0 and 3 do not appear                   */
+#define MJH_KERNEL_KCV 13        /* kinematics + crb / factor + velocity as one kernel: then 12 and 1 do not appear    */
+#define MJH_KERNEL_CS 14         /* constraint stage + register solver + integrator as one kernel                     */
+/* 15 is unassigned */
+#define MJH_KERNEL_PASS 16       /* the whole pass as one kernel (humanoid-class models)                              */
+#define MJH_KERNEL_KCV2 17       /* MJH_KERNEL_KCV on two wavefronts per workgroup                                    */
+#define MJH_KERNEL_STAGE 18      /* one RK4 stage of a small Newton model as one kernel                               */
+#define MJH_KERNEL_TAIL 19       /* that kernel running the constraint phase + the solver's first tier only           */
+#define MJH_KERNEL_INVERSE 20    /* the inverse-dynamics tail of mjh_inverse                                          */
+#define MJH_KERNEL_RAY 21        /* the ray kernel of mjh_ray                                                         */
+
 /* pair-function ids of the static collision table (collision_driver.py:106-125) */
 #define MJH_FN_PLANE_SPHERE 0
 #define MJH_FN_PLANE_CAPSULE 1
@@ -425,19 +449,15 @@ int mjh_model_leaf_counts(const mjhModel* m, int64_t* counts, int max);
 int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsigned char* mask, const void* qpos_rows,
                     const void* qvel_rows, int64_t B, void* hip_stream);
 
-/* bytes of dynamic LDS one environment occupies in pipeline phase `phase` (0..4: kinematics, crb/factor,
- * collision/constraint, velocity/acceleration, solve/integrate); the number of phases is 5. */
-int mjh_model_lds_bytes(const mjhModel* m, int phase);
+/* bytes of dynamic LDS one environment occupies in arena `arena`: 0..4 the pipeline phases (kinematics, crb/factor,
+ * collision/constraint, velocity/acceleration, solve/integrate), 5 the register solver, 16 its first tier, 17 the fused
+ * kinematics + crb + velocity kernel (MJH_KERNEL_KCV), 18 the fused constraint + solver kernel (MJH_KERNEL_CS), 19 the
+ * two-wave form of MJH_KERNEL_KCV (MJH_KERNEL_KCV2).  0 for any other number. */
+int mjh_model_lds_bytes(const mjhModel* m, int arena);
 
 /* measurement aid used by bench.py for the per-kernel roofline: while enabled, every kernel launch of mjh_step / mjh_forward is
  * bracketed by HIP events on the launch stream (mjh_inverse and mjh_ray too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
- * the elapsed milliseconds and the kernel id (0..4 pipeline phases, 5 velocity phase with fluid / gravcomp / tendons, 6 solver phase
- * with frictionloss / equality / dense limit rows, 7 constraint phase with those rows or max_contact_points, 8 constraint phase of small
- * models (contact rows straight to the leaf), 9 solver phase as the register solver (mjh_sol2_kernel: two environments per wavefront),
- * 10 convex narrow phase, 11 sensors, 12 kinematics + velocity phases as one kernel -- then 0 and 3 do not appear --, 13 kinematics + crb / factor + velocity as one kernel
- * (models whose crb stage packs like the other two), then 12 and 1 do not appear; 14 constraint stage + register solver + integrator as one kernel, 16 the whole pass as
- * one kernel (humanoid-class models), 17 kernel 13 on two wavefronts per workgroup, 18 one RK4 stage of a small Newton model as one kernel, 19 that kernel running the
- * constraint phase + first solver tier only, 20 the inverse-dynamics tail of mjh_inverse, 21 the ray kernel of mjh_ray; 15 is unassigned).  Returns the number of launches (<= max) or a negative code. */
+ * the elapsed milliseconds and the kernel id (MJH_KERNEL_*).  Returns the number of launches (<= max) or a negative code. */
 int mjh_debug_phase_timing(int enable);
 int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
 
@@ -445,7 +465,7 @@ int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
  * them off.  The shipped library is built without MJH_STAMPS: the pointer is stored and nothing reads it. */
 void mjh_debug_set_stamps(void* dev_ptr);
 
-/* global-memory bytes ONE launch of kernel `kernel` (ids as above) reads and writes per environment in a step (20: in an mjh_inverse call): the library's own
+/* global-memory bytes ONE launch of kernel `kernel` (MJH_KERNEL_*) reads and writes per environment in a step (MJH_KERNEL_INVERSE: in an mjh_inverse call): the library's own
  * account of its loads / stores through the Data leaves (csrc/mjh_io.h) -- the per-kernel "algorithmic bytes" of the roofline.
  * read_write_bytes[0] = read, [1] = written.  RK4 models: the mean over the four stage launches of a step (stages 1..3 write a private
  * workspace holding only the leaves a later phase reads).  Returns 0, or -2 when this model's step does not launch that kernel. */

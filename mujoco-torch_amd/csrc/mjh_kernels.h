@@ -4887,52 +4887,89 @@ struct Env {
 #undef STAMP
 #undef STAMP0
 
+// Occupancy defaults (waves per SIMD), one per measured case of sol2_waves / phase_waves below.  `build.sh -DMJH_..._WAVES=n` overrides one.
 #ifndef MJH_CRB32P_WAVES
-#define MJH_CRB32P_WAVES 4  /* packed float32 CRB (two / four environments per wavefront): at four waves per SIMD the ant runs it in 27.1 us (three: 32.2), the mesh scene in 23.0 (20.7) */
+#define MJH_CRB32P_WAVES 4
 #endif
 #ifndef MJH_SOL2_T1_WAVES
-#define MJH_SOL2_T1_WAVES 4  /* float32 register solver, NMAX = 8, one row slot per lane (the ant's first tier): 128 VGPRs + 80 B of scratch at four waves per SIMD, 94 us; 164 VGPRs at three: 100.7 us */
+#define MJH_SOL2_T1_WAVES 4
 #endif
 #ifndef MJH_SOL2_W16_WAVES
-#define MJH_SOL2_W16_WAVES 4  /* ... the same tier at four environments per wavefront */
+#define MJH_SOL2_W16_WAVES 4
 #endif
 #ifndef MJH_CON32D_WAVES
-#define MJH_CON32D_WAVES 4  /* float32 small-model constraint phase */
+#define MJH_CON32D_WAVES 4
 #endif
 #ifndef MJH_SOL32_WAVES
-#define MJH_SOL32_WAVES 3  /* float32 LDS solver: 168 VGPRs + ~96 B of scratch; measured on the mesh scene: 2 waves (173 VGPRs, no scratch) 374 us, 3 waves 338 us, 4 waves (128 + 156 B) 362 us */
+#define MJH_SOL32_WAVES 3
 #endif
 #ifndef MJH_KV32_WAVES
-#define MJH_KV32_WAVES 2  /* float32 fused kinematics + velocity kernel, packed: a lower bound -- the kernel needs ~122 VGPRs since the stage functions stopped sharing hoisted address arithmetic (round 2: 256) and runs four waves per SIMD: the ant's B = 16384 is one round.  Requesting the caller's cold ctrl / applied-force rows at the kernel's head instead of at their use: 129 VGPRs, humanoid -0.7 us, ant +2.4 us: not kept */
+#define MJH_KV32_WAVES 2
 #endif
 #ifndef MJH_KCV32_WAVES
-#define MJH_KCV32_WAVES 4  /* round 5: 137 VGPRs once the crb stage of the four-per-wavefront instantiation stopped compiling the 24 / 28 / 32-row register Cholesky variants it can never run (nv <= 16): 128 + 24 B at four waves per SIMD.  Rounds 1 - 4, when those variants set the allocation: float32 fused kinematics + crb + velocity kernel, packed: 173 VGPRs; at three waves per SIMD (168 + 20 B of scratch) the ant ran it in 99.7 us instead of 95.7, at four (128 + 112 B) in 104.5 */
+#define MJH_KCV32_WAVES 4
 #endif
 #ifndef MJH_KCV2_WAVES
-#define MJH_KCV2_WAVES 4  /* two-wave kernel 13 of packed float32 models: two workgroups of two waves per SIMD pair -- the point of the kernel is to be at four waves per SIMD where kernel 13 (169 VGPRs) sits at two */
+#define MJH_KCV2_WAVES 4
 #endif
 #ifndef MJH_CON64_WAVES
-#define MJH_CON64_WAVES 4  /* float64 plain constraint phase: 128 VGPRs + ~108 B of scratch buys the fourth wave per SIMD (16 environments per CU) */
+#define MJH_CON64_WAVES 4
 #endif
+#ifndef MJH_SOL2_F64_WAVES
+#define MJH_SOL2_F64_WAVES 1
+#endif
+
+// ---- the register solver's forms: the WT argument of mjh_sol2_kernel (its value is part of the kernel's name) --------------------------------------------------------------
+enum : int { SOL2_QUAD = 16, SOL2_QUAD_NEWTON = 17, SOL2_STAGE = 18, SOL2_PAIR = 32, SOL2_CS = 33, SOL2_PASS = 34, SOL2_CS_ONE = 35, SOL2_PASS_ONE = 36 };
+struct Sol2Form { int lanes; bool newton_only, stage, cs, pass, one; };  // lanes per environment; Newton-only code (no CG state); one RK4 stage; constraint stage / whole pass in front of the solve; one solver iteration
+constexpr Sol2Form sol2_form(int wt) {
+  if (wt == SOL2_PAIR) return {32, false, false, false, false, false};  // two environments per wavefront; an odd last environment leaves the second half of its wave idle
+  if (wt == SOL2_QUAD) return {16, false, false, false, false, false};  // four per wavefront (nv <= 16)
+  if (wt == SOL2_QUAD_NEWTON) return {16, true, false, false, false, false};  // ... Newton models: 128 VGPRs + 116 B of scratch instead of + 160 B for the ant's first tier, 227 instead of 243 VGPRs for the mesh scene's; ant 53.6 -> 52.2 us per launch, mesh scene 223.7 -> 219.1 us
+  if (wt == SOL2_STAGE) return {16, true, true, false, false, false};  // one RK4 stage of a small Newton model in ONE launch -- kernel 13's stages, the constraint phase and the solver's first tier behind one another (round 6)
+  if (wt == SOL2_CS) return {32, false, false, true, false, false};  // two per wavefront, the constraint stage in front of the solve (Env::run_con_sol2)
+  if (wt == SOL2_PASS) return {32, false, false, true, true, false};  // ... and kinematics + crb / factor + velocity in front of that: the whole forward pass + integrator of an environment in one kernel
+  if (wt == SOL2_CS_ONE) return {32, false, false, true, false, true};  // SOL2_CS for opt.iterations == 1 (the humanoid benchmark, solver.py:534-535): the solver loop's body is straight-line code -- the factor of M is dead behind the one preconditioning step instead of crossing the line search in 56 VGPRs
+  if (wt == SOL2_PASS_ONE) return {32, false, false, true, true, true};  // SOL2_PASS for opt.iterations == 1, as SOL2_CS_ONE is to SOL2_CS
+  return {0, false, false, false, false, false};
+}
+
 // Occupancy bounds (second launch-bound argument = waves per SIMD the allocator must fit): float64 kernels are left alone --
 // capping them at 128 VGPRs was measured 3-11 % slower than ~180-230 VGPRs at 2 waves/SIMD, their spills are twice as wide
 // (profiles/r01/notes.md).  The float32 solver, packed kinematics / velocity and CRB kernels sit just above an occupancy
 // step (197 / 181 / 185 -> 168 VGPRs = 3 waves, 132 -> 128 = 4 waves) and spill only 5-24 dwords to get under it; with
 // 32-64 environments per CU (ant B = 16384, mesh B = 8192) the extra wave in flight is worth +13 % / +12 % end to end.
-// The register solver's kernel: two environments per wavefront; an odd last environment leaves the second half of its wave idle.
-// WT: lanes per environment (32 or 16); WT = 17 is the four-per-wavefront kernel of NEWTON models (16 lanes, Newton-only code: 128 VGPRs + 116 B of scratch instead of + 160 B
-// for the ant's first tier, 227 instead of 243 VGPRs for the mesh scene's; ant 53.6 -> 52.2 us per launch, mesh scene 223.7 -> 219.1 us)
-#ifndef MJH_SOL2_F64_WAVES
-#define MJH_SOL2_F64_WAVES 1  /* float64 instantiations for <= 16 dofs (the twins of configs 3 / 5): at two waves per SIMD they spilled 80 - 600 B per lane to scratch memory; at ONE the unified register file holds the overflow in AGPRs (24 - 150 of them, no scratch).  Measured (MI355X, solver phase): mesh scene float64 B = 4096 190.6 -> 186.9 us, B = 16384 501 -> 463 us; ant float64 29.3 -> 28.3 / 54.9 -> 53.8 us */
-#endif
 template <typename REAL, int NMAX, int RPL, int WT>
-__global__ void __launch_bounds__(MJH_WAVE, (sizeof(REAL) == 4 && NMAX == 8 && WT < 33 && RPL * ((WT == 17 || WT == 18) ? 16 : WT) == 32) ? (WT != 32 ? MJH_SOL2_W16_WAVES : MJH_SOL2_T1_WAVES) : ((sizeof(REAL) == 8 && NMAX <= 16) ? MJH_SOL2_F64_WAVES : 2)) mjh_sol2_kernel(KArgs<REAL> args) {
-  constexpr int W = (WT == 17 || WT == 18) ? 16 : (WT >= 33 ? 32 : WT);
-  constexpr bool NEWTON_ONLY = WT == 17 || WT == 18;
-  constexpr bool STAGE = WT == 18;  // WT = 18: one RK4 stage of a small Newton model in ONE launch -- kernel 13's stages, the constraint phase and the solver's first tier behind one another (round 6)
-  constexpr bool ONE = WT == 35 || WT == 36;             // WT = 35: WT = 33 for models with opt.iterations == 1 (the humanoid benchmark, solver.py:534-535): the solver loop's body is straight-line code -- the factor of M is dead behind the one preconditioning step instead of crossing the line search in 56 VGPRs
-  constexpr bool CS = WT >= 33;  // WT = 33: two environments per wavefront, the constraint stage in front of the solve (Env::run_con_sol2)
-  constexpr bool ALL = WT == 34 || WT == 36;  // WT = 34 (36: its one-iteration form, as 35 is to 33): ... and kinematics + crb / factor + velocity in front of that: the whole forward pass + integrator of an environment in one kernel
+constexpr int sol2_waves() {
+  constexpr Sol2Form F = sol2_form(WT);
+  if (sizeof(REAL) == 4 && NMAX == 8 && RPL == 1 && F.lanes == 32 && !F.cs) return MJH_SOL2_T1_WAVES;  // float32 register solver, NMAX = 8, one row slot per lane (the ant's first tier): 128 VGPRs + 80 B of scratch at four waves per SIMD, 94 us; 164 VGPRs at three: 100.7 us
+  if (sizeof(REAL) == 4 && NMAX == 8 && RPL == 2 && F.lanes == 16) return MJH_SOL2_W16_WAVES;  // ... the same tier (32 rows) at four environments per wavefront
+  if (sizeof(REAL) == 8 && NMAX <= 16) return MJH_SOL2_F64_WAVES;  // float64 instantiations for <= 16 dofs (the twins of configs 3 / 5): at two waves per SIMD they spilled 80 - 600 B per lane to scratch memory; at ONE the unified register file holds the overflow in AGPRs (24 - 150 of them, no scratch).  Measured (MI355X, solver phase): mesh scene float64 B = 4096 190.6 -> 186.9 us, B = 16384 501 -> 463 us; ant float64 29.3 -> 28.3 / 54.9 -> 53.8 us
+  return 2;
+}
+template <typename REAL, int PHASE, int W>
+constexpr int phase_waves() {
+  constexpr bool F32 = sizeof(REAL) == 4, PACKED = W < MJH_WAVE;
+  if (F32 && PHASE == MJH_KERNEL_KCV2 && PACKED) return MJH_KCV2_WAVES;  // two-wave kernel 13 of packed float32 models: two workgroups of two waves per SIMD pair -- the point of the kernel is to be at four waves per SIMD where kernel 13 (169 VGPRs) sits at two
+  if (F32 && PHASE == MJH_KERNEL_CON_DIRECT) return MJH_CON32D_WAVES;  // float32 small-model constraint phase
+  if (F32 && PHASE == MJH_KERNEL_SOL) return MJH_SOL32_WAVES;  // float32 LDS solver: 168 VGPRs + ~96 B of scratch; measured on the mesh scene: 2 waves (173 VGPRs, no scratch) 374 us, 3 waves 338 us, 4 waves (128 + 156 B) 362 us
+  if (F32 && (PHASE == MJH_KERNEL_SOL_GEN || ((PHASE == MJH_KERNEL_KIN || PHASE == MJH_KERNEL_VEL) && PACKED))) return 3;
+  if (F32 && PHASE == MJH_KERNEL_KCV && PACKED) return MJH_KCV32_WAVES;  // round 5: 137 VGPRs once the crb stage of the four-per-wavefront instantiation stopped compiling the 24 / 28 / 32-row register Cholesky variants it can never run (nv <= 16): 128 + 24 B at four waves per SIMD.  Rounds 1 - 4, when those variants set the allocation: float32 fused kinematics + crb + velocity kernel, packed: 173 VGPRs; at three waves per SIMD (168 + 20 B of scratch) the ant ran it in 99.7 us instead of 95.7, at four (128 + 112 B) in 104.5
+  if (F32 && PHASE == MJH_KERNEL_KV && PACKED) return MJH_KV32_WAVES;  // float32 fused kinematics + velocity kernel, packed: a lower bound -- the kernel needs ~122 VGPRs since the stage functions stopped sharing hoisted address arithmetic (round 2: 256) and runs four waves per SIMD: the ant's B = 16384 is one round.  Requesting the caller's cold ctrl / applied-force rows at the kernel's head instead of at their use: 129 VGPRs, humanoid -0.7 us, ant +2.4 us: not kept
+  if (F32 && PHASE == MJH_KERNEL_CRB) return PACKED ? MJH_CRB32P_WAVES : 4;  // packed float32 CRB (two / four environments per wavefront): at four waves per SIMD the ant runs it in 27.1 us (three: 32.2), the mesh scene in 23.0 (20.7)
+  if (!F32 && PHASE == MJH_KERNEL_CON) return MJH_CON64_WAVES;  // float64 plain constraint phase: 128 VGPRs + ~108 B of scratch buys the fourth wave per SIMD (16 environments per CU)
+  if (!F32 && (PHASE == MJH_KERNEL_KV || PHASE == MJH_KERNEL_KCV)) return 2;
+  if (!F32 && PHASE == MJH_KERNEL_CRB && !PACKED) return 4;
+  return 1;
+}
+// threads per workgroup of a phase kernel (kernel and host): one wavefront; MJH_KERNEL_KCV2: a second one runs the crb / factor stage
+constexpr int phase_threads(int phase) { return phase == MJH_KERNEL_KCV2 ? 2 * MJH_WAVE : MJH_WAVE; }
+
+template <typename REAL, int NMAX, int RPL, int WT>
+__global__ void __launch_bounds__(MJH_WAVE, (sol2_waves<REAL, NMAX, RPL, WT>())) mjh_sol2_kernel(KArgs<REAL> args) {
+  constexpr Sol2Form F = sol2_form(WT);
+  constexpr int W = F.lanes;
+  constexpr bool NEWTON_ONLY = F.newton_only, STAGE = F.stage, CS = F.cs, ALL = F.pass, ONE = F.one;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const KArgs<REAL>& K = kargs<REAL>();
   constexpr int NSUB = MJH_WAVE / W;  // environments per wavefront: two (32 lanes each) or, for nv <= 16, four (16 lanes each)
@@ -5088,24 +5125,24 @@ __global__ void __launch_bounds__(MJH_WAVE, (sizeof(REAL) == 4 && NMAX == 8 && W
 }
 
 template <typename REAL, int PHASE, int W>
-__global__ void __launch_bounds__((PHASE == 17 ? 2 * MJH_WAVE : MJH_WAVE), ((sizeof(REAL) == 4 && PHASE == 17 && W < 64) ? MJH_KCV2_WAVES : (sizeof(REAL) == 4 && PHASE == 8) ? MJH_CON32D_WAVES : (sizeof(REAL) == 4 && PHASE == 4) ? MJH_SOL32_WAVES : (sizeof(REAL) == 4 && (PHASE == 6 || ((PHASE == 0 || PHASE == 3) && W < 64))) ? 3 : (sizeof(REAL) == 4 && PHASE == 13 && W < 64) ? MJH_KCV32_WAVES : (sizeof(REAL) == 4 && PHASE == 12 && W < 64) ? MJH_KV32_WAVES : ((sizeof(REAL) == 4 && PHASE == 1) ? (W < 64 ? MJH_CRB32P_WAVES : 4) : ((sizeof(REAL) == 8 && PHASE == 2) ? MJH_CON64_WAVES : ((sizeof(REAL) == 8 && (PHASE == 12 || PHASE == 13)) ? 2 : ((sizeof(REAL) == 8 && PHASE == 1 && W == 64) ? 4 : 1)))))) mjh_phase_kernel(KArgs<REAL> args) {
+__global__ void __launch_bounds__(phase_threads(PHASE), (phase_waves<REAL, PHASE, W>())) mjh_phase_kernel(KArgs<REAL> args) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const KArgs<REAL>& K = kargs<REAL>();
   constexpr int NSUB = MJH_WAVE / W;  // environments per wavefront: W lanes each, their own LDS arena each
-  const int sub = (W == MJH_WAVE) ? 0 : (int)((threadIdx.x & (MJH_WAVE - 1)) / W);  // (PHASE 17: two wavefronts per workgroup share the arenas of the same NSUB environments)  // folded away for a whole-wave environment: everything stays scalar
+  const int sub = (W == MJH_WAVE) ? 0 : (int)((threadIdx.x & (MJH_WAVE - 1)) / W);  // (MJH_KERNEL_KCV2: two wavefronts per workgroup share the arenas of the same NSUB environments)  // folded away for a whole-wave environment: everything stays scalar
   REAL* lds = reinterpret_cast<REAL*>(lds_raw) + sub * K.lds_reals;
   // One workgroup per NSUB environments, no grid-stride loop (the host cuts batches past 2^20 workgroups into several launches): with a loop around the body the optimiser keeps
   // whatever is loop-invariant -- addresses, kernarg-derived values of EVERY stage -- in registers across the whole body (round 5: the whole-pass kernel went 256 VGPRs + 48 B -> 153 without it)
   {
     const int64_t blk = blockIdx.x;  // env_count is a multiple of NSUB and the grid covers it exactly (host)
-    Env<REAL, W, PHASE == 6 || PHASE == 7, PHASE == 8> E(lds, K.env_begin + blk * NSUB + sub, K.flags);
-    if (PHASE == 0) E.template run_kin<false>();
-    else if (PHASE == 1) E.run_crb();
-    else if (PHASE == 2 || PHASE == 7 || PHASE == 8) E.run_con();  // 8: plain constraint phase of small models, contact rows straight to the leaf  // 7: constraint phase of models with equality / frictionloss / ball- or tendon-limit rows
-    else if (PHASE == 3) E.template run_vel<false>();
-    else if (PHASE == 5) E.template run_vel<true>();  // velocity phase of models with fluid forces (density / viscosity / wind)
-    else if (PHASE == 13) { E.template run_kin<false>(); wave_sync(); E.template crb_factor<true>(); wave_sync(); E.template run_vel<false, true>(); }  // ... and the crb / factor stage between them (small models: the three stages of one RK4 stage are one launch)
-    else if (PHASE == 17) {
+    Env<REAL, W, PHASE == MJH_KERNEL_SOL_GEN || PHASE == MJH_KERNEL_CON_GEN, PHASE == MJH_KERNEL_CON_DIRECT> E(lds, K.env_begin + blk * NSUB + sub, K.flags);
+    if (PHASE == MJH_KERNEL_KIN) E.template run_kin<false>();
+    else if (PHASE == MJH_KERNEL_CRB) E.run_crb();
+    else if (PHASE == MJH_KERNEL_CON || PHASE == MJH_KERNEL_CON_GEN || PHASE == MJH_KERNEL_CON_DIRECT) E.run_con();
+    else if (PHASE == MJH_KERNEL_VEL) E.template run_vel<false>();
+    else if (PHASE == MJH_KERNEL_VEL_OPT) E.template run_vel<true>();
+    else if (PHASE == MJH_KERNEL_KCV) { E.template run_kin<false>(); wave_sync(); E.template crb_factor<true>(); wave_sync(); E.template run_vel<false, true>(); }  // ... and the crb / factor stage between them (small models: the three stages of one RK4 stage are one launch)
+    else if (PHASE == MJH_KERNEL_KCV2) {
       // Kernel 13 on TWO wavefronts per workgroup (small float32 models): crb / factor and velocity both depend on the kinematics only (forward.py:73-99), so behind
       // the kinematics stage the first wave goes on with the velocity stage while a second one -- idle at the barrier until then -- runs crb / factor on cinert / cdof in the shared
       // arena (PH_KCV2: its own arrays are a region of their own).  The serial chain of an environment is KIN + max(VEL, CRB) instead of KIN + CRB + VEL.
@@ -5115,8 +5152,8 @@ __global__ void __launch_bounds__((PHASE == 17 ? 2 * MJH_WAVE : MJH_WAVE), ((siz
       if (role == 0) E.template run_vel<false, true>();
       else E.template crb_factor<true>();
     }
-    else if (PHASE == 12) { E.template run_kin<true>(); wave_sync(); E.template run_vel<false, true, true>(); }  // kinematics + velocity in one launch (the velocity phase needs nothing of CRB / CON)
-    else E.run_sol();                                 // 4: solver phase; 6: solver phase of models with dof-frictionloss rows
+    else if (PHASE == MJH_KERNEL_KV) { E.template run_kin<true>(); wave_sync(); E.template run_vel<false, true, true>(); }  // kinematics + velocity in one launch (the velocity phase needs nothing of CRB / CON)
+    else E.run_sol();  // MJH_KERNEL_SOL, MJH_KERNEL_SOL_GEN
     wave_sync();
   }
 }

@@ -36,6 +36,20 @@ extern template __global__ void mjh_ray_kernel<float>(RayArgs<float>);
 #undef C_
 #undef N_
 
+template <typename REAL> using Kernel = void (*)(KArgs<REAL>);
+// the register solver's instantiations (mjh_instances.h): NMAX, RPL, form (sol2_form), kernel
+template <typename REAL> struct Sol2Kernel { int nmax, rpl, wt; Kernel<REAL> fn; };
+#define NONE_(...)
+#define S_(R, N, RPL, WT) {N, RPL, WT, &mjh_sol2_kernel<R, N, RPL, WT>},
+template <typename REAL> const Sol2Kernel<REAL> kSol2Kernels[] = {MJH_INST_ALL(NONE_, S_, NONE_, NONE_, REAL)};
+#undef NONE_
+#undef S_
+template <typename REAL>
+Kernel<REAL> sol2_kernel(int nmax, int rpl, int wt) {
+  for (const Sol2Kernel<REAL>& k : kSol2Kernels<REAL>) if (k.nmax == nmax && k.rpl == rpl && k.wt == wt) return k.fn;
+  return nullptr;
+}
+
 static thread_local std::string g_err;
 static unsigned long long* g_stamps = nullptr;  // diagnostic builds only (mjh_debug_set_stamps)
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
@@ -45,7 +59,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 static struct {
   bool on = false;
   int n = 0;                          // launches recorded by the last call
-  int id[MJH_TIMING_MAX];             // 0..8 phase-kernel ids, 9 register solver, 10 convex narrow phase, 11 sensors, 12 / 13 / 17 fused kinematics (+ crb) + velocity, 14 fused constraint + register solver, 16 whole pass, 18 / 19 stage kernel, 20 inverse-dynamics tail, 21 ray kernel (15: unassigned)
+  int id[MJH_TIMING_MAX];             // MJH_KERNEL_* (include/mjhip.h)
   hipEvent_t ev[MJH_TIMING_MAX + 1];  // ev[i] .. ev[i + 1] brackets launch i
 } g_timing;
 static inline void timing_begin(hipStream_t s) { if (g_timing.on) { g_timing.n = 0; (void)hipEventRecord(g_timing.ev[0], s); } }
@@ -58,42 +72,41 @@ static inline void timing_mark(hipStream_t s, int id) {
     if (e_ != hipSuccess) return fail(-5, std::string(#x) + ": " + hipGetErrorString(e_));                 \
   } while (0)
 
+// The LDS arenas of a model: the five pipeline phases and the register solver (carved as lds_carve(M, 1 << arena)), then those of the fused kernels and of the
+// register solver's first tier.
+enum Arena { AR_KIN, AR_CRB, AR_CON, AR_VEL, AR_SOL, AR_SOL2, AR_KV, AR_KCV, AR_KCV2, AR_TIER, AR_CS, AR_COUNT };
+static_assert(AR_SOL2 + 1 == MJH_NARENA, "the arenas carved per model come first");
+struct ArenaLds {
+  LdsOff off;  // offsets of the arena's arrays
+  int bytes;   // ... and its size per environment
+};
+
 struct mjhModel {
   int dtype;
   void* blob;          // device allocation holding every table
   size_t blob_bytes;
-  LdsOff off[MJH_NARENA];
-  int lds_bytes[MJH_NARENA];
+  ArenaLds arena[AR_COUNT] = {};
+  int lds(Arena a) const { return arena[a].bytes; }
+  int pack2[AR_COUNT] = {};                // the phase kernels on an arena (phase_kernel) run two environments per wavefront
+  int pack4[AR_COUNT] = {};                // ... or four (16 lanes each): small models only
   int sol2_nmax = 0, sol2_rpl = 0;         // register solver (mjh_sol2_kernel) instantiation serving this model, 0 = not eligible
-  int fuse_kv = 0;                         // kinematics + velocity phases run as ONE kernel (12) from an arena of their own
-  LdsOff off_kv;
-  int lds_kv = 0;
-  int fuse_kcv = 0;                        // ... and the crb / factor stage between them: ONE kernel (13) for the three (models whose crb stage packs like the other two)
-  LdsOff off_kcv;
-  int lds_kcv = 0;
-  LdsOff off_kcv2;                         // ... and of its two-wave form (mjh_phase_kernel<.., 17, W>, timing id 17: PH_KCV2)
-  int lds_kcv2 = 0;
-  int kcv2 = 0;                            // a step launches the two-wave form instead of kernel 13 ...
+  int fuse_kv = 0;                         // kinematics + velocity phases run as ONE kernel (MJH_KERNEL_KV) from an arena of their own
+  int fuse_kcv = 0;                        // ... and the crb / factor stage between them: ONE kernel (MJH_KERNEL_KCV) for the three (models whose crb stage packs like the other two)
+  int kcv2 = 0;                            // a step launches the two-wave form (MJH_KERNEL_KCV2) instead of MJH_KERNEL_KCV ...
   int64_t kcv2_max_envs = 0;               // ... forced on (MJH_KCV2=1): any batch; otherwise 0 and the limit is kcv2_limit() of the LAUNCH's device
   int kcv2_per_wg = 0, kcv2_envs_per_wg = 0; // arena bytes and environments of one of its workgroups
   int sol2_tiers = 0;                      // 1: a first launch with ONE row slot per lane serves the environments whose active contacts fit 32 dense rows
   int sol2_w16_rpl = 0;                    // > 0: that first launch runs FOUR environments per wavefront (16 lanes each, nv <= 16) with this many row slots per lane
-  int sol2_w16_nmax = 0;                   // ... instantiated for 8, 12 or 16 dofs
-  LdsOff off_tier;                         // ... from an arena of its own (32 rows of efc_J instead of all of them)
-  int lds_tier = 0;
-  int fuse_all = 0;                        // ... and the whole pass as ONE kernel (mjh_sol2_kernel<.., 34>, timing id 16): kernel 13's stages in front of kernel 14's, one arena of max(lds_kcv, lds_cs)
+  int sol2_w16_nmax = 0;                   // ... instantiated for 8, 12 or 16 dofs; the first tier runs from an arena of its own (AR_TIER: 32 rows of efc_J instead of all of them)
+  int fuse_all = 0;                        // ... and the whole pass as ONE kernel (SOL2_PASS, MJH_KERNEL_PASS): kernel 13's stages in front of kernel 14's, one arena of max(AR_KCV, AR_CS)
   int lds_all = 0;
   int inv_lanes = 0, inv_envs = 0, inv_chunk = 0, inv_lds_env = 0;  // inverse-dynamics tail (mjh_inverse_kernel): lanes per environment, environments per workgroup, rows per LDS chunk, REALs per environment
   int any_damping = 0;                     // some dof_damping != 0 (discrete_acc's eulerdamp re-solve applies)
-  int fuse_stage = 0;                      // every RK4 stage of a small Newton model runs as ONE launch (mjh_sol2_kernel<.., 18>, timing id 18; stage 0 too unless MJH_FUSE_STAGE0=0): kernel 13's stages, the constraint phase (kernel 8) and the register solver's first tier
+  int fuse_stage = 0;                      // every RK4 stage of a small Newton model runs as ONE launch (SOL2_STAGE, MJH_KERNEL_STAGE; stage 0 too unless MJH_FUSE_STAGE0=0): kernel 13's stages, the constraint phase (kernel 8) and the register solver's first tier
   int lds_stage = 0;                       // ... dynamic LDS of one of its four-environment workgroups
   int fuse_tail = 0;                       // the tail of a pass -- constraint phase + the solver's first tier + integrator -- as ONE launch of the same kernel (parts 2 | 4): small Newton models whose pass cannot be one launch (convex narrow phase or sensors between the parts, Euler)
   int lds_tail = 0;
-  int fuse_cs = 0;                         // constraint stage + register solver + integrator run as ONE kernel (mjh_sol2_kernel<.., 33>, timing id 14) from an arena of its own
-  LdsOff off_cs;
-  int lds_cs = 0;
-  int pack2[MJH_NPHASE];                   // phase runs two environments per wavefront
-  int pack4[MJH_NPHASE];                   // ... or four (16 lanes each): small models only
+  int fuse_cs = 0;                         // constraint stage + register solver + integrator run as ONE kernel (SOL2_CS, MJH_KERNEL_CS) from an arena of its own
   int cvx_lds_bytes;                       // LDS scratch of one (environment, convex pair) wave
   int64_t work_reals;                      // per-environment REALs of workspace: RK4 stage Data and sums + the convex candidates of max_contact_points (0 for most Euler models)
   int64_t hs_reals = 0;                    // ... of which the constraint phase's hand-over to the register solver (KArgs::hs): small models with one contact condim
@@ -104,6 +117,47 @@ struct mjhModel {
 };
 
 namespace {
+
+// What the host knows of each phase kernel (mjh_phase_kernel<REAL, id, W>): the arena it runs from, the arena whose packing flags (mjhModel::pack2 / pack4) say
+// whether it runs two / four environments per wavefront, and the most environments per wavefront it is instantiated for (mjh_instances.h).  Its threads per
+// workgroup: phase_threads (mjh_kernels.h).
+struct PhaseKernel { Arena arena, pack; int max_envs; };
+constexpr PhaseKernel phase_kernel(int id) {
+  switch (id) {
+    case MJH_KERNEL_KIN: return {AR_KIN, AR_KIN, 4};
+    case MJH_KERNEL_CRB: return {AR_CRB, AR_CRB, 4};
+    case MJH_KERNEL_CON: return {AR_CON, AR_CON, 1};
+    case MJH_KERNEL_VEL: return {AR_VEL, AR_VEL, 4};
+    case MJH_KERNEL_SOL: return {AR_SOL, AR_SOL, 1};
+    case MJH_KERNEL_VEL_OPT: return {AR_VEL, AR_VEL, 4};           // (the velocity phase's arena and packing)
+    case MJH_KERNEL_SOL_GEN: return {AR_SOL, AR_SOL, 1};
+    case MJH_KERNEL_CON_GEN: return {AR_CON, AR_CON, 1};
+    case MJH_KERNEL_CON_DIRECT: return {AR_CON, AR_CON, 2};        // never four per wavefront
+    case MJH_KERNEL_KV: return {AR_KV, AR_KV, 4};
+    case MJH_KERNEL_KCV: return {AR_KCV, AR_CRB, 4};               // (fuse_kcv holds only when the crb stage packs like the other two)
+    case MJH_KERNEL_KCV2: return {AR_KCV2, AR_CRB, 4};
+  }
+  return {AR_COUNT, AR_COUNT, 0};
+}
+
+// lets launches of `kernel` take `bytes` of dynamic LDS
+template <typename F>
+hipError_t allow_lds(F* kernel, int bytes) {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
+// ... for a phase kernel at W lanes per environment: its arena for each of the MJH_WAVE / W environments of a workgroup
+template <typename REAL, int P, int W>
+hipError_t allow_phase_lds(const mjhModel* m) {
+  return allow_lds(&mjh_phase_kernel<REAL, P, W>, MJH_WAVE / W * m->lds(phase_kernel(P).arena));
+}
+// ... for every instantiation of register-solver form `wt`
+template <typename REAL>
+hipError_t allow_sol2_lds(int wt, int bytes) {
+  for (const Sol2Kernel<REAL>& k : kSol2Kernels<REAL>)
+    if (k.wt == wt)
+      if (const hipError_t e = allow_lds(k.fn, bytes)) return e;
+  return hipSuccess;
+}
 
 struct BlobBuilder {
   std::vector<unsigned char> host;
@@ -525,12 +579,13 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
   if (out->cvx_lds_bytes > 64 * 1024) return fail(-12, "convex hull too large for the pair kernel's LDS scratch");
 
   for (int p = 0; p < MJH_NARENA; p++) {
-    out->lds_bytes[p] = lds_carve(M, 1 << p, out->off[p]) * (int)sizeof(REAL);
-    if (p == 4 && out->lds_bytes[p] > 160 * 1024 && M.sol_qm_lds) {  // a large model: qM stays in global memory (L2) for the solver's products
+    ArenaLds& ar = out->arena[p];
+    ar.bytes = lds_carve(M, 1 << p, ar.off) * (int)sizeof(REAL);
+    if (p == AR_SOL && ar.bytes > 160 * 1024 && M.sol_qm_lds) {  // a large model: qM stays in global memory (L2) for the solver's products
       M.sol_qm_lds = 0;
-      out->lds_bytes[p] = lds_carve(M, 1 << p, out->off[p]) * (int)sizeof(REAL);
+      ar.bytes = lds_carve(M, 1 << p, ar.off) * (int)sizeof(REAL);
     }
-    if (p < MJH_NPHASE && out->lds_bytes[p] > 160 * 1024) return fail(-12, "model does not fit the 160 KiB LDS of one CU");
+    if (p < MJH_NPHASE && ar.bytes > 160 * 1024) return fail(-12, "model does not fit the 160 KiB LDS of one CU");
   }
   {  // register solver: CG, slide / hinge limit rows + contact rows only, one dof per lane of a 32-lane half
     static const bool off = [] { const char* e = getenv("MJH_SOL2"); return e && e[0] == '0'; }();
@@ -547,7 +602,7 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
     static const bool w16_off = [] { const char* e = getenv("MJH_SOL2_W16"); return e && e[0] == '0'; }();
     const bool w16 = !w16_off && nmax <= 16 && d->nv <= 16 && d->na <= 16 && d->nl <= 16;
     const bool solver_ok = d->solver == SOL_CG || (d->solver == SOL_NEWTON && nmax <= 16 && (d->nv <= newton_nv || w16));
-    if (!off && solver_ok && !general && d->nv <= 28 && nd <= 32 * (nmax <= 16 ? 8 : 2) && d->nl <= 32 && d->na <= 32 && d->nq <= 64 && 2 * out->lds_bytes[5] <= 64 * 1024) {
+    if (!off && solver_ok && !general && d->nv <= 28 && nd <= 32 * (nmax <= 16 ? 8 : 2) && d->nl <= 32 && d->na <= 32 && d->nq <= 64 && 2 * out->lds(AR_SOL2) <= 64 * 1024) {
       out->sol2_nmax = nmax;
       out->sol2_rpl = rpl;
       // measured on MI355X (profiles/r02/notes.md): ant solver phase 124 -> 114 us (the narrow tier runs three waves per SIMD).  MJH_SOL2_TIERS=0 keeps the single full-width launch.
@@ -561,8 +616,8 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
       if (w16) {
         DevModel<REAL> Mc = M;
         Mc.sol2_row_cap = 16 * w16_rpl;
-        out->lds_tier = lds_carve(Mc, PH_SOL2, out->off_tier) * (int)sizeof(REAL);
-        if (4 * out->lds_tier <= 64 * 1024) {
+        out->arena[AR_TIER].bytes = lds_carve(Mc, PH_SOL2, out->arena[AR_TIER].off) * (int)sizeof(REAL);
+        if (4 * out->lds(AR_TIER) <= 64 * 1024) {
           out->sol2_tiers = 1; out->sol2_w16_rpl = w16_rpl;
           out->sol2_w16_nmax = d->nv <= 8 ? 8 : (d->nv <= 12 ? 12 : 16);
         }
@@ -570,7 +625,7 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
       if (!out->sol2_tiers && rpl > 1 && !tiers_off) {
         DevModel<REAL> Mc = M;
         Mc.sol2_row_cap = 32;
-        out->lds_tier = lds_carve(Mc, PH_SOL2, out->off_tier) * (int)sizeof(REAL);
+        out->arena[AR_TIER].bytes = lds_carve(Mc, PH_SOL2, out->arena[AR_TIER].off) * (int)sizeof(REAL);
         out->sol2_tiers = 1;
       }
     }
@@ -583,12 +638,12 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
     out->fuse_cs = 0;
     if (!off && out->sol2_nmax == 28 && out->sol2_rpl == 1 && !out->sol2_tiers && !M.con_direct && !M.con_general && !M.topk && d->ncon > 0 && d->nefc > 0 && mono &&
         M.con_rows > 0 && M.ncrow == d->nefc - d->nl && d->nf == 0 && d->nv <= 32 && d->nq <= 64 && d->nl <= 32 && d->na <= 32) {
-      const int reals = lds_carve(M, PH_CS, out->off_cs);
+      const int reals = lds_carve(M, PH_CS, out->arena[AR_CS].off);
       if (reals > 0 && 2 * reals * (int)sizeof(REAL) <= 64 * 1024) {
-        out->lds_cs = reals * (int)sizeof(REAL);
+        out->arena[AR_CS].bytes = reals * (int)sizeof(REAL);
         out->fuse_cs = 1;
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_sol2_kernel<REAL, 28, 1, 33>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * out->lds_cs));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_sol2_kernel<REAL, 28, 1, 35>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * out->lds_cs));
+        HIP_TRY(allow_sol2_lds<REAL>(SOL2_CS, 2 * out->lds(AR_CS)));
+        HIP_TRY(allow_sol2_lds<REAL>(SOL2_CS_ONE, 2 * out->lds(AR_CS)));
       }
     }
   }
@@ -606,7 +661,7 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
     out->inv_lds_env = (3 * nv + chunk + chunk * nv + 1) & ~1;
     out->any_damping = 0;
     for (int i = 0; i < nv; i++) if (d->dof_damping[i] != 0) out->any_damping = 1;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_inverse_kernel<REAL>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));  // (the budget plus the rounding of lds_env)
+    HIP_TRY(allow_lds(&mjh_inverse_kernel<REAL>, 64 * 1024));  // (the budget plus the rounding of lds_env)
   }
   out->leaf_count = leaf_counts(d);
   out->work_reals = 0;
@@ -637,78 +692,78 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
   for (auto& f : fix) *f.first = (const unsigned char*)dev + f.second;
   out->blob = dev;
   out->blob_bytes = bb.host.size();
-#define SET_ATTR(P) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, P, MJH_WAVE>), hipFuncAttributeMaxDynamicSharedMemorySize, out->lds_bytes[P]));
-  SET_ATTR(0) SET_ATTR(1) SET_ATTR(2) SET_ATTR(3) SET_ATTR(4)
-#undef SET_ATTR
+  HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KIN, MJH_WAVE>(out)));
+  HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_CRB, MJH_WAVE>(out)));
+  HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_CON, MJH_WAVE>(out)));
+  HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_VEL, MJH_WAVE>(out)));
+  HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_SOL, MJH_WAVE>(out)));
   // phases that are register-bound (not LDS-bound) run two environments per wavefront, 32 lanes each: the same
   // VGPR budget then keeps twice as many environments in flight (mjh_kernels.h, Env<REAL, W>)
-  for (int p = 0; p < MJH_NPHASE; p++) out->pack2[p] = out->pack4[p] = 0;
-#define SET_PACK(P)                                                                                                          \
-  if (2 * out->lds_bytes[P] <= 64 * 1024) {                                                                                  \
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, P, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * out->lds_bytes[P])); \
-    out->pack2[P] = 1;                                                                                                       \
-  }
-  SET_PACK(0) SET_PACK(3)
+  if (2 * out->lds(AR_KIN) <= 64 * 1024) { HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KIN, 32>(out))); out->pack2[AR_KIN] = 1; }
+  if (2 * out->lds(AR_VEL) <= 64 * 1024) { HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_VEL, 32>(out))); out->pack2[AR_VEL] = 1; }
   {  // fused kinematics + velocity kernel (plain velocity phase only).  Measured on MI355X: profiles/r02/notes.md.  MJH_FUSE_KV=0 keeps two launches.
     static const bool fuse_off = [] { const char* e = getenv("MJH_FUSE_KV"); return e && e[0] == '0'; }();
     int defer_ok = 0;
-    out->lds_kv = lds_carve(M, PH_KINVEL, out->off_kv, &defer_ok) * (int)sizeof(REAL);
+    out->arena[AR_KV].bytes = lds_carve(M, PH_KINVEL, out->arena[AR_KV].off, &defer_ok) * (int)sizeof(REAL);
     static const bool defer_off = [] { const char* e = getenv("MJH_KV_DEFER"); return e && e[0] == '0'; }();
     M.kv_defer = (defer_ok && !defer_off) ? 1 : 0;
-    out->fuse_kv = (!fuse_off && !(M.has_fluid || M.has_gravcomp || M.ntendon > 0 || M.big) && out->lds_kv <= 160 * 1024) ? 1 : 0;
+    out->fuse_kv = (!fuse_off && !(M.has_fluid || M.has_gravcomp || M.ntendon > 0 || M.big) && out->lds(AR_KV) <= 160 * 1024) ? 1 : 0;
     if (out->fuse_kv) {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, 12, MJH_WAVE>), hipFuncAttributeMaxDynamicSharedMemorySize, out->lds_kv));
-      if (2 * out->lds_kv <= 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, 12, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * out->lds_kv));
-      if (4 * out->lds_kv <= 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, 12, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * out->lds_kv));
+      HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KV, MJH_WAVE>(out)));
+      if (2 * out->lds(AR_KV) <= 64 * 1024) HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KV, 32>(out)));
+      if (4 * out->lds(AR_KV) <= 64 * 1024) HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KV, 16>(out)));
     }
   }
   static const bool con_pack = [] { const char* e = getenv("MJH_CON_PACK"); return !(e && e[0] == '0'); }();
-  if (con_pack && M.con_direct && 2 * out->lds_bytes[2] <= 64 * 1024) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, 8, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * out->lds_bytes[2]));
-    out->pack2[2] = 1;
-  }
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, 8, MJH_WAVE>), hipFuncAttributeMaxDynamicSharedMemorySize, out->lds_bytes[2]));  // plain constraint phase: its contact rows go straight to the leaf, the arena is small enough for two per wavefront
+  if (con_pack && M.con_direct && 2 * out->lds(AR_CON) <= 64 * 1024) { HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_CON_DIRECT, 32>(out))); out->pack2[AR_CON] = 1; }
+  HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_CON_DIRECT, MJH_WAVE>(out)));  // plain constraint phase: its contact rows go straight to the leaf, the arena is small enough for two per wavefront
   // CRB: the register Cholesky keeps one matrix row per lane, so nv <= 32 would fit a 32-lane half too; measured on the float64
   // humanoid (nv 27) two per wavefront is SLOWER, 50.2 vs 39.9 us (132 VGPRs: 3 waves / SIMD instead of 4, and every broadcast of the
   // factorisation becomes two v_readlane + a select): opt-in only (MJH_CRB_PACK=1).  float32 small models: +13 % on the ant (round 1).
   // (round 4, after the register work of round 3: 35.1 vs 36.5 us, and it is what lets kernel 13 serve the humanoid: default on, MJH_CRB_PACK=0 turns it off)
   static const bool crb_pack = [] { const char* e = getenv("MJH_CRB_PACK"); return !(e && e[0] == '0'); }();
-  if ((sizeof(REAL) == 4 && d->nv <= 16) || (crb_pack && d->nv <= 32 && d->nv > 16)) { SET_PACK(1) }
-#undef SET_PACK
+  if (((sizeof(REAL) == 4 && d->nv <= 16) || (crb_pack && d->nv <= 32 && d->nv > 16)) && 2 * out->lds(AR_CRB) <= 64 * 1024) {
+    HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_CRB, 32>(out)));
+    out->pack2[AR_CRB] = 1;
+  }
   // small models (every per-body / per-joint / per-dof loop fits 16 lanes): FOUR environments per wavefront in the packed phases.
   // These phases are bound by the number of dependent chains a SIMD can interleave (registers cap the waves), so the same waves
   // carrying twice the environments is close to twice the throughput -- measured on the ant (B = 16384, 64 environments per CU):
   // see profiles/r02/notes.md.  MJH_PACK4=0 turns it off.
   static const bool pack4 = [] { const char* e = getenv("MJH_PACK4"); return !(e && e[0] == '0'); }();
   if (pack4 && d->nbody <= 16 && d->njnt <= 16 && d->nv <= 16) {
-#define SET_PACK4(P, Q)                                                                                                      \
-    if (out->pack2[Q] && 4 * out->lds_bytes[Q] <= 64 * 1024) {                                                               \
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, P, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * out->lds_bytes[Q])); \
-      if (P == Q) out->pack4[Q] = 1;                                                                                         \
+    if (out->pack2[AR_KIN] && 4 * out->lds(AR_KIN) <= 64 * 1024) { HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KIN, 16>(out))); out->pack4[AR_KIN] = 1; }
+    if (out->pack2[AR_CRB] && 4 * out->lds(AR_CRB) <= 64 * 1024) { HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_CRB, 16>(out))); out->pack4[AR_CRB] = 1; }
+    if (out->pack2[AR_VEL] && 4 * out->lds(AR_VEL) <= 64 * 1024) {
+      HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_VEL, 16>(out)));
+      HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_VEL_OPT, 16>(out)));
+      out->pack4[AR_VEL] = 1;
     }
-    SET_PACK4(0, 0) SET_PACK4(1, 1) SET_PACK4(3, 3) SET_PACK4(5, 3)
-#undef SET_PACK4
   }
+  // the fused kinematics + velocity kernel packs where both of its phases do and its own arena fits
+  out->pack2[AR_KV] = out->pack2[AR_KIN] && out->pack2[AR_VEL] && 2 * out->lds(AR_KV) <= 64 * 1024;
+  out->pack4[AR_KV] = out->pack4[AR_KIN] && out->pack4[AR_VEL] && 4 * out->lds(AR_KV) <= 64 * 1024;
   {  // kinematics + crb / factor + velocity as ONE kernel (13): when the crb stage packs environments per wavefront the way the other two do (float32 models with
      // nv <= 16; MJH_CRB_PACK for the rest).  Saves the crb kernel's loads of cinert / cdof, its launch and the wait between the launches.  MJH_FUSE_CRB=0: off.
     static const bool off = [] { const char* e = getenv("MJH_FUSE_CRB"); return e && e[0] == '0'; }();
-    out->lds_kcv = lds_carve(M, PH_KCV, out->off_kcv) * (int)sizeof(REAL);
-    const bool same_pack = out->pack2[1] == (out->pack2[0] && out->pack2[3] && 2 * out->lds_kv <= 64 * 1024) && out->pack4[1] == (out->pack4[0] && out->pack4[3] && 4 * out->lds_kv <= 64 * 1024);
-    out->fuse_kcv = (!off && out->fuse_kv && same_pack && out->pack2[1] && out->lds_kcv <= 160 * 1024 && 2 * out->lds_kcv <= 64 * 1024 && (!out->pack4[1] || 4 * out->lds_kcv <= 64 * 1024)) ? 1 : 0;
+    out->arena[AR_KCV].bytes = lds_carve(M, PH_KCV, out->arena[AR_KCV].off) * (int)sizeof(REAL);
+    const bool same_pack = out->pack2[AR_CRB] == out->pack2[AR_KV] && out->pack4[AR_CRB] == out->pack4[AR_KV];
+    out->fuse_kcv = (!off && out->fuse_kv && same_pack && out->pack2[AR_CRB] && out->lds(AR_KCV) <= 160 * 1024 && 2 * out->lds(AR_KCV) <= 64 * 1024 &&
+                     (!out->pack4[AR_CRB] || 4 * out->lds(AR_KCV) <= 64 * 1024)) ? 1 : 0;
     if (out->fuse_kcv) {
       // at every batch size (round 4; round 3 had kept the separate launches past one round of waves): the humanoid (two per wavefront) at B = 32768: 652 us against 452 + 218;
       // the ant (four per wavefront) at B = 16384, two rounds: 93.6 us against 75.8 + 21.8 (profiles/r04/notes.md)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, 13, MJH_WAVE>), hipFuncAttributeMaxDynamicSharedMemorySize, out->lds_kcv));
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, 13, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * out->lds_kcv));
-      if (out->pack4[1]) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, 13, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * out->lds_kcv));
+      HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KCV, MJH_WAVE>(out)));
+      HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KCV, 32>(out)));
+      if (out->pack4[AR_CRB]) HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KCV, 16>(out)));
     }
   }
   {  // kernel 13 on two wavefronts per workgroup (velocity beside crb / factor): packed float32 models.  MJH_KCV2=0 / 1 forces it off / on (also for float64, two per wavefront).
     static const int sw = [] { const char* e = getenv("MJH_KCV2"); return !e ? -1 : (e[0] == '1' ? 1 : 0); }();
     out->kcv2 = 0;
-    if (out->fuse_kcv && sw != 0 && (sw == 1 || (sizeof(REAL) == 4 && out->pack4[1]))) {
-      out->lds_kcv2 = lds_carve(M, PH_KCV2, out->off_kcv2) * (int)sizeof(REAL);
-      const int per_wg = (out->pack4[1] ? 4 : 2) * out->lds_kcv2;
+    if (out->fuse_kcv && sw != 0 && (sw == 1 || (sizeof(REAL) == 4 && out->pack4[AR_CRB]))) {
+      out->arena[AR_KCV2].bytes = lds_carve(M, PH_KCV2, out->arena[AR_KCV2].off) * (int)sizeof(REAL);
+      const int per_wg = (out->pack4[AR_CRB] ? 4 : 2) * out->lds(AR_KCV2);
       if (per_wg <= 64 * 1024) {
         out->kcv2 = 1;
         // The two-wave form pays while the whole batch is resident at once: two wavefronts per workgroup at four per SIMD are 8 workgroups per CU (and their arenas must fit the
@@ -716,26 +771,23 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
         // B = 8192 37.5 us against 46.0; ant B = 8192 46.1 against 54.5; ant B = 16384 (two rounds against one) 101 against 62.
         // The limit belongs to the device a LAUNCH runs on, not to the one that was current when the model was built: kcv2_limit() below, cached per device.
         out->kcv2_per_wg = per_wg;
-        out->kcv2_envs_per_wg = out->pack4[1] ? 4 : 2;
+        out->kcv2_envs_per_wg = out->pack4[AR_CRB] ? 4 : 2;
         out->kcv2_max_envs = sw == 1 ? ((int64_t)1 << 62) : 0;
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, 17, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * out->lds_kcv2));
-        if (out->pack4[1]) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, 17, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * out->lds_kcv2));
+        HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KCV2, 32>(out)));
+        if (out->pack4[AR_CRB]) HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KCV2, 16>(out)));
       }
     }
   }
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, 6, MJH_WAVE>), hipFuncAttributeMaxDynamicSharedMemorySize, out->lds_bytes[4]));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, 7, MJH_WAVE>), hipFuncAttributeMaxDynamicSharedMemorySize, out->lds_bytes[2]));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, 5, MJH_WAVE>), hipFuncAttributeMaxDynamicSharedMemorySize, out->lds_bytes[3]));
-  if (out->pack2[3]) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_phase_kernel<REAL, 5, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * out->lds_bytes[3]));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_convex_kernel<REAL>), hipFuncAttributeMaxDynamicSharedMemorySize, out->cvx_lds_bytes));
+  HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_SOL_GEN, MJH_WAVE>(out)));
+  HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_CON_GEN, MJH_WAVE>(out)));
+  HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_VEL_OPT, MJH_WAVE>(out)));
+  if (out->pack2[AR_VEL]) HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_VEL_OPT, 32>(out)));
+  HIP_TRY(allow_lds(&mjh_convex_kernel<REAL>, out->cvx_lds_bytes));
   if (out->sol2_nmax) {
-#define SET_SOL2(N, R) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_sol2_kernel<REAL, N, R, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * out->lds_bytes[5]));
-    SET_SOL2(8, 1) SET_SOL2(8, 2) SET_SOL2(8, 4) SET_SOL2(8, 8) SET_SOL2(16, 1) SET_SOL2(16, 2) SET_SOL2(16, 4) SET_SOL2(16, 8) SET_SOL2(28, 1) SET_SOL2(28, 2)
-#undef SET_SOL2
+    HIP_TRY(allow_sol2_lds<REAL>(SOL2_PAIR, 2 * out->lds(AR_SOL2)));
     if (out->sol2_w16_rpl) {
-#define SET_SOL2W(N, R) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_sol2_kernel<REAL, N, R, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * out->lds_tier)); HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_sol2_kernel<REAL, N, R, 17>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * out->lds_tier));
-      SET_SOL2W(8, 2) SET_SOL2W(8, 5) SET_SOL2W(12, 2) SET_SOL2W(12, 5) SET_SOL2W(16, 2) SET_SOL2W(16, 5)
-#undef SET_SOL2W
+      HIP_TRY(allow_sol2_lds<REAL>(SOL2_QUAD, 4 * out->lds(AR_TIER)));
+      HIP_TRY(allow_sol2_lds<REAL>(SOL2_QUAD_NEWTON, 4 * out->lds(AR_TIER)));
     }
   }
   {  // the whole pass in one kernel: models both fused kernels serve at two environments per wavefront, without convex pairs or sensors (their kernels sit between the two halves).
@@ -749,13 +801,13 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
     static const int sw = [] { const char* e = getenv("MJH_FUSE_ALL"); return !e ? -1 : (e[0] == '1' ? 1 : 0); }();
     const bool on = sw != 0;  // (round 5, second half: without the kernels' grid-stride loops the generic instantiation takes 228 VGPRs and no scratch either: default on for every model both fused kernels serve)
     out->fuse_all = 0;
-    if (on && out->fuse_cs && out->fuse_kcv && out->pack2[1] && !out->pack4[1] && M.ncvxpair == 0 && d->nsensor == 0) {
-      out->lds_all = out->lds_kcv > out->lds_cs ? out->lds_kcv : out->lds_cs;
+    if (on && out->fuse_cs && out->fuse_kcv && out->pack2[AR_CRB] && !out->pack4[AR_CRB] && M.ncvxpair == 0 && d->nsensor == 0) {
+      out->lds_all = out->lds(AR_KCV) > out->lds(AR_CS) ? out->lds(AR_KCV) : out->lds(AR_CS);
       if (2 * out->lds_all <= 64 * 1024) {
         out->fuse_all = 1;
         M.nt_all = M.all_handoff;
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_sol2_kernel<REAL, 28, 1, 34>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * out->lds_all));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_sol2_kernel<REAL, 28, 1, 36>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * out->lds_all));
+        HIP_TRY(allow_sol2_lds<REAL>(SOL2_PASS, 2 * out->lds_all));
+        HIP_TRY(allow_sol2_lds<REAL>(SOL2_PASS_ONE, 2 * out->lds_all));
       }
     }
   }
@@ -763,11 +815,11 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
      // per wavefront: run twice per wave) and the solver's packed Newton tier at four, behind one another in mjh_sol2_kernel<.., 18>.  MJH_FUSE_STAGE=0: the three launches.
     static const bool off = [] { const char* e = getenv("MJH_FUSE_STAGE"); return e && e[0] == '0'; }();
     out->fuse_stage = 0;
-    if (!off && d->integrator == INT_RK4 && d->solver == SOL_NEWTON && out->fuse_kcv && out->pack4[1] && M.con_direct && out->pack2[2] && out->sol2_tiers && out->sol2_w16_nmax == 8 &&
+    if (!off && d->integrator == INT_RK4 && d->solver == SOL_NEWTON && out->fuse_kcv && out->pack4[AR_CRB] && M.con_direct && out->pack2[AR_CON] && out->sol2_tiers && out->sol2_w16_nmax == 8 &&
         (out->sol2_w16_rpl == 2 || out->sol2_w16_rpl == 5) && M.ncvxpair == 0 && d->nefc > 0) {
-      int need = 4 * out->lds_kcv;
-      if (2 * out->lds_bytes[2] > need) need = 2 * out->lds_bytes[2];
-      if (4 * out->lds_tier > need) need = 4 * out->lds_tier;
+      int need = 4 * out->lds(AR_KCV);
+      if (2 * out->lds(AR_CON) > need) need = 2 * out->lds(AR_CON);
+      if (4 * out->lds(AR_TIER) > need) need = 4 * out->lds(AR_TIER);
       if (need <= 64 * 1024) {
         out->fuse_stage = 1;
         out->lds_stage = need;
@@ -778,16 +830,13 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
     // against 167.9 + 49.2 in two launches -- 8-dof tiers only (the one instantiation that is built), whose kernel sits at the constraint phase's own four waves per SIMD.
     static const bool tail_off = [] { const char* e = getenv("MJH_FUSE_TAIL"); return e && e[0] == '0'; }();
     out->fuse_tail = 0;
-    if (!tail_off && d->solver == SOL_NEWTON && M.con_direct && out->pack2[2] && out->sol2_tiers && out->sol2_w16_nmax == 8 && d->nefc > 0 && !M.topk) {
-      int need = 2 * out->lds_bytes[2];
-      if (4 * out->lds_tier > need) need = 4 * out->lds_tier;
+    if (!tail_off && d->solver == SOL_NEWTON && M.con_direct && out->pack2[AR_CON] && out->sol2_tiers && out->sol2_w16_nmax == 8 && d->nefc > 0 && !M.topk) {
+      int need = 2 * out->lds(AR_CON);
+      if (4 * out->lds(AR_TIER) > need) need = 4 * out->lds(AR_TIER);
       if (need <= 64 * 1024) { out->fuse_tail = 1; out->lds_tail = need; }
     }
     if (out->fuse_stage || out->fuse_tail) {
-      const int need = out->lds_stage > out->lds_tail ? out->lds_stage : out->lds_tail;
-#define SET_ST(N, R) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mjh_sol2_kernel<REAL, N, R, 18>), hipFuncAttributeMaxDynamicSharedMemorySize, need));
-      SET_ST(8, 2) SET_ST(8, 5)
-#undef SET_ST
+      HIP_TRY(allow_sol2_lds<REAL>(SOL2_STAGE, out->lds_stage > out->lds_tail ? out->lds_stage : out->lds_tail));
     }
   }
   return 0;
@@ -800,43 +849,53 @@ static int64_t max_grid() {
   return g;
 }
 
+// The kernels run ONE unit of work per workgroup, `per_wg` units each (no grid-stride loop): `count` units go out as launches of at most `max_wg` workgroups.
+// launch(first, n, workgroups) enqueues the one of units [first, first + n).
+template <typename F>
+int launch_cut(int64_t count, int64_t per_wg, F&& launch, int64_t max_wg = max_grid()) {
+  for (int64_t first = 0; first < count; first += per_wg * max_wg) {
+    const int64_t n = count - first < per_wg * max_wg ? count - first : per_wg * max_wg;
+    launch(first, n, (unsigned)((n + per_wg - 1) / per_wg));
+    HIP_TRY(hipGetLastError());
+  }
+  return 0;
+}
+
 template <typename REAL, int P, int W>
 int launch_range(const mjhModel* m, KArgs<REAL>& a, int64_t begin, int64_t count, hipStream_t stream) {
   if (count <= 0) return 0;
   constexpr int NSUB = MJH_WAVE / W;
-  constexpr int A = P == 5 ? 3 : (P == 6 ? 4 : ((P == 7 || P == 8) ? 2 : (P == 17 ? 0 : P)));  // kernels 5 / 6: velocity phase with fluid forces, solver phase with frictionloss rows
-  const int arena_bytes = P == 17 ? m->lds_kcv2 : (P == 13 ? m->lds_kcv : (P == 12 ? m->lds_kv : m->lds_bytes[(P == 12 || P == 13) ? 0 : A]));
-  a.off = P == 17 ? m->off_kcv2 : (P == 13 ? m->off_kcv : (P == 12 ? m->off_kv : m->off[(P == 12 || P == 13) ? 0 : A]));
-  a.env_begin = begin; a.env_count = count;
-  a.lds_reals = arena_bytes / (int)sizeof(REAL);
-  const int64_t blocks = count / NSUB;
-  for (int64_t b0 = 0; b0 < blocks; b0 += max_grid()) {  // the kernels have no grid-stride loop: one launch per 2^20 workgroups
-    const int64_t grid = blocks - b0 < max_grid() ? blocks - b0 : max_grid();
-    a.env_begin = begin + b0 * NSUB; a.env_count = grid * NSUB;
-    hipLaunchKernelGGL((mjh_phase_kernel<REAL, P, W>), dim3((unsigned)grid), dim3(P == 17 ? 2 * MJH_WAVE : MJH_WAVE), (size_t)(NSUB * arena_bytes), stream, a);  // (17: a second wavefront per workgroup runs the crb / factor stage)
-    HIP_TRY(hipGetLastError());
-  }
+  const ArenaLds& ar = m->arena[phase_kernel(P).arena];
+  a.off = ar.off;
+  a.lds_reals = ar.bytes / (int)sizeof(REAL);
+  const int rc = launch_cut(count, NSUB, [&](int64_t first, int64_t n, unsigned grid) {
+    a.env_begin = begin + first; a.env_count = n;
+    hipLaunchKernelGGL((mjh_phase_kernel<REAL, P, W>), dim3(grid), dim3(phase_threads(P)), (size_t)(NSUB * ar.bytes), stream, a);
+  });
+  if (rc) return rc;
   timing_mark(stream, P);
   return 0;
 }
 template <typename REAL, int P>
 int launch_phase(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
-  constexpr bool PACKABLE = (P == 0 || P == 1 || P == 3 || P == 5 || P == 8 || P == 12 || P == 13 || P == 17);
-  constexpr int PI = !PACKABLE ? 0 : (P == 5 ? 3 : (P == 8 ? 2 : ((P == 12 || P == 13 || P == 17) ? 0 : P)));  // index into the per-phase packing flags
-  const bool can2 = !PACKABLE ? false : ((P == 13 || P == 17) ? (bool)m->pack2[1] : (P == 12 ? (m->pack2[0] && m->pack2[3] && 2 * m->lds_kv <= 64 * 1024) : (bool)m->pack2[PI]));  // (13: fuse_kcv holds only when the crb stage packs like the other two)
-  const bool can4 = !PACKABLE ? false : ((P == 13 || P == 17) ? (bool)m->pack4[1] : (P == 12 ? (m->pack4[0] && m->pack4[3] && 4 * m->lds_kv <= 64 * 1024) : (P != 8 && m->pack4[PI])));
-  if (PACKABLE && can2 && a.B >= 2) {  // groups of four / pairs of environments, then the odd one on its own
-    int64_t done = 0;
-    int rc = 0;
-    if (can4 && a.B >= 4) {
-      done = a.B & ~(int64_t)3;
-      if ((rc = launch_range<REAL, P, ((PACKABLE && P != 8) ? 16 : MJH_WAVE)>(m, a, 0, done, stream))) return rc;
+  constexpr PhaseKernel K = phase_kernel(P);
+  int64_t done = 0;
+  int rc = 0;
+  if constexpr (K.max_envs > 1) {
+    if (m->pack2[K.pack] && a.B >= 2) {  // groups of four / pairs of environments, then the odd one on its own
+      if constexpr (K.max_envs == 4) {
+        if (m->pack4[K.pack] && a.B >= 4) {
+          done = a.B & ~(int64_t)3;
+          if ((rc = launch_range<REAL, P, 16>(m, a, 0, done, stream))) return rc;
+        }
+      }
+      const int64_t even = (a.B - done) & ~(int64_t)1;
+      if ((rc = launch_range<REAL, P, 32>(m, a, done, even, stream))) return rc;
+      done += even;
     }
-    const int64_t even = (a.B - done) & ~(int64_t)1;
-    if ((rc = launch_range<REAL, P, (PACKABLE ? 32 : MJH_WAVE)>(m, a, done, even, stream))) return rc;
-    return launch_range<REAL, (P == 17 ? 13 : P), MJH_WAVE>(m, a, done + even, a.B - done - even, stream);  // (the odd environment: one per wavefront -- the two-wave form only exists packed, kernel 13 serves it)
   }
-  return launch_range<REAL, (P == 17 ? 13 : P), MJH_WAVE>(m, a, 0, a.B, stream);
+  // (one environment per wavefront: the two-wave form only exists packed, kernel 13 serves the odd environment)
+  return launch_range<REAL, (P == MJH_KERNEL_KCV2 ? MJH_KERNEL_KCV : P), MJH_WAVE>(m, a, done, a.B - done, stream);
 }
 
 // MJH_XSWAP=mask (12 bits of the workgroup index; 0: off): in the whole-pass kernel and the stage kernel, workgroups of odd parity under the mask run the velocity stage before
@@ -857,62 +916,71 @@ static int xswap_k_mask(int64_t workgroups) {
   return (forced || workgroups <= 4096) ? f : 0;
 }
 
+// the out-of-lockstep masks of a launcher of `workgroups` workgroups: a.flags carries MJH_XSWAP's for the launcher's scope, a.xswap_k MJH_XSWAP_K's
+template <typename REAL>
+struct OutOfLockstep {
+  KArgs<REAL>& a;
+  const int flags;
+  OutOfLockstep(KArgs<REAL>& args, int64_t workgroups) : a(args), flags(args.flags) {
+    a.flags |= xswap_flags(workgroups);
+    a.xswap_k = xswap_k_mask(workgroups);
+  }
+  ~OutOfLockstep() { a.flags = flags; }
+};
+
+// register-solver instantiation (NMAX, RPL, form WT) over the batch, MJH_WAVE / lanes environments per workgroup
+template <typename REAL>
+int launch_sol2_kernel(KArgs<REAL>& a, int nmax, int rpl, int wt, int lds, hipStream_t stream) {
+  const Kernel<REAL> fn = sol2_kernel<REAL>(nmax, rpl, wt);
+  if (!fn) return fail(-5, "no register-solver instantiation for this model");
+  if (a.scan_marks) {  // the marks-scanning second tier walks the batch itself: one grid of at most 4096 waves (env_begin = 0, env_count = B)
+    const int64_t waves = (a.B + MJH_WAVE - 1) / MJH_WAVE;
+    hipLaunchKernelGGL(fn, dim3((unsigned)(waves < 4096 ? waves : 4096)), dim3(MJH_WAVE), (size_t)lds, stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  }
+  const int rc = launch_cut(a.B, MJH_WAVE / sol2_form(wt).lanes, [&](int64_t first, int64_t n, unsigned grid) {
+    a.env_begin = first; a.env_count = n;
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(MJH_WAVE), (size_t)lds, stream, a);
+  });
+  a.env_begin = 0; a.env_count = a.B;
+  return rc;
+}
+
 // the solver phase through the register solver: two (or, first tier of a small model, four) environments per wavefront
 template <typename REAL>
 int launch_sol2(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream, bool first_done = false) {  // first_done: the stage kernel has run the first tier (and marked what it left): only the second tier is launched
   a.env_begin = 0; a.env_count = a.B;
-  const int64_t blocks = (a.B + 1) / 2;
-  const int64_t grid = blocks < (int64_t)1 << 20 ? blocks : (int64_t)1 << 20;
-  // (the kernels have no grid-stride loop: one launch per 2^20 workgroups of NS environments each; the marks-scanning second tier keeps its own walk)
-#define CHUNKED(NS, LAUNCH) do { if (a.scan_marks) { a.env_begin = 0; a.env_count = a.B; const int64_t g_ = grid; (void)g_; LAUNCH(grid); } else for (int64_t e0_ = 0; e0_ < a.B; e0_ += NS * max_grid()) { const int64_t n_ = a.B - e0_ < NS * max_grid() ? a.B - e0_ : NS * max_grid(); a.env_begin = e0_; a.env_count = n_; LAUNCH((n_ + NS - 1) / NS); } a.env_begin = 0; a.env_count = a.B; } while (0)
-#define GO(N, R) do { auto L_ = [&](int64_t g) { hipLaunchKernelGGL((mjh_sol2_kernel<REAL, N, R, 32>), dim3((unsigned)g), dim3(MJH_WAVE), lds, stream, a); }; CHUNKED(2, L_); } while (0)
-#define GOW(N, R) do { auto L_ = [&](int64_t g) { if (a.M.solver == SOL_NEWTON) hipLaunchKernelGGL((mjh_sol2_kernel<REAL, N, R, 17>), dim3((unsigned)g), dim3(MJH_WAVE), lds, stream, a); else hipLaunchKernelGGL((mjh_sol2_kernel<REAL, N, R, 16>), dim3((unsigned)g), dim3(MJH_WAVE), lds, stream, a); }; CHUNKED(4, L_); } while (0)  /* 17: the Newton-only code of the four-per-wavefront tier */
   const int nd = a.M.nefc - a.M.nf - a.M.nl;
   bool second = true;
   const bool marks = m->sol2_tiers && a.cur.qacc != nullptr;  // the first tier marks what it leaves, the second scans the marks (needs the qacc leaf)
   a.mark_leftover = marks ? 1 : 0;
+  int rc = 0;
+  a.row_lo = -1;
   if (m->sol2_tiers) {  // first tier: fewer row slots per lane, its own (smaller) arena
-    a.off = m->off_tier;
-    a.lds_reals = m->lds_tier / (int)sizeof(REAL);
+    a.off = m->arena[AR_TIER].off;
+    a.lds_reals = m->lds(AR_TIER) / (int)sizeof(REAL);
     if (m->sol2_w16_rpl) {
-      const int64_t blocks4 = (a.B + 3) / 4;
-      const int64_t grid4 = blocks4 < (int64_t)1 << 20 ? blocks4 : (int64_t)1 << 20;
-      a.row_lo = -1; a.row_hi = 16 * m->sol2_w16_rpl;
-      const size_t lds = (size_t)(4 * m->lds_tier);
-      if (first_done) {}
-      else if (m->sol2_w16_nmax == 8) { if (m->sol2_w16_rpl == 2) GOW(8, 2); else GOW(8, 5); }
-      else if (m->sol2_w16_nmax == 12) { if (m->sol2_w16_rpl == 2) GOW(12, 2); else GOW(12, 5); }
-      else { if (m->sol2_w16_rpl == 2) GOW(16, 2); else GOW(16, 5); }
+      a.row_hi = 16 * m->sol2_w16_rpl;
+      const int wt = a.M.solver == SOL_NEWTON ? SOL2_QUAD_NEWTON : SOL2_QUAD;
+      if (!first_done && (rc = launch_sol2_kernel(a, m->sol2_w16_nmax, m->sol2_w16_rpl, wt, 4 * m->lds(AR_TIER), stream))) return rc;
       second = nd > a.row_hi;  // every environment fits the first tier otherwise
     } else {
-      a.row_lo = -1; a.row_hi = 32;
-      const size_t lds = (size_t)(2 * m->lds_tier);
-      if (m->sol2_nmax == 8) GO(8, 1); else if (m->sol2_nmax == 16) GO(16, 1); else GO(28, 1);
+      a.row_hi = 32;
+      if ((rc = launch_sol2_kernel(a, m->sol2_nmax, 1, SOL2_PAIR, 2 * m->lds(AR_TIER), stream))) return rc;
     }
-    HIP_TRY(hipGetLastError());
     a.row_lo = a.row_hi;
-  } else {
-    a.row_lo = -1;
   }
   a.mark_leftover = 0;
   if (second) {
     a.row_hi = 0x7fffffff;
-    a.off = m->off[5];
-    a.lds_reals = m->lds_bytes[5] / (int)sizeof(REAL);
+    a.off = m->arena[AR_SOL2].off;
+    a.lds_reals = m->lds(AR_SOL2) / (int)sizeof(REAL);
     a.scan_marks = marks ? 1 : 0;
-    const int64_t sblocks = (a.B + MJH_WAVE - 1) / MJH_WAVE;
-    const int64_t grid = marks ? (sblocks < 4096 ? sblocks : 4096) : (blocks < (int64_t)1 << 20 ? blocks : (int64_t)1 << 20);
-    const size_t lds = (size_t)(2 * m->lds_bytes[5]);
-    if (m->sol2_nmax == 8) { if (m->sol2_rpl == 1) GO(8, 1); else if (m->sol2_rpl == 2) GO(8, 2); else if (m->sol2_rpl == 4) GO(8, 4); else GO(8, 8); }
-    else if (m->sol2_nmax == 16) { if (m->sol2_rpl == 1) GO(16, 1); else if (m->sol2_rpl == 2) GO(16, 2); else if (m->sol2_rpl == 4) GO(16, 4); else GO(16, 8); }
-    else { if (m->sol2_rpl == 1) GO(28, 1); else GO(28, 2); }
-    HIP_TRY(hipGetLastError());
+    if ((rc = launch_sol2_kernel(a, m->sol2_nmax, m->sol2_rpl, SOL2_PAIR, 2 * m->lds(AR_SOL2), stream))) return rc;
     a.scan_marks = 0;
   }
-#undef GO
-#undef GOW
-#undef CHUNKED
-  if (!(first_done && !second)) timing_mark(stream, 9);  // both tiers under one mark: the solver phase (behind the stage kernel: the second tier alone, when there is one)
+  if (!(first_done && !second)) timing_mark(stream, MJH_KERNEL_SOL2);  // both tiers under one mark: the solver phase (behind the stage kernel: the second tier alone, when there is one)
   return 0;
 }
 
@@ -920,85 +988,60 @@ int launch_sol2(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream, bool firs
 template <typename REAL>
 int launch_stage(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream, int parts = 7) {  // parts 6: the tail of a pass (constraint phase + first solver tier) behind launches of its own for the rest
   a.stage_parts = parts;
-  const int keep_flags_ = a.flags;
-  a.flags |= xswap_flags(a.B / 4);
-  struct RestoreF_ { KArgs<REAL>& a; int f; ~RestoreF_() { a.flags = f; } } restore_f_{a, keep_flags_};
-  a.xswap_k = xswap_k_mask(a.B / 4);
+  const OutOfLockstep<REAL> swap(a, a.B / 4);
   static const int xswap_c = [] { const char* e = getenv("MJH_XSWAP_C"); return e ? (int)(strtol(e, nullptr, 0) & 0xfff) : 0x400; }();  // MJH_XSWAP_C=mask (0: off; see KArgs::xswap_c): measured ant 30.9 -> 31.1 M env-steps/s
   a.xswap_c = a.rk_stage == 0 ? xswap_c : 0;
-  a.off = m->off_kcv; a.lds_reals = m->lds_kcv / (int)sizeof(REAL);
-  a.off2 = m->off[2]; a.lds_reals2 = m->lds_bytes[2] / (int)sizeof(REAL);
-  a.off3 = m->off_tier; a.lds_reals3 = m->lds_tier / (int)sizeof(REAL);
+  a.off = m->arena[AR_KCV].off; a.lds_reals = m->lds(AR_KCV) / (int)sizeof(REAL);
+  a.off2 = m->arena[AR_CON].off; a.lds_reals2 = m->lds(AR_CON) / (int)sizeof(REAL);
+  a.off3 = m->arena[AR_TIER].off; a.lds_reals3 = m->lds(AR_TIER) / (int)sizeof(REAL);
   a.row_lo = -1; a.row_hi = 16 * m->sol2_w16_rpl;
   a.mark_leftover = (m->sol2_tiers && a.cur.qacc != nullptr) ? 1 : 0;
   a.scan_marks = 0;
-  for (int64_t e0 = 0; e0 < a.B; e0 += 4 * max_grid()) {  // (no grid-stride loop in the kernels: one launch per 2^20 workgroups)
-    const int64_t n = a.B - e0 < 4 * max_grid() ? a.B - e0 : 4 * max_grid();
-    a.env_begin = e0; a.env_count = n;
-    const size_t lds = (size_t)(parts == 7 ? m->lds_stage : m->lds_tail);
-    const dim3 g((unsigned)(n / 4)), b(MJH_WAVE);
-    if (m->sol2_w16_rpl == 2) hipLaunchKernelGGL((mjh_sol2_kernel<REAL, 8, 2, 18>), g, b, lds, stream, a);  // (fuse_stage / fuse_tail: 8-dof tiers only)
-    else hipLaunchKernelGGL((mjh_sol2_kernel<REAL, 8, 5, 18>), g, b, lds, stream, a);
-    HIP_TRY(hipGetLastError());
-  }
-  a.env_begin = 0; a.env_count = a.B;
-  timing_mark(stream, parts == 7 ? 18 : 19);
+  // (fuse_stage / fuse_tail: 8-dof tiers only)
+  if (const int rc = launch_sol2_kernel(a, 8, m->sol2_w16_rpl, SOL2_STAGE, parts == 7 ? m->lds_stage : m->lds_tail, stream)) return rc;
+  timing_mark(stream, parts == 7 ? MJH_KERNEL_STAGE : MJH_KERNEL_TAIL);
   return launch_sol2<REAL>(m, a, stream, true);
 }
 
 // constraint stage + register solver + integrator in one launch (mjhModel::fuse_cs)
 template <typename REAL>
 int launch_cs(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
-  a.env_begin = 0; a.env_count = a.B;
-  a.off = m->off_cs;
-  a.lds_reals = m->lds_cs / (int)sizeof(REAL);
+  a.off = m->arena[AR_CS].off;
+  a.lds_reals = m->lds(AR_CS) / (int)sizeof(REAL);
   a.row_lo = -1; a.row_hi = 0x7fffffff;
   a.mark_leftover = 0; a.scan_marks = 0;
   static const bool one_off = [] { const char* e = getenv("MJH_CS_ONE"); return e && e[0] == '0'; }();  // (A / B switch: MJH_CS_ONE=0 launches the generic instantiation for one-iteration models too)
-  for (int64_t e0 = 0; e0 < a.B; e0 += 2 * max_grid()) {  // (no grid-stride loop in the kernels: one launch per 2^20 workgroups)
-    const int64_t n = a.B - e0 < 2 * max_grid() ? a.B - e0 : 2 * max_grid(), grid = (n + 1) / 2;
-    a.env_begin = e0; a.env_count = n;
-    if (a.M.iterations == 1 && !one_off) hipLaunchKernelGGL((mjh_sol2_kernel<REAL, 28, 1, 35>), dim3((unsigned)grid), dim3(MJH_WAVE), (size_t)(2 * m->lds_cs), stream, a);  // opt.iterations == 1 (solver.py:534-535: the loop body runs exactly once): straight-line solver code
-    else hipLaunchKernelGGL((mjh_sol2_kernel<REAL, 28, 1, 33>), dim3((unsigned)grid), dim3(MJH_WAVE), (size_t)(2 * m->lds_cs), stream, a);
-  }
-  a.env_begin = 0; a.env_count = a.B;
-  HIP_TRY(hipGetLastError());
-  timing_mark(stream, 14);
+  // opt.iterations == 1 (solver.py:534-535: the loop body runs exactly once): straight-line solver code
+  const int wt = a.M.iterations == 1 && !one_off ? SOL2_CS_ONE : SOL2_CS;
+  if (const int rc = launch_sol2_kernel(a, 28, 1, wt, 2 * m->lds(AR_CS), stream)) return rc;
+  timing_mark(stream, MJH_KERNEL_CS);
   return 0;
 }
 
-// the whole pass in one launch (mjhModel::fuse_all)
+// the whole pass in one launch (mjhModel::fuse_all).  The caller bounds B to one launch.
 template <typename REAL>
 int launch_all(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
-  a.env_begin = 0; a.env_count = a.B;
-  a.off = m->off_kcv; a.off2 = m->off_cs;
+  a.off = m->arena[AR_KCV].off; a.off2 = m->arena[AR_CS].off;
   a.lds_reals = m->lds_all / (int)sizeof(REAL);
   a.row_lo = -1; a.row_hi = 0x7fffffff;
   a.mark_leftover = 0; a.scan_marks = 0;
   const int64_t blocks = (a.B + 1) / 2;
-  const int64_t grid = blocks < (int64_t)1 << 20 ? blocks : (int64_t)1 << 20;
-  const int keep_flags_ = a.flags;
-  a.flags |= xswap_flags(grid);
-  struct RestoreF_ { KArgs<REAL>& a; int f; ~RestoreF_() { a.flags = f; } } restore_f_{a, keep_flags_};
-  a.xswap_k = xswap_k_mask(grid);
-  if (a.M.iterations == 1) hipLaunchKernelGGL((mjh_sol2_kernel<REAL, 28, 1, 36>), dim3((unsigned)grid), dim3(MJH_WAVE), (size_t)(2 * m->lds_all), stream, a);
-  else hipLaunchKernelGGL((mjh_sol2_kernel<REAL, 28, 1, 34>), dim3((unsigned)grid), dim3(MJH_WAVE), (size_t)(2 * m->lds_all), stream, a);
-  HIP_TRY(hipGetLastError());
-  timing_mark(stream, 16);
+  const OutOfLockstep<REAL> swap(a, blocks < (int64_t)1 << 20 ? blocks : (int64_t)1 << 20);
+  if (const int rc = launch_sol2_kernel(a, 28, 1, a.M.iterations == 1 ? SOL2_PASS_ONE : SOL2_PASS, 2 * m->lds_all, stream)) return rc;
+  timing_mark(stream, MJH_KERNEL_PASS);
   return 0;
 }
 
-// convex narrow phase: one wavefront per (environment, pair); sensors: one per environment.  No grid-stride loops in the kernels: one launch per 2^22 items / 2^20 environments
+// convex narrow phase: one wavefront per (environment, pair), one launch per 2^22 of them; sensors: one per environment
 template <typename REAL>
 int launch_convex(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
-  const int64_t items = a.B * a.M.ncvxpair;
-  for (int64_t i0 = 0; i0 < items; i0 += 4 * max_grid()) {
-    const int64_t grid = items - i0 < 4 * max_grid() ? items - i0 : 4 * max_grid();
-    a.env_begin = i0;  // (first ITEM of this launch)
-    hipLaunchKernelGGL((mjh_convex_kernel<REAL>), dim3((unsigned)grid), dim3(MJH_WAVE), (size_t)m->cvx_lds_bytes, stream, a);
-    HIP_TRY(hipGetLastError());
-  }
+  const int rc = launch_cut(a.B * a.M.ncvxpair, 1, [&](int64_t first, int64_t, unsigned grid) {
+    a.env_begin = first;  // (first ITEM of this launch)
+    hipLaunchKernelGGL((mjh_convex_kernel<REAL>), dim3(grid), dim3(MJH_WAVE), (size_t)m->cvx_lds_bytes, stream, a);
+  }, 4 * max_grid());
   a.env_begin = 0;
+  if (rc) return rc;
+  timing_mark(stream, MJH_KERNEL_CONVEX);
   return 0;
 }
 template <typename REAL>
@@ -1011,14 +1054,14 @@ int launch_sensor_kernel(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) 
   epw = epw < 1 ? 1 : (epw_env > 0 ? (epw > 8 ? 8 : epw) : (epw > 2 ? 2 : epw));
   a.sns_epw = epw;
   const size_t lds = sizeof(double) * (size_t)(a.M.nrfq + 1) * (size_t)epw;
-  for (int64_t e0 = 0; e0 < a.B; e0 += epw * max_grid()) {
-    const int64_t n = a.B - e0 < epw * max_grid() ? a.B - e0 : epw * max_grid(), grid = (n + epw - 1) / epw;
-    a.env_begin = e0; a.env_count = n;
-    if (a.M.sns_full) hipLaunchKernelGGL((mjh_sensor_kernel<REAL, 1>), dim3((unsigned)grid), dim3(MJH_WAVE), lds, stream, a);
-    else hipLaunchKernelGGL((mjh_sensor_kernel<REAL, 0>), dim3((unsigned)grid), dim3(MJH_WAVE), lds, stream, a);
-    HIP_TRY(hipGetLastError());
-  }
+  const int rc = launch_cut(a.B, epw, [&](int64_t first, int64_t n, unsigned grid) {
+    a.env_begin = first; a.env_count = n;
+    if (a.M.sns_full) hipLaunchKernelGGL((mjh_sensor_kernel<REAL, 1>), dim3(grid), dim3(MJH_WAVE), lds, stream, a);
+    else hipLaunchKernelGGL((mjh_sensor_kernel<REAL, 0>), dim3(grid), dim3(MJH_WAVE), lds, stream, a);
+  });
   a.env_begin = 0; a.env_count = a.B;
+  if (rc) return rc;
+  timing_mark(stream, MJH_KERNEL_SENSOR);
   return 0;
 }
 
@@ -1043,53 +1086,56 @@ static int64_t kcv2_limit(const mjhModel* m, hipStream_t stream) {
   return (int64_t)cus_of[dev] * wgs * m->kcv2_envs_per_wg;
 }
 
+// Stage masks: mjh_forward runs the pipeline up to and including the highest stage bit asked for, so a phase runs when any stage at or past its own is.
+constexpr int kFromCrb = MJH_STAGE_ALL & ~MJH_STAGE_KINEMATICS;
+constexpr int kFromCollision = kFromCrb & ~MJH_STAGE_CRB;
+constexpr int kFromVelocity = MJH_STAGE_VELOCITY | MJH_STAGE_ACTUATION | MJH_STAGE_SOLVE;
+constexpr int kFromActuation = MJH_STAGE_ACTUATION | MJH_STAGE_SOLVE;
+constexpr int kUpToVelocity = MJH_STAGE_ALL & ~kFromActuation;
+
 // one forward pass = the phases selected by `stages`
 template <typename REAL>
 int forward_pass(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
   int rc = 0;
   const int st = a.stages;
-  if (m->fuse_all && (st & 0x7f) == 0x7f && a.B >= 2 && (a.B & 1) == 0 && a.B <= 2 * max_grid() /* one workgroup per pair: the kernel has no grid-stride loop */ && a.cur.efc_J && a.cur.efc_D && a.cur.efc_aref && a.cur.qM && a.cur.qLD) return launch_all<REAL>(m, a, stream);
+  if (m->fuse_all && (st & MJH_STAGE_ALL) == MJH_STAGE_ALL && a.B >= 2 && (a.B & 1) == 0 && a.B <= 2 * max_grid() /* one workgroup per pair: the kernel has no grid-stride loop */ && a.cur.efc_J && a.cur.efc_D && a.cur.efc_aref && a.cur.qM && a.cur.qLD) return launch_all<REAL>(m, a, stream);
   // MJH_FUSE_STAGE0=0: stage 0 (which writes the returned Data in full) keeps its three launches.  Its sensors (they read leaves of the kinematics and velocity stages only) follow the
   // stage kernel: in an RK4 step nothing of stage 0 writes the returned state -- the final advance is stage 3's -- so the jointpos / ballquat readers of out.qpos race nothing.
   static const bool stage0_off = [] { const char* e = getenv("MJH_FUSE_STAGE0"); return e && e[0] == '0'; }();
-  if (m->fuse_stage && a.rk_stage >= (stage0_off ? 1 : 0) && (st & 0x7f) == 0x7f && a.B >= 4 && (a.B & 3) == 0 && a.cur.qM && a.cur.qLD && a.cur.qfrc_smooth && a.cur.contact_dist &&
+  if (m->fuse_stage && a.rk_stage >= (stage0_off ? 1 : 0) && (st & MJH_STAGE_ALL) == MJH_STAGE_ALL && a.B >= 4 && (a.B & 3) == 0 && a.cur.qM && a.cur.qLD && a.cur.qfrc_smooth && a.cur.contact_dist &&
       a.cur.efc_J && a.cur.efc_D && a.cur.efc_aref) {
     if ((rc = launch_stage<REAL>(m, a, stream))) return rc;
     if (a.M.nsensor > 0 && a.rk_stage == 0 && a.cur.sensordata) {
       if ((rc = launch_sensor_kernel<REAL>(m, a, stream))) return rc;
-      timing_mark(stream, 11);
     }
     return 0;
   }
-  const bool fused_kv = m->fuse_kv && (st & 0x70);  // the velocity phase is asked for: it rides with the kinematics (it needs nothing of CRB / CON)
-  const bool fused_kcv = fused_kv && m->fuse_kcv && (st & 0x7e);  // ... and so does the crb / factor stage (small models)
-  if ((st & 0x7f) && (rc = fused_kcv ? ((m->kcv2 && a.B <= kcv2_limit(m, stream)) ? launch_phase<REAL, 17>(m, a, stream) : launch_phase<REAL, 13>(m, a, stream)) : (fused_kv ? launch_phase<REAL, 12>(m, a, stream) : launch_phase<REAL, 0>(m, a, stream)))) return rc;
-  if ((st & 0x7c) && a.M.ncvxpair > 0) {  // convex narrow phase: one wave per (environment, pair); needs only the geom frames of PH_KIN
+  const bool fused_kv = m->fuse_kv && (st & kFromVelocity);  // the velocity phase is asked for: it rides with the kinematics (it needs nothing of CRB / CON)
+  const bool fused_kcv = fused_kv && m->fuse_kcv && (st & kFromCrb);  // ... and so does the crb / factor stage (small models)
+  if ((st & MJH_STAGE_ALL) && (rc = fused_kcv ? ((m->kcv2 && a.B <= kcv2_limit(m, stream)) ? launch_phase<REAL, MJH_KERNEL_KCV2>(m, a, stream) : launch_phase<REAL, MJH_KERNEL_KCV>(m, a, stream)) : (fused_kv ? launch_phase<REAL, MJH_KERNEL_KV>(m, a, stream) : launch_phase<REAL, MJH_KERNEL_KIN>(m, a, stream)))) return rc;
+  if ((st & kFromCollision) && a.M.ncvxpair > 0) {  // convex narrow phase: one wave per (environment, pair); needs only the geom frames of PH_KIN
     if ((rc = launch_convex<REAL>(m, a, stream))) return rc;
-    timing_mark(stream, 10);
   }
-  if ((st & 0x7e) && !fused_kcv && (rc = launch_phase<REAL, 1>(m, a, stream))) return rc;
-  const bool fused_cs = m->fuse_cs && (st & 0x7c) && (st & 0x40) && a.cur.efc_J && a.cur.efc_D && a.cur.efc_aref;  // the whole tail of the pass is asked for: constraint stage and solve share a kernel
-  const bool fused_tail = !fused_cs && m->fuse_tail && (st & 0x7c) == 0x7c && a.B >= 4 && (a.B & 3) == 0 && a.cur.qM && a.cur.qLD && a.cur.qfrc_smooth && a.cur.contact_dist &&
+  if ((st & kFromCrb) && !fused_kcv && (rc = launch_phase<REAL, MJH_KERNEL_CRB>(m, a, stream))) return rc;
+  const bool fused_cs = m->fuse_cs && (st & kFromCollision) && (st & MJH_STAGE_SOLVE) && a.cur.efc_J && a.cur.efc_D && a.cur.efc_aref;  // the whole tail of the pass is asked for: constraint stage and solve share a kernel
+  const bool fused_tail = !fused_cs && m->fuse_tail && (st & kFromCollision) == kFromCollision && a.B >= 4 && (a.B & 3) == 0 && a.cur.qM && a.cur.qLD && a.cur.qfrc_smooth && a.cur.contact_dist &&
                           a.cur.efc_J && a.cur.efc_D && a.cur.efc_aref && !(a.M.has_fluid || a.M.has_gravcomp || a.M.ntendon > 0 || a.M.big) && fused_kv;  // (the velocity stage has run: it rode with the kinematics)
   if (fused_tail) {  // small Newton models: constraint phase + first solver tier + integrator in one launch (their sensors read leaves of the kinematics / velocity stages only: first)
-    if ((st & 0x40) && a.M.nsensor > 0 && a.rk_stage <= 0 && a.cur.sensordata) {
+    if ((st & MJH_STAGE_SOLVE) && a.M.nsensor > 0 && a.rk_stage <= 0 && a.cur.sensordata) {
       if ((rc = launch_sensor_kernel<REAL>(m, a, stream))) return rc;
-      timing_mark(stream, 11);
     }
     return launch_stage<REAL>(m, a, stream, 6);
   }
-  if (!fused_cs && (st & 0x7c) && (a.M.ncon > 0 || a.M.nefc > 0) &&
-      (rc = a.M.con_general ? launch_phase<REAL, 7>(m, a, stream) : (a.M.con_direct ? launch_phase<REAL, 8>(m, a, stream) : launch_phase<REAL, 2>(m, a, stream)))) return rc;
-  if ((st & 0x70) && !fused_kv && (rc = (a.M.has_fluid || a.M.has_gravcomp || a.M.ntendon > 0 || a.M.big) ? launch_phase<REAL, 5>(m, a, stream) : launch_phase<REAL, 3>(m, a, stream))) return rc;
-  const bool want_sensors = (st & 0x40) && a.M.nsensor > 0 && a.rk_stage <= 0 && a.cur.sensordata;  // needs only the leaves of KIN and VEL
+  if (!fused_cs && (st & kFromCollision) && (a.M.ncon > 0 || a.M.nefc > 0) &&
+      (rc = a.M.con_general ? launch_phase<REAL, MJH_KERNEL_CON_GEN>(m, a, stream) : (a.M.con_direct ? launch_phase<REAL, MJH_KERNEL_CON_DIRECT>(m, a, stream) : launch_phase<REAL, MJH_KERNEL_CON>(m, a, stream)))) return rc;
+  if ((st & kFromVelocity) && !fused_kv && (rc = (a.M.has_fluid || a.M.has_gravcomp || a.M.ntendon > 0 || a.M.big) ? launch_phase<REAL, MJH_KERNEL_VEL_OPT>(m, a, stream) : launch_phase<REAL, MJH_KERNEL_VEL>(m, a, stream))) return rc;
+  const bool want_sensors = (st & MJH_STAGE_SOLVE) && a.M.nsensor > 0 && a.rk_stage <= 0 && a.cur.sensordata;  // needs only the leaves of KIN and VEL
   if (want_sensors) {  // (round 4's opt-in side stream for this launch is gone: it raced the integrator tail's write of out.qpos, which jointpos / ballquat sensors read, and measured no gain -- profiles/r04/notes.md)
     if ((rc = launch_sensor_kernel<REAL>(m, a, stream))) return rc;
-    timing_mark(stream, 11);
   }
   if (fused_cs) return launch_cs<REAL>(m, a, stream);
-  if ((st & 0x60) && m->sol2_nmax) return launch_sol2<REAL>(m, a, stream);
-  if ((st & 0x60) && (rc = (a.M.nf > 0 || a.M.nft > 0 || a.M.ne > 0 || a.M.nlb > 0 || a.M.nlt > 0) ? launch_phase<REAL, 6>(m, a, stream) : launch_phase<REAL, 4>(m, a, stream))) return rc;  // 0x20: _acceleration's solve lives at the head of the solver phase
+  if ((st & kFromActuation) && m->sol2_nmax) return launch_sol2<REAL>(m, a, stream);
+  if ((st & kFromActuation) && (rc = (a.M.nf > 0 || a.M.nft > 0 || a.M.ne > 0 || a.M.nlb > 0 || a.M.nlt > 0) ? launch_phase<REAL, MJH_KERNEL_SOL_GEN>(m, a, stream) : launch_phase<REAL, MJH_KERNEL_SOL>(m, a, stream))) return rc;  // (MJH_STAGE_ACTUATION: _acceleration's solve lives at the head of the solver phase)
   return 0;
 }
 
@@ -1112,9 +1158,9 @@ int run(const mjhModel* m, const DevModel<REAL>& M, const mjhData* in, mjhData* 
   a.warm_src = a.in.qacc_warmstart;
   a.stamps = g_stamps;
   if (!a.in.qpos || !a.in.qvel) return fail(-22, "in.qpos and in.qvel are required");
-  if ((a.stages & 0x60) && !(fin.qM && fin.qLD && fin.qfrc_smooth)) return fail(-22, "the solver phase reads out.qM / out.qLD: both leaves are required");
-  if (M.ncon > 0 && M.nefc > 0 && (a.stages & 0x40) && !fin.contact_dist) return fail(-22, "the solver phase reads out.contact_dist (active-contact row compaction): the leaf is required");
-  if (M.ncvxpair > 0 && (a.stages & 0x7c) && !(fin.contact_dist && fin.contact_pos && fin.contact_frame && fin.geom_xpos && fin.geom_xmat))
+  if ((a.stages & kFromActuation) && !(fin.qM && fin.qLD && fin.qfrc_smooth)) return fail(-22, "the solver phase reads out.qM / out.qLD: both leaves are required");
+  if (M.ncon > 0 && M.nefc > 0 && (a.stages & MJH_STAGE_SOLVE) && !fin.contact_dist) return fail(-22, "the solver phase reads out.contact_dist (active-contact row compaction): the leaf is required");
+  if (M.ncvxpair > 0 && (a.stages & kFromCollision) && !(fin.contact_dist && fin.contact_pos && fin.contact_frame && fin.geom_xpos && fin.geom_xmat))
     return fail(-22, "models with convex pairs need out.geom_xpos/geom_xmat and out.contact_dist/pos/frame");
   hipStream_t s = (hipStream_t)stream;
   REAL* w = (REAL*)work;
@@ -1122,7 +1168,7 @@ int run(const mjhModel* m, const DevModel<REAL>& M, const mjhData* in, mjhData* 
     if (work) { a.hs = w; a.hs_reals = (int)m->hs_reals; }
     w += m->hs_reals * B;
   }
-  if (m->cand_reals > 0 && (a.stages & 0x7c)) {  // max_contact_points over box / mesh pairs: the candidates live at the head of the workspace
+  if (m->cand_reals > 0 && (a.stages & kFromCollision)) {  // max_contact_points over box / mesh pairs: the candidates live at the head of the workspace
     if (!work) return fail(-22, "max_contact_points with box / mesh pairs needs a workspace of mjh_model_work_bytes(m) * B bytes");
     a.cand = w;
     w += m->cand_reals * B;
@@ -1181,7 +1227,7 @@ int run_inverse(const mjhModel* m, const DevModel<REAL>& M, const mjhData* in, m
   if (!qfrc_inverse || !o.qfrc_constraint || !o.qM || !o.qLD || !o.qfrc_bias || !o.qfrc_passive) return fail(-22, "inverse: qfrc_inverse and out.qfrc_constraint / qM / qLD / qfrc_bias / qfrc_passive are required");
   if (M.nefc > 0 && !(o.efc_J && o.efc_D && o.efc_aref && o.efc_force)) return fail(-22, "inverse: out.efc_J / efc_D / efc_aref / efc_force are required");
   // (the hand-over workspace of the register solver is not used: no solver runs.  A workspace is needed only for the max_contact_points candidates, which it holds at its head)
-  int rc = run<REAL>(m, M, in, out, m->cand_reals > 0 ? work : nullptr, B, flags & MJH_FLAG_FIXED_ITERATIONS, 0, 0x1F, stream);
+  int rc = run<REAL>(m, M, in, out, m->cand_reals > 0 ? work : nullptr, B, flags & MJH_FLAG_FIXED_ITERATIONS, 0, kUpToVelocity, stream);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   InvArgs<REAL> ia;
@@ -1194,13 +1240,12 @@ int run_inverse(const mjhModel* m, const DevModel<REAL>& M, const mjhData* in, m
   ia.discrete = (discrete && M.integrator == INT_EULER && !(M.disableflags & DSBL_EULERDAMP) && m->any_damping) ? 1 : 0;
   ia.lanes = m->inv_lanes; ia.envs = m->inv_envs; ia.chunk = m->inv_chunk; ia.lds_env = m->inv_lds_env;
   const size_t lds = (size_t)ia.envs * ia.lds_env * sizeof(REAL);
-  for (int64_t e0 = 0; e0 < B; e0 += ia.envs * max_grid()) {  // (no grid-stride loop: one launch per 2^20 workgroups)
-    const int64_t n = B - e0 < ia.envs * max_grid() ? B - e0 : ia.envs * max_grid();
-    ia.env_begin = e0; ia.env_count = n;
-    hipLaunchKernelGGL((mjh_inverse_kernel<REAL>), dim3((unsigned)((n + ia.envs - 1) / ia.envs)), dim3(256), lds, s, ia);
-    HIP_TRY(hipGetLastError());
-  }
-  timing_mark(s, 20);
+  if ((rc = launch_cut(B, ia.envs, [&](int64_t first, int64_t n, unsigned grid) {
+         ia.env_begin = first; ia.env_count = n;
+         hipLaunchKernelGGL((mjh_inverse_kernel<REAL>), dim3(grid), dim3(256), lds, s, ia);
+       })))
+    return rc;
+  timing_mark(s, MJH_KERNEL_INVERSE);
   if (M.nsensor > 0 && o.sensordata) {  // sensor_pos / sensor_vel / sensor_acc: leaves this call does not write (actuator_force, qfrc_actuator) are the caller's
     KArgs<REAL> a;
     memset(&a, 0, sizeof(a));
@@ -1210,10 +1255,9 @@ int run_inverse(const mjhModel* m, const DevModel<REAL>& M, const mjhData* in, m
     if (!a.cur.actuator_force) a.cur.actuator_force = a.in.actuator_force;
     if (!a.cur.qfrc_actuator) a.cur.qfrc_actuator = a.in.qfrc_actuator;
     a.fin = state_of(o);
-    a.B = B; a.flags = flags; a.do_step = 0; a.stages = 0x1F; a.rk_stage = -1; a.state_from_cur = 0;
+    a.B = B; a.flags = flags; a.do_step = 0; a.stages = kUpToVelocity; a.rk_stage = -1; a.state_from_cur = 0;
     a.warm_src = a.in.qacc_warmstart;
     if ((rc = launch_sensor_kernel<REAL>(m, a, s))) return rc;
-    timing_mark(s, 11);
   }
   return 0;
 }
@@ -1246,14 +1290,12 @@ int run_ray(const mjhModel* m, const DevModel<REAL>& M, const void* geom_xpos, c
   if (chunk < 1) chunk = 1;
   a.chunk = (int)chunk;
   const size_t lds = c->ncand > 0 ? (size_t)(span * chunk * 12 * (int64_t)sizeof(REAL)) : 0;
-  const int64_t total = B * R, cap = (int64_t)MJH_RAY_WG * max_grid();
-  for (int64_t q0 = 0; q0 < total; q0 += cap) {  // (no grid-stride loop: one launch per 2^20 workgroups)
-    const int64_t n = total - q0 < cap ? total - q0 : cap;
-    a.env_base = q0 / R; a.r_base = (int)(q0 % R); a.npairs = (int)n;
-    hipLaunchKernelGGL((mjh_ray_kernel<REAL>), dim3((unsigned)((n + MJH_RAY_WG - 1) / MJH_RAY_WG)), dim3(MJH_RAY_WG), lds, s, a);
-    HIP_TRY(hipGetLastError());
-  }
-  timing_mark(s, 21);
+  if (const int rc = launch_cut(B * R, MJH_RAY_WG, [&](int64_t first, int64_t n, unsigned grid) {
+        a.env_base = first / R; a.r_base = (int)(first % R); a.npairs = (int)n;
+        hipLaunchKernelGGL((mjh_ray_kernel<REAL>), dim3(grid), dim3(MJH_RAY_WG), lds, s, a);
+      }))
+    return rc;
+  timing_mark(s, MJH_KERNEL_RAY);
   return 0;
 }
 
@@ -1387,16 +1429,16 @@ static int mjh_model_kernel_io_impl(const mjhModel* m, int kernel, int64_t* read
 }
 int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes) {
   if (!m || !read_write_bytes) return fail(-22, "null argument");
-  if ((kernel == 9) != (m->sol2_nmax != 0) && (kernel == 9 || kernel == 4 || kernel == 6)) return -2;  // the solver phase runs as ONE of kernels 4 / 6 / 9
-  if (kernel == 17) { if (!m->kcv2) return -2; const bool prev = g_io_inner; g_io_inner = true; const int rc = mjh_model_kernel_io(m, 13, read_write_bytes); g_io_inner = prev; return rc; }  // the two-wave form of kernel 13 moves the same bytes
-  if (kernel == 13 && !m->fuse_kcv) return -2;  // (a model with kernel 13 reports both accounts: which one a step launches depends on the batch)
-  if ((kernel == 12) != (m->fuse_kv != 0) && (kernel == 12 || kernel == 0 || kernel == 3)) return -2;  // kinematics + velocity: ONE kernel (12) or two (0, 3)
+  if ((kernel == MJH_KERNEL_SOL2) != (m->sol2_nmax != 0) && (kernel == MJH_KERNEL_SOL2 || kernel == MJH_KERNEL_SOL || kernel == MJH_KERNEL_SOL_GEN)) return -2;  // the solver phase runs as ONE of kernels 4 / 6 / 9
+  if (kernel == MJH_KERNEL_KCV2) return m->kcv2 ? mjh_model_kernel_io_impl(m, MJH_KERNEL_KCV, read_write_bytes) : -2;  // the two-wave form of kernel 13 moves the same bytes
+  if (kernel == MJH_KERNEL_KCV && !m->fuse_kcv) return -2;  // (a model with kernel 13 reports both accounts: which one a step launches depends on the batch)
+  if ((kernel == MJH_KERNEL_KV) != (m->fuse_kv != 0) && (kernel == MJH_KERNEL_KV || kernel == MJH_KERNEL_KIN || kernel == MJH_KERNEL_VEL)) return -2;  // kinematics + velocity: ONE kernel (12) or two (0, 3)
   const bool f64 = m->dtype == MJH_F64;
   const bool rk4 = (f64 ? m->m64.integrator : m->m32.integrator) == INT_RK4;
   auto io_of = [&](int k, int64_t* a) -> int {  // RK4: the mean over the four stage launches of a step (the sensor kernel runs once)
     int64_t b[2] = {0, 0};
     int rc = f64 ? mjh_kernel_io<double>(m->m64, k, 1, &a[0], &a[1]) : mjh_kernel_io<float>(m->m32, k, 1, &a[0], &a[1]);
-    if (rc == 0 && rk4 && k != 11) {
+    if (rc == 0 && rk4 && k != MJH_KERNEL_SENSOR) {
       rc = f64 ? mjh_kernel_io<double>(m->m64, k, 2, &b[0], &b[1]) : mjh_kernel_io<float>(m->m32, k, 2, &b[0], &b[1]);
       if (g_io_stage == 2) { a[0] = b[0]; a[1] = b[1]; }                      // the stage kernel: launches of stages 1..3 only
       else if (m->fuse_stage) {}                                               // ... whose model launches kernels 13 / 8 / 9 in stage 0 only
@@ -1405,72 +1447,73 @@ int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes
     return rc;
   };
   int64_t a[2] = {0, 0};
-  if (kernel == 20) {  // the inverse-dynamics tail (mjh_inverse): efc_J and qM once, efc_D / efc_aref, qacc, qfrc_bias / passive in; efc_force, qfrc_constraint, qfrc_inverse out.
+  if (kernel == MJH_KERNEL_INVERSE) {  // the inverse-dynamics tail (mjh_inverse): efc_J and qM once, efc_D / efc_aref, qacc, qfrc_bias / passive in; efc_force, qfrc_constraint, qfrc_inverse out.
     // (the discrete branch reads qM a second time and the factor's lower triangle: not counted, it depends on the call's flags)
     const int64_t R = f64 ? 8 : 4, nv = f64 ? m->m64.nv : m->m32.nv, nefc = f64 ? m->m64.nefc : m->m32.nefc;
     read_write_bytes[0] = (nefc * nv + 2 * nefc + nv * nv + 3 * nv) * R;
     read_write_bytes[1] = (nefc + 2 * nv) * R;
     return 0;
   }
-  if (kernel == 16) {  // the whole pass in one launch: the accounts of kernels 13 and 14 (what the second half reads of the first it still reads from the leaves)
+  if (kernel == MJH_KERNEL_PASS) {  // the whole pass in one launch: the accounts of kernels 13 and 14 (what the second half reads of the first it still reads from the leaves)
     if (!m->fuse_all) return -2;
     int64_t a13[2] = {0, 0}, a14[2] = {0, 0};
     const mjhModel* mm = m;
-    if (mjh_model_kernel_io_impl(mm, 13, a13) != 0 || mjh_model_kernel_io_impl(mm, 14, a14) != 0) return -2;
+    if (mjh_model_kernel_io_impl(mm, MJH_KERNEL_KCV, a13) != 0 || mjh_model_kernel_io_impl(mm, MJH_KERNEL_CS, a14) != 0) return -2;
     read_write_bytes[0] = a13[0] + a14[0]; read_write_bytes[1] = a13[1] + a14[1];
     return 0;
   }
-  if (kernel == 18) {  // one RK4 stage in one launch: the stage accounts of kernel 13, the constraint phase and the register solver (what a part reads of the previous one it still reads from the workspace leaves)
+  if (kernel == MJH_KERNEL_STAGE) {  // one RK4 stage in one launch: the stage accounts of kernel 13, the constraint phase and the register solver (what a part reads of the previous one it still reads from the workspace leaves)
     if (!m->fuse_stage) return -2;
     int64_t a13[2] = {0, 0}, a8[2] = {0, 0}, a9[2] = {0, 0};
     const int prev = g_io_stage;
     g_io_stage = 2;
-    const int rc = (mjh_model_kernel_io_impl(m, 13, a13) != 0 || mjh_model_kernel_io_impl(m, 8, a8) != 0 || mjh_model_kernel_io_impl(m, 9, a9) != 0) ? -2 : 0;
+    const int rc = (mjh_model_kernel_io_impl(m, MJH_KERNEL_KCV, a13) != 0 || mjh_model_kernel_io_impl(m, MJH_KERNEL_CON_DIRECT, a8) != 0 || mjh_model_kernel_io_impl(m, MJH_KERNEL_SOL2, a9) != 0) ? -2 : 0;
     g_io_stage = prev;
     if (rc) return rc;
     read_write_bytes[0] = a13[0] + a8[0] + a9[0]; read_write_bytes[1] = a13[1] + a8[1] + a9[1];
     return 0;
   }
-  if (kernel == 19) {  // the tail of a pass in one launch: the accounts of the constraint phase and the register solver
+  if (kernel == MJH_KERNEL_TAIL) {  // the tail of a pass in one launch: the accounts of the constraint phase and the register solver
     if (!m->fuse_tail) return -2;
     int64_t a8[2] = {0, 0}, a9[2] = {0, 0};
-    if (mjh_model_kernel_io_impl(m, 8, a8) != 0 || mjh_model_kernel_io_impl(m, 9, a9) != 0) return -2;
+    if (mjh_model_kernel_io_impl(m, MJH_KERNEL_CON_DIRECT, a8) != 0 || mjh_model_kernel_io_impl(m, MJH_KERNEL_SOL2, a9) != 0) return -2;
     read_write_bytes[0] = a8[0] + a9[0]; read_write_bytes[1] = a8[1] + a9[1];
     return 0;
   }
-  if ((kernel == 13 || kernel == 14) && m->fuse_all && !g_io_inner) return -2;
-  if (kernel == 14) {  // constraint stage + register solver: the two accounts minus what stays in the arena between them -- the dense rows of efc_J, efc_D / efc_aref, one entry per single-column row, qvel
+  if ((kernel == MJH_KERNEL_KCV || kernel == MJH_KERNEL_CS) && m->fuse_all && !g_io_inner) return -2;
+  if (kernel == MJH_KERNEL_CS) {  // constraint stage + register solver: the two accounts minus what stays in the arena between them -- the dense rows of efc_J, efc_D / efc_aref, one entry per single-column row, qvel
     if (!m->fuse_cs) return -2;
     int64_t k2[2] = {0, 0}, k4[2] = {0, 0};
-    if (io_of(2, k2) != 0 || io_of(4, k4) != 0) return -2;
+    if (io_of(MJH_KERNEL_CON, k2) != 0 || io_of(MJH_KERNEL_SOL, k4) != 0) return -2;
     const int64_t R = f64 ? 8 : 4, nv = f64 ? m->m64.nv : m->m32.nv, nefc = f64 ? m->m64.nefc : m->m32.nefc, nl = f64 ? m->m64.nl : m->m32.nl;
     read_write_bytes[0] = k2[0] + k4[0] - ((nefc - nl) * nv + 2 * nefc + nl + nv) * R;
     read_write_bytes[1] = k2[1] + k4[1];
     return 0;
   }
-  if ((kernel == 2 || kernel == 9) && m->fuse_cs) return -2;  // (a full pass of this model launches kernel 14 instead)
-  if (kernel == 12 || kernel == 13) {  // the accounts of the fused stages minus what stays in the arena between them: qpos, cdof, cinert, subtree_com, xipos are not read back (13: nor cinert, cdof by the crb stage)
+  if ((kernel == MJH_KERNEL_CON || kernel == MJH_KERNEL_SOL2) && m->fuse_cs) return -2;  // (a full pass of this model launches kernel 14 instead)
+  if (kernel == MJH_KERNEL_KV || kernel == MJH_KERNEL_KCV) {  // the accounts of the fused stages minus what stays in the arena between them: qpos, cdof, cinert, subtree_com, xipos are not read back (13: nor cinert, cdof by the crb stage)
     int64_t k0[2] = {0, 0}, k3[2] = {0, 0}, k1[2] = {0, 0};
-    if (io_of(0, k0) != 0 || io_of(3, k3) != 0 || (kernel == 13 && io_of(1, k1) != 0)) return -2;
+    if (io_of(MJH_KERNEL_KIN, k0) != 0 || io_of(MJH_KERNEL_VEL, k3) != 0 || (kernel == MJH_KERNEL_KCV && io_of(MJH_KERNEL_CRB, k1) != 0)) return -2;
     const int64_t R = f64 ? 8 : 4, nq = f64 ? m->m64.nq : m->m32.nq, nv = f64 ? m->m64.nv : m->m32.nv, nb = f64 ? m->m64.nbody : m->m32.nbody;
-    read_write_bytes[0] = k0[0] + k3[0] - (nq + 6 * nv + 10 * nb + 3 * nb + 3 * nb) * R + (kernel == 13 ? k1[0] - (10 * nb + 6 * nv) * R : 0);
-    read_write_bytes[1] = k0[1] + k3[1] + (kernel == 13 ? k1[1] : 0);
+    read_write_bytes[0] = k0[0] + k3[0] - (nq + 6 * nv + 10 * nb + 3 * nb + 3 * nb) * R + (kernel == MJH_KERNEL_KCV ? k1[0] - (10 * nb + 6 * nv) * R : 0);
+    read_write_bytes[1] = k0[1] + k3[1] + (kernel == MJH_KERNEL_KCV ? k1[1] : 0);
     return 0;
   }
-  const int k = kernel == 9 ? 4 : kernel;  // the register solver moves the same leaves as the plain LDS solver
+  const int k = kernel == MJH_KERNEL_SOL2 ? MJH_KERNEL_SOL : kernel;  // the register solver moves the same leaves as the plain LDS solver
   if (io_of(k, a) != 0) return -2;  // -2: this model's step does not launch that kernel
   read_write_bytes[0] = a[0]; read_write_bytes[1] = a[1];
   return 0;
 }
 
 int64_t mjh_model_work_bytes(const mjhModel* m) { return m ? m->work_reals * (m->dtype == MJH_F64 ? 8 : 4) : 0; }
-int mjh_model_lds_bytes(const mjhModel* m, int phase) {  // phase 5: the register solver's arena; 16 / 17 / 18: its packed first tier, the fused kinematics + crb + velocity kernel, the fused constraint + solver kernel (per environment)
+int mjh_model_lds_bytes(const mjhModel* m, int arena) {  // the query numbers of include/mjhip.h: 0..5 the arenas carved per model, 16..19 the others
   if (!m) return 0;
-  if (phase == 16) return m->lds_tier;
-  if (phase == 17) return m->lds_kcv;
-  if (phase == 18) return m->lds_cs;
-  if (phase == 19) return m->lds_kcv2;
-  return (phase >= 0 && phase < MJH_NARENA) ? m->lds_bytes[phase] : 0;
+  if (arena >= 0 && arena < MJH_NARENA) return m->lds((Arena)arena);
+  if (arena == 16) return m->lds(AR_TIER);
+  if (arena == 17) return m->lds(AR_KCV);
+  if (arena == 18) return m->lds(AR_CS);
+  if (arena == 19) return m->lds(AR_KCV2);
+  return 0;
 }
 const char* mjh_last_error(void) { return g_err.c_str(); }
 int mjh_abi_version(void) { return MJH_ABI_VERSION; }
