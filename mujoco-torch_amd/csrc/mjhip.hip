@@ -5,6 +5,7 @@
 // the binding (ctypes) passes raw device pointers.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -81,6 +82,9 @@ struct ArenaLds {
   int bytes;   // ... and its size per environment
 };
 
+// A real Data leaf in the RK4 stage workspace: not there, there with its slot in the stage Data, or there with the slot left NULL (the space is still taken)
+enum StageLeaf : unsigned char { STAGE_NONE, STAGE_SLOT, STAGE_SPACE };
+
 struct mjhModel {
   int dtype;
   void* blob;          // device allocation holding every table
@@ -112,6 +116,7 @@ struct mjhModel {
   int64_t hs_reals = 0;                    // ... of which the constraint phase's hand-over to the register solver (KArgs::hs): small models with one contact condim
   int64_t cand_reals = 0;                  // ... of which the candidate contacts (at the HEAD of the workspace: its first B * cand_reals reals; the RK4 stage Data and sums follow)
   std::vector<int64_t> leaf_count;         // per-env element count of every real Data leaf, ABI order
+  std::vector<StageLeaf> stage_leaf;       // ... and its part in the RK4 stage workspace (RK4 models)
   DevModel<double> m64;
   DevModel<float> m32;
 };
@@ -149,6 +154,15 @@ hipError_t allow_lds(F* kernel, int bytes) {
 template <typename REAL, int P, int W>
 hipError_t allow_phase_lds(const mjhModel* m) {
   return allow_lds(&mjh_phase_kernel<REAL, P, W>, MJH_WAVE / W * m->lds(phase_kernel(P).arena));
+}
+// ... at every width launch_phase runs it at: one environment per wavefront, and two / four where the packing flags of its arena say so
+template <typename REAL, int P>
+hipError_t allow_phase_lds_packed(const mjhModel* m) {
+  constexpr PhaseKernel K = phase_kernel(P);
+  hipError_t e = allow_phase_lds<REAL, P, MJH_WAVE>(m);
+  if constexpr (K.max_envs > 1) if (!e && m->pack2[K.pack]) e = allow_phase_lds<REAL, P, 32>(m);
+  if constexpr (K.max_envs == 4) if (!e && m->pack4[K.pack]) e = allow_phase_lds<REAL, P, 16>(m);
+  return e;
 }
 // ... for every instantiation of register-solver form `wt`
 template <typename REAL>
@@ -209,10 +223,51 @@ bool is_stage_leaf(const char* name, bool has_convex, bool has_fluid, bool has_e
   return false;
 }
 
+// The library's environment switches: measurement aids, each turning a measured default the other way.  Read once, at the first model creation.
+bool on(const char* e) { return !(e && e[0] == '0'); }                              // unset, or anything but "0...": on
+int tri(const char* e) { return !e ? -1 : (e[0] == '1' ? 1 : 0); }                  // -1: unset (the default), 1: forced on, 0: off
+int mask12(const char* e) { return e ? (int)(strtol(e, nullptr, 0) & 0xfff) : -1; }  // 12 bits of the workgroup index; -1: unset
+int num(const char* e, int unset) { return e ? atoi(e) : unset; }
+struct Switches {
+  bool all_handoff = on(getenv("MJH_ALL_HANDOFF"));
+  bool lds_diet = on(getenv("MJH_LDS_DIET"));
+  bool pair_cull = on(getenv("MJH_PAIR_CULL"));
+  bool kin_level = on(getenv("MJH_KIN_LEVEL"));
+  bool sol2_mfma = on(getenv("MJH_SOL2_MFMA"));
+  bool sol2_incr = on(getenv("MJH_SOL2_INCR"));
+  bool handover = on(getenv("MJH_HANDOVER"));
+  int kcv2 = tri(getenv("MJH_KCV2"));
+  int fuse_all = tri(getenv("MJH_FUSE_ALL"));
+  bool fuse_stage = on(getenv("MJH_FUSE_STAGE"));
+  bool fuse_stage0 = on(getenv("MJH_FUSE_STAGE0"));
+  bool fuse_tail = on(getenv("MJH_FUSE_TAIL"));
+  bool cs_one = on(getenv("MJH_CS_ONE"));
+  int xswap = mask12(getenv("MJH_XSWAP"));  // (an explicit mask applies at every launch size: the bit-identity tests)
+  int xswap_k = mask12(getenv("MJH_XSWAP_K"));
+  int xswap_c = mask12(getenv("MJH_XSWAP_C"));
+  int sensor_epw = num(getenv("MJH_SENSOR_EPW"), 0);  // 0: auto
+  int max_grid_log2 = std::min(std::max(num(getenv("MJH_MAX_GRID_LOG2"), 20), 0), 20);
+};
+const Switches& switches() {
+  static const Switches s;
+  return s;
+}
+
+constexpr int kLdsCu = 160 * 1024;  // the LDS of one CU: the most one workgroup can take (a phase keeps 160 KB / arena environments of a CU in flight: profiles/r01/notes.md)
+constexpr int kLdsWg = 64 * 1024;   // the most dynamic LDS per workgroup the packed, fused and solver forms are planned for (each form's test of whether it serves a model)
+
+// carves `arena` for phase bit `phase_bit` from the flags of M (the model's DevModel, or a copy of it with the register solver's first-tier row cap); returns its bytes per environment
 template <typename REAL>
-int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
-  BlobBuilder bb;
-  std::vector<std::pair<const void**, size_t>> fix;  // (pointer slot, offset)
+int carve(mjhModel* out, Arena arena, const DevModel<REAL>& M, int phase_bit, int* kv_defer_ok = nullptr) {
+  ArenaLds& ar = out->arena[arena];
+  return ar.bytes = lds_carve(M, phase_bit, ar.off, kv_defer_ok) * (int)sizeof(REAL);
+}
+
+using Fixups = std::vector<std::pair<const void**, size_t>>;  // (pointer slot of DevModel, offset in the blob)
+
+// ---- tables: the model copied into DevModel and the blob, and the topology, row, transmission and sensor tables derived from it (no kernel choice) ----
+template <typename REAL>
+int tables(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M, BlobBuilder& bb, Fixups& fix) {
   memset(&M, 0, sizeof(M));
 #define X(n) M.n = d->n;
   MJH_MODEL_INTS(X)
@@ -223,16 +278,9 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
   M.wind[0] = (REAL)d->wind_x; M.wind[1] = (REAL)d->wind_y; M.wind[2] = (REAL)d->wind_z;
   M.magnetic[0] = (REAL)d->magnetic_x; M.magnetic[1] = (REAL)d->magnetic_y; M.magnetic[2] = (REAL)d->magnetic_z;
   M.has_fluid = (d->density > 0) || (d->viscosity > 0) || (d->wind_x != 0) || (d->wind_y != 0) || (d->wind_z != 0);
-  M.has_gravcomp = 0;
   M.con_general = (d->nf > 0 || d->nft > 0 || d->ne > 0 || d->nlb > 0 || d->nlt > 0 || d->topk) ? 1 : 0;
   if (d->nft > 0 && d->nf + d->nl + d->nft > 64) return fail(-38, "frictionloss rows beyond the first 64 solver rows are not supported");
   for (int b = 0; b < d->nbody; b++) if (d->body_gravcomp[b] != 0) M.has_gravcomp = 1;
-  {
-    // measured on MI355X (profiles/r02/notes.md): ant (nv 8) constraint phase 127 -> 112 us, mesh scene 58 -> 54 us; the humanoid (nv 27) is
-    // slower that way (43 -> 59 us: every (contact, dof) lane re-reads 27-wide rows through L2) and keeps the dense copy in LDS
-    static const int direct_nv = [] { const char* e = getenv("MJH_CON_DIRECT_NV"); return e ? atoi(e) : 16; }();
-    M.con_direct = (d->nv <= direct_nv && !(d->nf > 0 || d->nft > 0 || d->ne > 0 || d->nlb > 0 || d->nlt > 0 || d->topk)) ? 1 : 0;
-  }
   M.gravity[0] = (REAL)d->gravity_x; M.gravity[1] = (REAL)d->gravity_y; M.gravity[2] = (REAL)d->gravity_z;
   M.meaninertia = d->meaninertia; M.tolerance = d->tolerance; M.ls_tolerance = d->ls_tolerance;
 #define X(n) fix.push_back({(const void**)&M.n, bb.add(d->n, sizeof(int32_t) * (size_t)d->len_##n)});
@@ -252,16 +300,7 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
   const int NW = nv > 64 ? (nv + 63) / 64 : 1;  // 64-bit words per dof mask
   M.mask_words = NW;
   M.big = nv > 64 ? 1 : 0;
-  {
-    static const bool ho_off = [] { const char* e = getenv("MJH_ALL_HANDOFF"); return e && e[0] == '0'; }();
-    M.all_handoff = (!ho_off && d->ngeom <= 32 && d->nbody <= 32 && nv <= 32) ? 1 : 0;
-  }
-  {  // small plain models (the ones that run four environments per wavefront, no optional physics): a leaner arena (DevModel::lds_diet).  MJH_LDS_DIET=0: off
-    static const bool diet_off = [] { const char* e = getenv("MJH_LDS_DIET"); return e && e[0] == '0'; }();
-    M.lds_diet = (!diet_off && d->nbody <= 16 && d->njnt <= 16 && nv <= 16 && !M.has_fluid && !M.has_gravcomp && d->ntendon == 0) ? 1 : 0;
-  }
   if (M.big) M.con_general = 1;  // the general constraint kernel (7) reads multi-word masks; so does the optional-physics velocity kernel (5)
-  if (M.big) M.con_direct = 0;
   std::vector<int> depth(nb, 0), sub_end(nb, 0);
   int max_depth = 1;
   for (int b = 1; b < nb; b++) {
@@ -392,8 +431,6 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
       pcull[2 * p] = (REAL)(reach * reach); pcull[2 * p + 1] = (REAL)(r1 + r2);
     }
     fix.push_back({(const void**)&M.pair_cull, bb.add(pcull.data(), sizeof(REAL) * pcull.size())});
-    static const bool cull_off = [] { const char* e = getenv("MJH_PAIR_CULL"); return e && e[0] == '0'; }();  // MJH_PAIR_CULL=0: RK4 stages 1..3 narrow-phase every pair like stage 0
-    M.pair_cull_on = cull_off ? 0 : 1;
   }
   {
     int max_jnt = 1;
@@ -409,10 +446,6 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
         }
       }
     M.max_jnt = max_jnt;
-    {  // the level sweep (Env::kinematics): same operations per body as the walk, bit-identical; MJH_KIN_LEVEL=0 keeps the walk (A / B runs)
-      static const int lv = [] { const char* e = getenv("MJH_KIN_LEVEL"); return e ? (e[0] != '0') : 1; }();
-      M.kin_lvl = (lv && nb > 1 && nb <= 32) ? 1 : 0;  // (nb <= 32: one body per lane in EVERY instantiation the model can run at -- 16 lanes per environment only with nbody <= 16, else 32 or 64 -- so that which kernel a batch size or an odd tail selects never changes a bit)
-    }
     fix.push_back({(const void**)&M.chain_dof, bb.add(chain_dof.data(), sizeof(int) * chain_dof.size())});
     fix.push_back({(const void**)&M.chain_jnt, bb.add(chain_jnt.data(), sizeof(int) * chain_jnt.size())});
   }
@@ -547,13 +580,6 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
   }
   fix.push_back({(const void**)&M.dof_limrow, bb.add(dof_limrow.data(), sizeof(int) * dof_limrow.size())});
   M.max_depth = max_depth;
-  M.sol_qm_lds = (d->nefc > 0 && d->iterations > 4) ? 1 : 0;  // one pass over qM per solver iteration: from LDS when there are many
-  {  // register solver, Newton, float32: J^T diag(w) J on the matrix cores (v_mfma_f32_4x4x1, 16 independent 4 x 4 blocks: each environment's lanes feed only their own blocks).  MJH_SOL2_MFMA=0: vector path
-    static const bool mfma_off = [] { const char* e = getenv("MJH_SOL2_MFMA"); return e && e[0] == '0'; }();
-    M.sol2_hs = (!mfma_off && sizeof(REAL) == 4 && d->solver == SOL_NEWTON && d->nv <= 16 && d->nefc > 0) ? 1 : 0;
-    static const bool incr_off = [] { const char* e = getenv("MJH_SOL2_INCR"); return e && e[0] == '0'; }();
-    M.sol2_incr = (!incr_off && d->solver == SOL_NEWTON && d->nv <= 16 && d->nefc > 0) ? 1 : 0;
-  }
   // convex pairs and the LDS scratch their wave needs (layout in mjh_convex.h)
   std::vector<int> cvx_pairs;
   int cvx_reals = 0;
@@ -576,75 +602,82 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
   fix.push_back({(const void**)&M.cvx_pairs, bb.add(cvx_pairs.data(), sizeof(int) * cvx_pairs.size())});
   M.ncvxpair = (int)cvx_pairs.size();
   out->cvx_lds_bytes = (cvx_reals + 8) * (int)sizeof(REAL);
-  if (out->cvx_lds_bytes > 64 * 1024) return fail(-12, "convex hull too large for the pair kernel's LDS scratch");
+  if (out->cvx_lds_bytes > kLdsWg) return fail(-12, "convex hull too large for the pair kernel's LDS scratch");
+  for (int i = 0; i < nv; i++) if (d->dof_damping[i] != 0) out->any_damping = 1;
+  out->leaf_count = leaf_counts(d);
+  return 0;
+}
+
+// ---- plan: every choice of path, arena, packing, solver tier and fusion that serves the model, and the workspace they need (no HIP call) ----
+template <typename REAL>
+int plan(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
+  const Switches& sw = switches();
+  const int nv = d->nv;
+  // measured on MI355X (profiles/r02/notes.md): ant (nv 8) constraint phase 127 -> 112 us, mesh scene 58 -> 54 us; the humanoid (nv 27) is
+  // slower that way (43 -> 59 us: every (contact, dof) lane re-reads 27-wide rows through L2) and keeps the dense copy in LDS
+  M.con_direct = (nv <= 16 && !M.con_general) ? 1 : 0;
+  M.all_handoff = (sw.all_handoff && d->ngeom <= 32 && d->nbody <= 32 && nv <= 32) ? 1 : 0;
+  // small plain models (the ones that run four environments per wavefront, no optional physics): a leaner arena (DevModel::lds_diet).  MJH_LDS_DIET=0: off
+  M.lds_diet = (sw.lds_diet && d->nbody <= 16 && d->njnt <= 16 && nv <= 16 && !M.has_fluid && !M.has_gravcomp && d->ntendon == 0) ? 1 : 0;
+  M.pair_cull_on = sw.pair_cull ? 1 : 0;  // MJH_PAIR_CULL=0: RK4 stages 1..3 narrow-phase every pair like stage 0
+  // the level sweep (Env::kinematics): same operations per body as the walk, bit-identical; MJH_KIN_LEVEL=0 keeps the walk (A / B runs)
+  M.kin_lvl = (sw.kin_level && d->nbody > 1 && d->nbody <= 32) ? 1 : 0;  // (nb <= 32: one body per lane in EVERY instantiation the model can run at -- 16 lanes per environment only with nbody <= 16, else 32 or 64 -- so that which kernel a batch size or an odd tail selects never changes a bit)
+  M.sol_qm_lds = (d->nefc > 0 && d->iterations > 4) ? 1 : 0;  // one pass over qM per solver iteration: from LDS when there are many
+  // register solver, Newton, float32: J^T diag(w) J on the matrix cores (v_mfma_f32_4x4x1, 16 independent 4 x 4 blocks: each environment's lanes feed only their own blocks).  MJH_SOL2_MFMA=0: vector path
+  M.sol2_hs = (sw.sol2_mfma && sizeof(REAL) == 4 && d->solver == SOL_NEWTON && nv <= 16 && d->nefc > 0) ? 1 : 0;
+  M.sol2_incr = (sw.sol2_incr && d->solver == SOL_NEWTON && nv <= 16 && d->nefc > 0) ? 1 : 0;
 
   for (int p = 0; p < MJH_NARENA; p++) {
-    ArenaLds& ar = out->arena[p];
-    ar.bytes = lds_carve(M, 1 << p, ar.off) * (int)sizeof(REAL);
-    if (p == AR_SOL && ar.bytes > 160 * 1024 && M.sol_qm_lds) {  // a large model: qM stays in global memory (L2) for the solver's products
+    carve(out, (Arena)p, M, 1 << p);
+    if (p == AR_SOL && out->lds(AR_SOL) > kLdsCu && M.sol_qm_lds) {  // a large model: qM stays in global memory (L2) for the solver's products
       M.sol_qm_lds = 0;
-      ar.bytes = lds_carve(M, 1 << p, ar.off) * (int)sizeof(REAL);
+      carve(out, AR_SOL, M, 1 << p);
     }
-    if (p < MJH_NPHASE && ar.bytes > 160 * 1024) return fail(-12, "model does not fit the 160 KiB LDS of one CU");
+    if (p < MJH_NPHASE && out->lds((Arena)p) > kLdsCu) return fail(-12, "model does not fit the 160 KiB LDS of one CU");
   }
   {  // register solver: CG, slide / hinge limit rows + contact rows only, one dof per lane of a 32-lane half
-    static const bool off = [] { const char* e = getenv("MJH_SOL2"); return e && e[0] == '0'; }();
     const int nd = d->nefc - d->nf - d->nl;
     const bool general = d->nf > 0 || d->nft > 0 || d->ne > 0 || d->nlb > 0 || d->nlt > 0;
-    out->sol2_nmax = out->sol2_rpl = 0;
-    const int nmax = d->nv <= 8 ? 8 : (d->nv <= 16 ? 16 : 28), rpl = nd <= 32 ? 1 : (nd <= 64 ? 2 : (nd <= 128 ? 4 : 8));
+    const int nmax = nv <= 8 ? 8 : (nv <= 16 ? 16 : 28), rpl = nd <= 32 ? 1 : (nd <= 64 ? 2 : (nd <= 128 ? 4 : 8));
     // Newton (Hessian built and factorised in registers): two environments per wavefront run until BOTH have converged, which pays
     // when the solves are short -- measured on MI355X: ant (nv 8, 1 - 3 iterations) solver phase 229 -> 175 us, mesh scene (nv 12, up to
-    // 100 iterations x 50 line-search steps, very uneven across environments) 548 -> 691 us.  MJH_SOL2_NEWTON_NV moves the cut.
-    static const int newton_nv = [] { const char* e = getenv("MJH_SOL2_NEWTON_NV"); return e ? atoi(e) : 8; }();
+    // 100 iterations x 50 line-search steps, very uneven across environments) 548 -> 691 us.
     // (... with FOUR environments per wavefront -- the first tier of models whose nv, na and single-column rows fit 16 lanes, see below -- the shared
     // nv-sized work outweighs the wait: the mesh scene's solver phase 338 -> see profiles/r03/notes.md)
-    static const bool w16_off = [] { const char* e = getenv("MJH_SOL2_W16"); return e && e[0] == '0'; }();
-    const bool w16 = !w16_off && nmax <= 16 && d->nv <= 16 && d->na <= 16 && d->nl <= 16;
-    const bool solver_ok = d->solver == SOL_CG || (d->solver == SOL_NEWTON && nmax <= 16 && (d->nv <= newton_nv || w16));
-    if (!off && solver_ok && !general && d->nv <= 28 && nd <= 32 * (nmax <= 16 ? 8 : 2) && d->nl <= 32 && d->na <= 32 && d->nq <= 64 && 2 * out->lds(AR_SOL2) <= 64 * 1024) {
+    const bool w16 = nv <= 16 && d->na <= 16 && d->nl <= 16;
+    const bool solver_ok = d->solver == SOL_CG || (d->solver == SOL_NEWTON && (nv <= 8 || w16));
+    if (solver_ok && !general && nv <= 28 && nd <= 32 * (nmax <= 16 ? 8 : 2) && d->nl <= 32 && d->na <= 32 && d->nq <= 64 && 2 * out->lds(AR_SOL2) <= kLdsWg) {
       out->sol2_nmax = nmax;
       out->sol2_rpl = rpl;
-      // measured on MI355X (profiles/r02/notes.md): ant solver phase 124 -> 114 us (the narrow tier runs three waves per SIMD).  MJH_SOL2_TIERS=0 keeps the single full-width launch.
-      static const bool tiers_off = [] { const char* e = getenv("MJH_SOL2_TIERS"); return e && e[0] == '0'; }();
+      // measured on MI355X (profiles/r02/notes.md): ant solver phase 124 -> 114 us (the narrow tier runs three waves per SIMD).
       // Small models (nv, na and the single-column rows fit 16 lanes): the first tier packs FOUR environments per wavefront.  The solver's nv-sized
       // work (substitutions, Cholesky of the Newton Hessian, M products) costs a wave the same whatever it carries, so its cost per environment
       // halves, and a CU keeps twice the environments in flight.  Row slots of that tier: 2 per lane (32 rows) for contacts of up to 4 rows,
-      // 5 (80 rows) for wider ones (condim 6 pyramidal: 10 rows per contact).  MJH_SOL2_W16=0 keeps two per wavefront; MJH_SOL2_W16_RPL picks the slots.
-      static const int w16_rpl_env = [] { const char* e = getenv("MJH_SOL2_W16_RPL"); return e ? atoi(e) : 0; }();
-      const int w16_rpl = (w16_rpl_env == 2 || w16_rpl_env == 5) ? w16_rpl_env : ((M.con_rows > 0 && M.con_rows <= 4) || nd <= 32 ? 2 : 5);
+      // 5 (80 rows) for wider ones (condim 6 pyramidal: 10 rows per contact).
+      const int w16_rpl = ((M.con_rows > 0 && M.con_rows <= 4) || nd <= 32) ? 2 : 5;
+      DevModel<REAL> Mc = M;
       if (w16) {
-        DevModel<REAL> Mc = M;
         Mc.sol2_row_cap = 16 * w16_rpl;
-        out->arena[AR_TIER].bytes = lds_carve(Mc, PH_SOL2, out->arena[AR_TIER].off) * (int)sizeof(REAL);
-        if (4 * out->lds(AR_TIER) <= 64 * 1024) {
+        if (4 * carve(out, AR_TIER, Mc, PH_SOL2) <= kLdsWg) {
           out->sol2_tiers = 1; out->sol2_w16_rpl = w16_rpl;
-          out->sol2_w16_nmax = d->nv <= 8 ? 8 : (d->nv <= 12 ? 12 : 16);
+          out->sol2_w16_nmax = nv <= 8 ? 8 : (nv <= 12 ? 12 : 16);
         }
       }
-      if (!out->sol2_tiers && rpl > 1 && !tiers_off) {
-        DevModel<REAL> Mc = M;
+      if (!out->sol2_tiers && rpl > 1) {
         Mc.sol2_row_cap = 32;
-        out->arena[AR_TIER].bytes = lds_carve(Mc, PH_SOL2, out->arena[AR_TIER].off) * (int)sizeof(REAL);
+        carve(out, AR_TIER, Mc, PH_SOL2);
         out->sol2_tiers = 1;
       }
     }
   }
   {  // constraint stage + register solver in one kernel: plain rows, one dense-row slot per lane, no tiers, nv in (16, 28] (the instantiation that is built).
-     // Measured on the humanoid (MI355X, B = 4096): profiles/r04/notes.md.  MJH_FUSE_CS=0 keeps the two launches.
-    static const bool off = [] { const char* e = getenv("MJH_FUSE_CS"); return e && e[0] == '0'; }();
+     // Measured on the humanoid (MI355X, B = 4096): profiles/r04/notes.md.
     bool mono = true;  // contact rows in contact order (the in-place row compaction walks them upwards)
     for (int c = 1; c < d->ncon; c++) mono = mono && d->con_efc_address[c] > d->con_efc_address[c - 1];
-    out->fuse_cs = 0;
-    if (!off && out->sol2_nmax == 28 && out->sol2_rpl == 1 && !out->sol2_tiers && !M.con_direct && !M.con_general && !M.topk && d->ncon > 0 && d->nefc > 0 && mono &&
-        M.con_rows > 0 && M.ncrow == d->nefc - d->nl && d->nf == 0 && d->nv <= 32 && d->nq <= 64 && d->nl <= 32 && d->na <= 32) {
-      const int reals = lds_carve(M, PH_CS, out->arena[AR_CS].off);
-      if (reals > 0 && 2 * reals * (int)sizeof(REAL) <= 64 * 1024) {
-        out->arena[AR_CS].bytes = reals * (int)sizeof(REAL);
-        out->fuse_cs = 1;
-        HIP_TRY(allow_sol2_lds<REAL>(SOL2_CS, 2 * out->lds(AR_CS)));
-        HIP_TRY(allow_sol2_lds<REAL>(SOL2_CS_ONE, 2 * out->lds(AR_CS)));
-      }
+    if (out->sol2_nmax == 28 && out->sol2_rpl == 1 && !out->sol2_tiers && !M.con_direct && !M.con_general && !M.topk && d->ncon > 0 && d->nefc > 0 && mono &&
+        M.con_rows > 0 && M.ncrow == d->nefc - d->nl && d->nf == 0 && nv <= 32 && d->nq <= 64 && d->nl <= 32 && d->na <= 32) {
+      if (carve(out, AR_CS, M, PH_CS) > 0 && 2 * out->lds(AR_CS) <= kLdsWg) out->fuse_cs = 1;
+      else out->arena[AR_CS].bytes = 0;  // (the carve is negative when the overlays do not work out)
     }
   }
   {  // inverse-dynamics tail (mjh_inverse.h): one environment per 16 / 32 / 64 lanes, 256 lanes per workgroup, LDS_BUDGET bytes per workgroup shared by its environments.
@@ -659,195 +692,179 @@ int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
     if (chunk < 1) return fail(-12, "inverse dynamics: nv too large for the LDS chunk of one environment");
     out->inv_chunk = chunk;
     out->inv_lds_env = (3 * nv + chunk + chunk * nv + 1) & ~1;
-    out->any_damping = 0;
-    for (int i = 0; i < nv; i++) if (d->dof_damping[i] != 0) out->any_damping = 1;
-    HIP_TRY(allow_lds(&mjh_inverse_kernel<REAL>, 64 * 1024));  // (the budget plus the rounding of lds_env)
   }
-  out->leaf_count = leaf_counts(d);
-  out->work_reals = 0;
+  // phases that are register-bound (not LDS-bound) run two environments per wavefront, 32 lanes each: the same
+  // VGPR budget then keeps twice as many environments in flight (mjh_kernels.h, Env<REAL, W>)
+  out->pack2[AR_KIN] = 2 * out->lds(AR_KIN) <= kLdsWg;
+  out->pack2[AR_VEL] = 2 * out->lds(AR_VEL) <= kLdsWg;
+  {  // fused kinematics + velocity kernel (plain velocity phase only).  Measured on MI355X: profiles/r02/notes.md.
+    int defer_ok = 0;
+    carve(out, AR_KV, M, PH_KINVEL, &defer_ok);
+    M.kv_defer = defer_ok;
+    out->fuse_kv = (!(M.has_fluid || M.has_gravcomp || M.ntendon > 0 || M.big) && out->lds(AR_KV) <= kLdsCu) ? 1 : 0;
+  }
+  out->pack2[AR_CON] = M.con_direct && 2 * out->lds(AR_CON) <= kLdsWg;  // plain constraint phase: its contact rows go straight to the leaf, the arena is small enough for two per wavefront
+  // CRB: the register Cholesky keeps one matrix row per lane, so nv <= 32 would fit a 32-lane half too; measured on the float64
+  // humanoid (nv 27) two per wavefront is SLOWER, 50.2 vs 39.9 us (132 VGPRs: 3 waves / SIMD instead of 4, and every broadcast of the
+  // factorisation becomes two v_readlane + a select).  float32 small models: +13 % on the ant (round 1).
+  // (round 4, after the register work of round 3: 35.1 vs 36.5 us, and it is what lets kernel 13 serve the humanoid)
+  out->pack2[AR_CRB] = ((sizeof(REAL) == 4 && nv <= 16) || (nv <= 32 && nv > 16)) && 2 * out->lds(AR_CRB) <= kLdsWg;
+  // small models (every per-body / per-joint / per-dof loop fits 16 lanes): FOUR environments per wavefront in the packed phases.
+  // These phases are bound by the number of dependent chains a SIMD can interleave (registers cap the waves), so the same waves
+  // carrying twice the environments is close to twice the throughput -- measured on the ant (B = 16384, 64 environments per CU):
+  // see profiles/r02/notes.md.
+  if (d->nbody <= 16 && d->njnt <= 16 && nv <= 16)
+    for (const Arena a : {AR_KIN, AR_CRB, AR_VEL}) out->pack4[a] = out->pack2[a] && 4 * out->lds(a) <= kLdsWg;
+  // the fused kinematics + velocity kernel packs where both of its phases do and its own arena fits
+  out->pack2[AR_KV] = out->pack2[AR_KIN] && out->pack2[AR_VEL] && 2 * out->lds(AR_KV) <= kLdsWg;
+  out->pack4[AR_KV] = out->pack4[AR_KIN] && out->pack4[AR_VEL] && 4 * out->lds(AR_KV) <= kLdsWg;
+  {  // kinematics + crb / factor + velocity as ONE kernel (13): when the crb stage packs environments per wavefront the way the other two do (float32 models with
+     // nv <= 16, and every model with 16 < nv <= 32).  Saves the crb kernel's loads of cinert / cdof, its launch and the wait between the launches.
+     // At every batch size (round 4; round 3 had kept the separate launches past one round of waves): the humanoid (two per wavefront) at B = 32768: 652 us against 452 + 218;
+     // the ant (four per wavefront) at B = 16384, two rounds: 93.6 us against 75.8 + 21.8 (profiles/r04/notes.md)
+    carve(out, AR_KCV, M, PH_KCV);
+    const bool same_pack = out->pack2[AR_CRB] == out->pack2[AR_KV] && out->pack4[AR_CRB] == out->pack4[AR_KV];
+    out->fuse_kcv = (out->fuse_kv && same_pack && out->pack2[AR_CRB] && out->lds(AR_KCV) <= kLdsCu && 2 * out->lds(AR_KCV) <= kLdsWg &&
+                     (!out->pack4[AR_CRB] || 4 * out->lds(AR_KCV) <= kLdsWg)) ? 1 : 0;
+  }
+  // kernel 13 on two wavefronts per workgroup (velocity beside crb / factor): packed float32 models.  MJH_KCV2=0 / 1 forces it off / on (also for float64, two per wavefront).
+  if (out->fuse_kcv && sw.kcv2 != 0 && (sw.kcv2 == 1 || (sizeof(REAL) == 4 && out->pack4[AR_CRB]))) {
+    const int per_wg = (out->pack4[AR_CRB] ? 4 : 2) * carve(out, AR_KCV2, M, PH_KCV2);
+    if (per_wg <= kLdsWg) {
+      out->kcv2 = 1;
+      // The two-wave form pays while the whole batch is resident at once: two wavefronts per workgroup at four per SIMD are 8 workgroups per CU (and their arenas must fit the
+      // CU's 160 KB).  Past that it runs more rounds of waves than kernel 13 (which fits 16 one-wave workgroups) and loses.  Measured (MI355X, profiles/r05/notes.md): mesh scene
+      // B = 8192 37.5 us against 46.0; ant B = 8192 46.1 against 54.5; ant B = 16384 (two rounds against one) 101 against 62.
+      // The limit belongs to the device a LAUNCH runs on, not to the one that was current when the model was built: kcv2_limit() below, cached per device.
+      out->kcv2_per_wg = per_wg;
+      out->kcv2_envs_per_wg = out->pack4[AR_CRB] ? 4 : 2;
+      out->kcv2_max_envs = sw.kcv2 == 1 ? ((int64_t)1 << 62) : 0;
+    }
+  }
+  // the whole pass in one kernel: models both fused kernels serve at two environments per wavefront, without convex pairs or sensors (their kernels sit between the two halves).
+  // Measured (MI355X, humanoid B = 4096, three A / B pairs in one call, profiles/r04/notes.md): 166.8 - 170.5 us in one launch against 91.7 - 93.1 + 76.4 - 76.7 in two
+  // (23.5 - 24.3 M against 24.1 - 24.6 M env-steps/s): the one function is allocated 256 VGPRs + 304 B of scratch where the halves take 198 + 0 and 256 + 120 B, and that
+  // costs what the missing device-wide barrier saves.  Opt-in (MJH_FUSE_ALL=1).
+  // Round 5: for models with opt.iterations == 1 (the humanoid benchmark) the one-iteration instantiation (W = 36: the solver loop is straight-line code, the factor of M
+  // dies behind its one preconditioning step) takes 256 VGPRs + 52 B where the generic one takes 256 + 304 B, and the single launch wins at every batch size: B = 4096
+  // 155.0 - 155.9 us against 91.0 + 71.0 - 71.6 in two launches (25.5 - 25.7 M against 25.0 - 25.2 M env-steps/s), B = 32768 1162 us against 657 + 577 (27.8 - 28.1 M against
+  // 26.4 M; profiles/r05/notes.md).  Default on for those models (MJH_FUSE_ALL=0: off); still opt-in (MJH_FUSE_ALL=1) for the others.
+  // (round 5, second half: without the kernels' grid-stride loops the generic instantiation takes 228 VGPRs and no scratch either: default on for every model both fused kernels serve)
+  if (sw.fuse_all != 0 && out->fuse_cs && out->fuse_kcv && out->pack2[AR_CRB] && !out->pack4[AR_CRB] && M.ncvxpair == 0 && d->nsensor == 0) {
+    out->lds_all = std::max(out->lds(AR_KCV), out->lds(AR_CS));
+    if (2 * out->lds_all <= kLdsWg) {
+      out->fuse_all = 1;
+      M.nt_all = M.all_handoff;
+    }
+  }
+  // One launch per RK4 stage (stage 0 too, unless MJH_FUSE_STAGE0=0) for small Newton models: kernel 13 at four environments per wavefront, the direct constraint phase (kernel 8, two
+  // per wavefront: run twice per wave) and the solver's packed Newton tier at four, behind one another in mjh_sol2_kernel<.., 18>.  MJH_FUSE_STAGE=0: the three launches.
+  if (sw.fuse_stage && d->integrator == INT_RK4 && d->solver == SOL_NEWTON && out->fuse_kcv && out->pack4[AR_CRB] && M.con_direct && out->pack2[AR_CON] && out->sol2_tiers &&
+      out->sol2_w16_nmax == 8 && (out->sol2_w16_rpl == 2 || out->sol2_w16_rpl == 5) && M.ncvxpair == 0 && d->nefc > 0) {
+    const int need = std::max({4 * out->lds(AR_KCV), 2 * out->lds(AR_CON), 4 * out->lds(AR_TIER)});
+    if (need <= kLdsWg) { out->fuse_stage = 1; out->lds_stage = need; }
+  }
+  // ... and the tail of a pass alone (MJH_FUSE_TAIL=0: the two launches)
+  // Measured (MI355X, profiles/r06/notes.md): mesh scene (12 dofs: the tier's instantiation takes 227 VGPRs, two waves per SIMD, and the constraint phase inherits that) 219.6 us
+  // against 167.9 + 49.2 in two launches -- 8-dof tiers only (the one instantiation that is built), whose kernel sits at the constraint phase's own four waves per SIMD.
+  if (sw.fuse_tail && d->solver == SOL_NEWTON && M.con_direct && out->pack2[AR_CON] && out->sol2_tiers && out->sol2_w16_nmax == 8 && d->nefc > 0 && !M.topk) {
+    const int need = std::max(2 * out->lds(AR_CON), 4 * out->lds(AR_TIER));
+    if (need <= kLdsWg) { out->fuse_tail = 1; out->lds_tail = need; }
+  }
+
+  // workspace per environment (run()): [hand-over | candidates | RK4 stage Data | RK4 sums]
   if (d->integrator == INT_RK4) {
     const char* names[] = {
 #define X(n) #n,
         MJH_DATA_REALS(X)
 #undef X
     };
+    out->stage_leaf.assign(out->leaf_count.size(), STAGE_NONE);
     for (size_t i = 0; i < out->leaf_count.size(); i++)
-      if (is_stage_leaf(names[i], M.ncvxpair > 0, M.has_fluid != 0, M.ne > 0, M.topk != 0)) out->work_reals += out->leaf_count[i];
+      if (is_stage_leaf(names[i], M.ncvxpair > 0, M.has_fluid != 0, M.ne > 0, M.topk != 0)) {
+        // (kernel 13 keeps cinert / xipos in its arena from the kinematics to the crb and velocity stages: no later LAUNCH of a stage reads their workspace copies -- left NULL, the stores are skipped)
+        out->stage_leaf[i] = (out->fuse_kcv && (!strcmp(names[i], "cinert") || !strcmp(names[i], "xipos"))) ? STAGE_SPACE : STAGE_SLOT;
+        out->work_reals += out->leaf_count[i];
+      }
     out->work_reals += 4 * (int64_t)d->nv + 2 * (int64_t)d->na;  // qvel0, kqvel(unused), sum_qvel, sum_qacc, act0, sum_actdot
   }
   {  // hand-over of the small-model constraint phase (kernel 8) to the register solver: [count | contact -> slot | D | aref | rows] of the active contacts' rows, compact.  MJH_HANDOVER=0: off
-    static const bool off = [] { const char* e = getenv("MJH_HANDOVER"); return e && e[0] == '0'; }();
     const int64_t nd = (int64_t)d->nefc - d->nl;
     // Measured (MI355X, profiles/r05/notes.md): ant (RK4: stages 1..3 write the hand-over INSTEAD of their workspace leaves) solver phase 44.7 -> 42.3 us per stage, constraint phase unchanged;
     // mesh scene (Euler: the leaves AND the hand-over) solver 197.9 -> 194.4 us but constraint phase 47.2 -> 52.0: RK4 models only.
-    out->hs_reals = (!off && d->integrator == INT_RK4 && M.con_direct && M.crow_by_con && out->sol2_nmax && !out->fuse_cs && nd > 0) ? ((1 + (int64_t)d->ncon + 2 * nd + nd * d->nv + 3) & ~(int64_t)3) : 0;
+    out->hs_reals = (sw.handover && d->integrator == INT_RK4 && M.con_direct && M.crow_by_con && out->sol2_nmax && !out->fuse_cs && nd > 0) ? ((1 + (int64_t)d->ncon + 2 * nd + nd * d->nv + 3) & ~(int64_t)3) : 0;
     out->work_reals += out->hs_reals;
   }
   out->cand_reals = (d->topk && M.ncvxpair > 0) ? 13 * (int64_t)d->ncand : 0;  // candidate contacts of the convex narrow phase (dist, pos, frame)
   out->work_reals += out->cand_reals;
+  return 0;
+}
 
+// ---- grants: the dynamic LDS of every kernel the plan can launch, from the plan's fields (hipFuncSetAttribute is per function: the last model built sets it) ----
+template <typename REAL>
+int grant_lds(const mjhModel* m) {
+  HIP_TRY((allow_phase_lds_packed<REAL, MJH_KERNEL_KIN>(m)));
+  HIP_TRY((allow_phase_lds_packed<REAL, MJH_KERNEL_CRB>(m)));
+  HIP_TRY((allow_phase_lds_packed<REAL, MJH_KERNEL_CON>(m)));
+  HIP_TRY((allow_phase_lds_packed<REAL, MJH_KERNEL_VEL>(m)));
+  HIP_TRY((allow_phase_lds_packed<REAL, MJH_KERNEL_SOL>(m)));
+  HIP_TRY((allow_phase_lds_packed<REAL, MJH_KERNEL_SOL_GEN>(m)));
+  HIP_TRY((allow_phase_lds_packed<REAL, MJH_KERNEL_CON_GEN>(m)));
+  HIP_TRY((allow_phase_lds_packed<REAL, MJH_KERNEL_CON_DIRECT>(m)));
+  HIP_TRY((allow_phase_lds_packed<REAL, MJH_KERNEL_VEL_OPT>(m)));
+  if (m->fuse_kcv) HIP_TRY((allow_phase_lds_packed<REAL, MJH_KERNEL_KCV>(m)));  // (fuse_kcv: the crb arena packs two per wavefront)
+  if (m->fuse_kv) {  // (its packed forms by its own arena alone: pack2 / pack4 of AR_KV also need both phases packed)
+    HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KV, MJH_WAVE>(m)));
+    if (2 * m->lds(AR_KV) <= kLdsWg) HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KV, 32>(m)));
+    if (4 * m->lds(AR_KV) <= kLdsWg) HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KV, 16>(m)));
+  }
+  if (m->kcv2) {  // (the two-wave form only exists packed)
+    HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KCV2, 32>(m)));
+    if (m->pack4[AR_CRB]) HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KCV2, 16>(m)));
+  }
+  HIP_TRY(allow_lds(&mjh_convex_kernel<REAL>, m->cvx_lds_bytes));
+  if (m->sol2_nmax) HIP_TRY(allow_sol2_lds<REAL>(SOL2_PAIR, 2 * m->lds(AR_SOL2)));
+  if (m->sol2_w16_rpl) {
+    HIP_TRY(allow_sol2_lds<REAL>(SOL2_QUAD, 4 * m->lds(AR_TIER)));
+    HIP_TRY(allow_sol2_lds<REAL>(SOL2_QUAD_NEWTON, 4 * m->lds(AR_TIER)));
+  }
+  if (m->fuse_cs) {
+    HIP_TRY(allow_sol2_lds<REAL>(SOL2_CS, 2 * m->lds(AR_CS)));
+    HIP_TRY(allow_sol2_lds<REAL>(SOL2_CS_ONE, 2 * m->lds(AR_CS)));
+  }
+  if (m->fuse_all) {
+    HIP_TRY(allow_sol2_lds<REAL>(SOL2_PASS, 2 * m->lds_all));
+    HIP_TRY(allow_sol2_lds<REAL>(SOL2_PASS_ONE, 2 * m->lds_all));
+  }
+  if (m->fuse_stage || m->fuse_tail) HIP_TRY(allow_sol2_lds<REAL>(SOL2_STAGE, std::max(m->lds_stage, m->lds_tail)));
+  HIP_TRY(allow_lds(&mjh_inverse_kernel<REAL>, kLdsWg));  // (the inverse tail's LDS_BUDGET plus the rounding of lds_env)
+  return 0;
+}
+
+// ---- upload: the blob to the device, DevModel's table pointers into it ----
+int upload(mjhModel* out, const BlobBuilder& bb, const Fixups& fix) {
   void* dev = nullptr;
   HIP_TRY(hipMalloc(&dev, bb.host.size() + 16));
+  out->blob = dev;  // (mjh_model_create releases it if what follows fails)
+  out->blob_bytes = bb.host.size();
   HIP_TRY(hipMemcpy(dev, bb.host.data(), bb.host.size(), hipMemcpyHostToDevice));
   for (auto& f : fix) *f.first = (const unsigned char*)dev + f.second;
-  out->blob = dev;
-  out->blob_bytes = bb.host.size();
-  HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KIN, MJH_WAVE>(out)));
-  HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_CRB, MJH_WAVE>(out)));
-  HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_CON, MJH_WAVE>(out)));
-  HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_VEL, MJH_WAVE>(out)));
-  HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_SOL, MJH_WAVE>(out)));
-  // phases that are register-bound (not LDS-bound) run two environments per wavefront, 32 lanes each: the same
-  // VGPR budget then keeps twice as many environments in flight (mjh_kernels.h, Env<REAL, W>)
-  if (2 * out->lds(AR_KIN) <= 64 * 1024) { HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KIN, 32>(out))); out->pack2[AR_KIN] = 1; }
-  if (2 * out->lds(AR_VEL) <= 64 * 1024) { HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_VEL, 32>(out))); out->pack2[AR_VEL] = 1; }
-  {  // fused kinematics + velocity kernel (plain velocity phase only).  Measured on MI355X: profiles/r02/notes.md.  MJH_FUSE_KV=0 keeps two launches.
-    static const bool fuse_off = [] { const char* e = getenv("MJH_FUSE_KV"); return e && e[0] == '0'; }();
-    int defer_ok = 0;
-    out->arena[AR_KV].bytes = lds_carve(M, PH_KINVEL, out->arena[AR_KV].off, &defer_ok) * (int)sizeof(REAL);
-    static const bool defer_off = [] { const char* e = getenv("MJH_KV_DEFER"); return e && e[0] == '0'; }();
-    M.kv_defer = (defer_ok && !defer_off) ? 1 : 0;
-    out->fuse_kv = (!fuse_off && !(M.has_fluid || M.has_gravcomp || M.ntendon > 0 || M.big) && out->lds(AR_KV) <= 160 * 1024) ? 1 : 0;
-    if (out->fuse_kv) {
-      HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KV, MJH_WAVE>(out)));
-      if (2 * out->lds(AR_KV) <= 64 * 1024) HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KV, 32>(out)));
-      if (4 * out->lds(AR_KV) <= 64 * 1024) HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KV, 16>(out)));
-    }
-  }
-  static const bool con_pack = [] { const char* e = getenv("MJH_CON_PACK"); return !(e && e[0] == '0'); }();
-  if (con_pack && M.con_direct && 2 * out->lds(AR_CON) <= 64 * 1024) { HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_CON_DIRECT, 32>(out))); out->pack2[AR_CON] = 1; }
-  HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_CON_DIRECT, MJH_WAVE>(out)));  // plain constraint phase: its contact rows go straight to the leaf, the arena is small enough for two per wavefront
-  // CRB: the register Cholesky keeps one matrix row per lane, so nv <= 32 would fit a 32-lane half too; measured on the float64
-  // humanoid (nv 27) two per wavefront is SLOWER, 50.2 vs 39.9 us (132 VGPRs: 3 waves / SIMD instead of 4, and every broadcast of the
-  // factorisation becomes two v_readlane + a select): opt-in only (MJH_CRB_PACK=1).  float32 small models: +13 % on the ant (round 1).
-  // (round 4, after the register work of round 3: 35.1 vs 36.5 us, and it is what lets kernel 13 serve the humanoid: default on, MJH_CRB_PACK=0 turns it off)
-  static const bool crb_pack = [] { const char* e = getenv("MJH_CRB_PACK"); return !(e && e[0] == '0'); }();
-  if (((sizeof(REAL) == 4 && d->nv <= 16) || (crb_pack && d->nv <= 32 && d->nv > 16)) && 2 * out->lds(AR_CRB) <= 64 * 1024) {
-    HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_CRB, 32>(out)));
-    out->pack2[AR_CRB] = 1;
-  }
-  // small models (every per-body / per-joint / per-dof loop fits 16 lanes): FOUR environments per wavefront in the packed phases.
-  // These phases are bound by the number of dependent chains a SIMD can interleave (registers cap the waves), so the same waves
-  // carrying twice the environments is close to twice the throughput -- measured on the ant (B = 16384, 64 environments per CU):
-  // see profiles/r02/notes.md.  MJH_PACK4=0 turns it off.
-  static const bool pack4 = [] { const char* e = getenv("MJH_PACK4"); return !(e && e[0] == '0'); }();
-  if (pack4 && d->nbody <= 16 && d->njnt <= 16 && d->nv <= 16) {
-    if (out->pack2[AR_KIN] && 4 * out->lds(AR_KIN) <= 64 * 1024) { HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KIN, 16>(out))); out->pack4[AR_KIN] = 1; }
-    if (out->pack2[AR_CRB] && 4 * out->lds(AR_CRB) <= 64 * 1024) { HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_CRB, 16>(out))); out->pack4[AR_CRB] = 1; }
-    if (out->pack2[AR_VEL] && 4 * out->lds(AR_VEL) <= 64 * 1024) {
-      HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_VEL, 16>(out)));
-      HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_VEL_OPT, 16>(out)));
-      out->pack4[AR_VEL] = 1;
-    }
-  }
-  // the fused kinematics + velocity kernel packs where both of its phases do and its own arena fits
-  out->pack2[AR_KV] = out->pack2[AR_KIN] && out->pack2[AR_VEL] && 2 * out->lds(AR_KV) <= 64 * 1024;
-  out->pack4[AR_KV] = out->pack4[AR_KIN] && out->pack4[AR_VEL] && 4 * out->lds(AR_KV) <= 64 * 1024;
-  {  // kinematics + crb / factor + velocity as ONE kernel (13): when the crb stage packs environments per wavefront the way the other two do (float32 models with
-     // nv <= 16; MJH_CRB_PACK for the rest).  Saves the crb kernel's loads of cinert / cdof, its launch and the wait between the launches.  MJH_FUSE_CRB=0: off.
-    static const bool off = [] { const char* e = getenv("MJH_FUSE_CRB"); return e && e[0] == '0'; }();
-    out->arena[AR_KCV].bytes = lds_carve(M, PH_KCV, out->arena[AR_KCV].off) * (int)sizeof(REAL);
-    const bool same_pack = out->pack2[AR_CRB] == out->pack2[AR_KV] && out->pack4[AR_CRB] == out->pack4[AR_KV];
-    out->fuse_kcv = (!off && out->fuse_kv && same_pack && out->pack2[AR_CRB] && out->lds(AR_KCV) <= 160 * 1024 && 2 * out->lds(AR_KCV) <= 64 * 1024 &&
-                     (!out->pack4[AR_CRB] || 4 * out->lds(AR_KCV) <= 64 * 1024)) ? 1 : 0;
-    if (out->fuse_kcv) {
-      // at every batch size (round 4; round 3 had kept the separate launches past one round of waves): the humanoid (two per wavefront) at B = 32768: 652 us against 452 + 218;
-      // the ant (four per wavefront) at B = 16384, two rounds: 93.6 us against 75.8 + 21.8 (profiles/r04/notes.md)
-      HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KCV, MJH_WAVE>(out)));
-      HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KCV, 32>(out)));
-      if (out->pack4[AR_CRB]) HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KCV, 16>(out)));
-    }
-  }
-  {  // kernel 13 on two wavefronts per workgroup (velocity beside crb / factor): packed float32 models.  MJH_KCV2=0 / 1 forces it off / on (also for float64, two per wavefront).
-    static const int sw = [] { const char* e = getenv("MJH_KCV2"); return !e ? -1 : (e[0] == '1' ? 1 : 0); }();
-    out->kcv2 = 0;
-    if (out->fuse_kcv && sw != 0 && (sw == 1 || (sizeof(REAL) == 4 && out->pack4[AR_CRB]))) {
-      out->arena[AR_KCV2].bytes = lds_carve(M, PH_KCV2, out->arena[AR_KCV2].off) * (int)sizeof(REAL);
-      const int per_wg = (out->pack4[AR_CRB] ? 4 : 2) * out->lds(AR_KCV2);
-      if (per_wg <= 64 * 1024) {
-        out->kcv2 = 1;
-        // The two-wave form pays while the whole batch is resident at once: two wavefronts per workgroup at four per SIMD are 8 workgroups per CU (and their arenas must fit the
-        // CU's 160 KB).  Past that it runs more rounds of waves than kernel 13 (which fits 16 one-wave workgroups) and loses.  Measured (MI355X, profiles/r05/notes.md): mesh scene
-        // B = 8192 37.5 us against 46.0; ant B = 8192 46.1 against 54.5; ant B = 16384 (two rounds against one) 101 against 62.
-        // The limit belongs to the device a LAUNCH runs on, not to the one that was current when the model was built: kcv2_limit() below, cached per device.
-        out->kcv2_per_wg = per_wg;
-        out->kcv2_envs_per_wg = out->pack4[AR_CRB] ? 4 : 2;
-        out->kcv2_max_envs = sw == 1 ? ((int64_t)1 << 62) : 0;
-        HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KCV2, 32>(out)));
-        if (out->pack4[AR_CRB]) HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_KCV2, 16>(out)));
-      }
-    }
-  }
-  HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_SOL_GEN, MJH_WAVE>(out)));
-  HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_CON_GEN, MJH_WAVE>(out)));
-  HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_VEL_OPT, MJH_WAVE>(out)));
-  if (out->pack2[AR_VEL]) HIP_TRY((allow_phase_lds<REAL, MJH_KERNEL_VEL_OPT, 32>(out)));
-  HIP_TRY(allow_lds(&mjh_convex_kernel<REAL>, out->cvx_lds_bytes));
-  if (out->sol2_nmax) {
-    HIP_TRY(allow_sol2_lds<REAL>(SOL2_PAIR, 2 * out->lds(AR_SOL2)));
-    if (out->sol2_w16_rpl) {
-      HIP_TRY(allow_sol2_lds<REAL>(SOL2_QUAD, 4 * out->lds(AR_TIER)));
-      HIP_TRY(allow_sol2_lds<REAL>(SOL2_QUAD_NEWTON, 4 * out->lds(AR_TIER)));
-    }
-  }
-  {  // the whole pass in one kernel: models both fused kernels serve at two environments per wavefront, without convex pairs or sensors (their kernels sit between the two halves).
-    // Measured (MI355X, humanoid B = 4096, three A / B pairs in one call, profiles/r04/notes.md): 166.8 - 170.5 us in one launch against 91.7 - 93.1 + 76.4 - 76.7 in two
-    // (23.5 - 24.3 M against 24.1 - 24.6 M env-steps/s): the one function is allocated 256 VGPRs + 304 B of scratch where the halves take 198 + 0 and 256 + 120 B, and that
-    // costs what the missing device-wide barrier saves.  Opt-in (MJH_FUSE_ALL=1).
-    // Round 5: for models with opt.iterations == 1 (the humanoid benchmark) the one-iteration instantiation (W = 36: the solver loop is straight-line code, the factor of M
-    // dies behind its one preconditioning step) takes 256 VGPRs + 52 B where the generic one takes 256 + 304 B, and the single launch wins at every batch size: B = 4096
-    // 155.0 - 155.9 us against 91.0 + 71.0 - 71.6 in two launches (25.5 - 25.7 M against 25.0 - 25.2 M env-steps/s), B = 32768 1162 us against 657 + 577 (27.8 - 28.1 M against
-    // 26.4 M; profiles/r05/notes.md).  Default on for those models (MJH_FUSE_ALL=0: off); still opt-in (MJH_FUSE_ALL=1) for the others.
-    static const int sw = [] { const char* e = getenv("MJH_FUSE_ALL"); return !e ? -1 : (e[0] == '1' ? 1 : 0); }();
-    const bool on = sw != 0;  // (round 5, second half: without the kernels' grid-stride loops the generic instantiation takes 228 VGPRs and no scratch either: default on for every model both fused kernels serve)
-    out->fuse_all = 0;
-    if (on && out->fuse_cs && out->fuse_kcv && out->pack2[AR_CRB] && !out->pack4[AR_CRB] && M.ncvxpair == 0 && d->nsensor == 0) {
-      out->lds_all = out->lds(AR_KCV) > out->lds(AR_CS) ? out->lds(AR_KCV) : out->lds(AR_CS);
-      if (2 * out->lds_all <= 64 * 1024) {
-        out->fuse_all = 1;
-        M.nt_all = M.all_handoff;
-        HIP_TRY(allow_sol2_lds<REAL>(SOL2_PASS, 2 * out->lds_all));
-        HIP_TRY(allow_sol2_lds<REAL>(SOL2_PASS_ONE, 2 * out->lds_all));
-      }
-    }
-  }
-  {  // One launch per RK4 stage (stage 0 too, unless MJH_FUSE_STAGE0=0) for small Newton models: kernel 13 at four environments per wavefront, the direct constraint phase (kernel 8, two
-     // per wavefront: run twice per wave) and the solver's packed Newton tier at four, behind one another in mjh_sol2_kernel<.., 18>.  MJH_FUSE_STAGE=0: the three launches.
-    static const bool off = [] { const char* e = getenv("MJH_FUSE_STAGE"); return e && e[0] == '0'; }();
-    out->fuse_stage = 0;
-    if (!off && d->integrator == INT_RK4 && d->solver == SOL_NEWTON && out->fuse_kcv && out->pack4[AR_CRB] && M.con_direct && out->pack2[AR_CON] && out->sol2_tiers && out->sol2_w16_nmax == 8 &&
-        (out->sol2_w16_rpl == 2 || out->sol2_w16_rpl == 5) && M.ncvxpair == 0 && d->nefc > 0) {
-      int need = 4 * out->lds(AR_KCV);
-      if (2 * out->lds(AR_CON) > need) need = 2 * out->lds(AR_CON);
-      if (4 * out->lds(AR_TIER) > need) need = 4 * out->lds(AR_TIER);
-      if (need <= 64 * 1024) {
-        out->fuse_stage = 1;
-        out->lds_stage = need;
-      }
-    }
-    // ... and the tail of a pass alone (MJH_FUSE_TAIL=0: the two launches)
-    // Measured (MI355X, profiles/r06/notes.md): mesh scene (12 dofs: the tier's instantiation takes 227 VGPRs, two waves per SIMD, and the constraint phase inherits that) 219.6 us
-    // against 167.9 + 49.2 in two launches -- 8-dof tiers only (the one instantiation that is built), whose kernel sits at the constraint phase's own four waves per SIMD.
-    static const bool tail_off = [] { const char* e = getenv("MJH_FUSE_TAIL"); return e && e[0] == '0'; }();
-    out->fuse_tail = 0;
-    if (!tail_off && d->solver == SOL_NEWTON && M.con_direct && out->pack2[AR_CON] && out->sol2_tiers && out->sol2_w16_nmax == 8 && d->nefc > 0 && !M.topk) {
-      int need = 2 * out->lds(AR_CON);
-      if (4 * out->lds(AR_TIER) > need) need = 4 * out->lds(AR_TIER);
-      if (need <= 64 * 1024) { out->fuse_tail = 1; out->lds_tail = need; }
-    }
-    if (out->fuse_stage || out->fuse_tail) {
-      HIP_TRY(allow_sol2_lds<REAL>(SOL2_STAGE, out->lds_stage > out->lds_tail ? out->lds_stage : out->lds_tail));
-    }
-  }
   return 0;
+}
+
+template <typename REAL>
+int build(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
+  BlobBuilder bb;
+  Fixups fix;
+  if (const int rc = tables(d, out, M, bb, fix)) return rc;
+  if (const int rc = plan(d, out, M)) return rc;
+  if (const int rc = grant_lds<REAL>(out)) return rc;
+  return upload(out, bb, fix);
 }
 
 // Workgroups per launch.  The kernels run ONE unit of work per workgroup (no grid-stride loop), so a batch past this many is cut into several launches.  2^20 by default;
 // MJH_MAX_GRID_LOG2 lowers it so that the tests reach the multi-launch paths at small batches.
-static int64_t max_grid() {
-  static const int64_t g = [] { const char* e = getenv("MJH_MAX_GRID_LOG2"); int v = e ? atoi(e) : 20; return (int64_t)1 << (v < 0 ? 0 : (v > 20 ? 20 : v)); }();
-  return g;
-}
+static int64_t max_grid() { return (int64_t)1 << switches().max_grid_log2; }
 
 // The kernels run ONE unit of work per workgroup, `per_wg` units each (no grid-stride loop): `count` units go out as launches of at most `max_wg` workgroups.
 // launch(first, n, workgroups) enqueues the one of units [first, first + n).
@@ -902,19 +919,10 @@ int launch_phase(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
 // crb / factor (mjh_sol2_kernel: "out of lockstep").  Default 0x100: workgroups 256 apart, i.e. different wave slots of the same CUs under the round-robin placement.  Measured
 // (MI355X, humanoid B = 4096, profiles/r06/notes.md): 141.5 - 144.0 us -> 137.0 - 137.6 us whatever the mask (0x1 .. 0xfff); B = 32768 (eight rounds: the waves drift apart by themselves) unchanged.
 // Launches of more than 4096 workgroups keep one order: B = 32768 (eight rounds, the waves drift apart by themselves) measured 1015 us in one order against 1033 us with the swap.
-static int xswap_flags(int64_t workgroups) {
-  static const int f = [] { const char* e = getenv("MJH_XSWAP"); const long v = e ? strtol(e, nullptr, 0) : 0x100; return (int)((v & 0xfff) << 16); }();
-  static const bool forced = getenv("MJH_XSWAP") != nullptr;  // (an explicit mask applies at every size: the bit-identity tests)
-  return (forced || workgroups <= 4096) ? f : 0;
-}
-
 // MJH_XSWAP_K=mask (default 0x200; 0: off): the same idea inside the kinematics stage -- workgroups of odd parity under this mask run com_pos before the geom / site / camera frames
 // (Env::kinematics, com_first).  Measured (MI355X, humanoid B = 4096, profiles/r06/notes.md): 138.8 -> 136.0 us on top of MJH_XSWAP; bit-identical.
-static int xswap_k_mask(int64_t workgroups) {
-  static const int f = [] { const char* e = getenv("MJH_XSWAP_K"); return e ? (int)(strtol(e, nullptr, 0) & 0xfff) : 0x200; }();
-  static const bool forced = getenv("MJH_XSWAP_K") != nullptr;
-  return (forced || workgroups <= 4096) ? f : 0;
-}
+// A mask that is set applies at every launch size; the defaults at launches of at most 4096 workgroups.
+static int xswap_mask(int set, int default_mask, int64_t workgroups) { return set >= 0 ? set : (workgroups <= 4096 ? default_mask : 0); }
 
 // the out-of-lockstep masks of a launcher of `workgroups` workgroups: a.flags carries MJH_XSWAP's for the launcher's scope, a.xswap_k MJH_XSWAP_K's
 template <typename REAL>
@@ -922,8 +930,8 @@ struct OutOfLockstep {
   KArgs<REAL>& a;
   const int flags;
   OutOfLockstep(KArgs<REAL>& args, int64_t workgroups) : a(args), flags(args.flags) {
-    a.flags |= xswap_flags(workgroups);
-    a.xswap_k = xswap_k_mask(workgroups);
+    a.flags |= xswap_mask(switches().xswap, 0x100, workgroups) << 16;
+    a.xswap_k = xswap_mask(switches().xswap_k, 0x200, workgroups);
   }
   ~OutOfLockstep() { a.flags = flags; }
 };
@@ -989,8 +997,8 @@ template <typename REAL>
 int launch_stage(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream, int parts = 7) {  // parts 6: the tail of a pass (constraint phase + first solver tier) behind launches of its own for the rest
   a.stage_parts = parts;
   const OutOfLockstep<REAL> swap(a, a.B / 4);
-  static const int xswap_c = [] { const char* e = getenv("MJH_XSWAP_C"); return e ? (int)(strtol(e, nullptr, 0) & 0xfff) : 0x400; }();  // MJH_XSWAP_C=mask (0: off; see KArgs::xswap_c): measured ant 30.9 -> 31.1 M env-steps/s
-  a.xswap_c = a.rk_stage == 0 ? xswap_c : 0;
+  const int xswap_c = switches().xswap_c;  // MJH_XSWAP_C=mask (default 0x400, 0: off; see KArgs::xswap_c): measured ant 30.9 -> 31.1 M env-steps/s
+  a.xswap_c = a.rk_stage == 0 ? (xswap_c >= 0 ? xswap_c : 0x400) : 0;
   a.off = m->arena[AR_KCV].off; a.lds_reals = m->lds(AR_KCV) / (int)sizeof(REAL);
   a.off2 = m->arena[AR_CON].off; a.lds_reals2 = m->lds(AR_CON) / (int)sizeof(REAL);
   a.off3 = m->arena[AR_TIER].off; a.lds_reals3 = m->lds(AR_TIER) / (int)sizeof(REAL);
@@ -1010,9 +1018,9 @@ int launch_cs(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
   a.lds_reals = m->lds(AR_CS) / (int)sizeof(REAL);
   a.row_lo = -1; a.row_hi = 0x7fffffff;
   a.mark_leftover = 0; a.scan_marks = 0;
-  static const bool one_off = [] { const char* e = getenv("MJH_CS_ONE"); return e && e[0] == '0'; }();  // (A / B switch: MJH_CS_ONE=0 launches the generic instantiation for one-iteration models too)
   // opt.iterations == 1 (solver.py:534-535: the loop body runs exactly once): straight-line solver code
-  const int wt = a.M.iterations == 1 && !one_off ? SOL2_CS_ONE : SOL2_CS;
+  // (A / B switch: MJH_CS_ONE=0 launches the generic instantiation for one-iteration models too)
+  const int wt = a.M.iterations == 1 && switches().cs_one ? SOL2_CS_ONE : SOL2_CS;
   if (const int rc = launch_sol2_kernel(a, 28, 1, wt, 2 * m->lds(AR_CS), stream)) return rc;
   timing_mark(stream, MJH_KERNEL_CS);
   return 0;
@@ -1049,7 +1057,7 @@ int launch_sensor_kernel(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) 
   (void)m;
   // environments per wavefront: two when their slots fit the 64 lanes of the slot phase (MJH_SENSOR_EPW overrides).  Measured (MI355X, ant B = 16384, 27 slots and 104 ray tests per environment):
   // one 36.8 - 37.1 us, two 28.8 - 29.0, four 35.6 - 35.7 (a quarter of the workgroups: too few waves to hide the kernel's two dependent load chains) -- profiles/r05/notes.md
-  static const int epw_env = [] { const char* e = getenv("MJH_SENSOR_EPW"); return e ? atoi(e) : 0; }();
+  const int epw_env = switches().sensor_epw;
   int epw = epw_env > 0 ? epw_env : (a.M.nsensordata > 0 ? MJH_WAVE / a.M.nsensordata : 1);
   epw = epw < 1 ? 1 : (epw_env > 0 ? (epw > 8 ? 8 : epw) : (epw > 2 ? 2 : epw));
   a.sns_epw = epw;
@@ -1075,9 +1083,9 @@ static int64_t kcv2_limit(const mjhModel* m, hipStream_t stream) {
   if (hipStreamGetDevice(stream, &dev) != hipSuccess && hipGetDevice(&dev) != hipSuccess) dev = 0;
   if (dev < 0 || dev >= 64) dev = 0;
   if (!cus_of[dev]) {
-    int cus = 256, lds = 160 * 1024;
+    int cus = 256, lds = kLdsCu;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess || lds < 64 * 1024) lds = 160 * 1024;
+    if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess || lds < kLdsWg) lds = kLdsCu;
     lds_of[dev] = lds;
     cus_of[dev] = cus > 0 ? cus : 256;
   }
@@ -1101,8 +1109,7 @@ int forward_pass(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
   if (m->fuse_all && (st & MJH_STAGE_ALL) == MJH_STAGE_ALL && a.B >= 2 && (a.B & 1) == 0 && a.B <= 2 * max_grid() /* one workgroup per pair: the kernel has no grid-stride loop */ && a.cur.efc_J && a.cur.efc_D && a.cur.efc_aref && a.cur.qM && a.cur.qLD) return launch_all<REAL>(m, a, stream);
   // MJH_FUSE_STAGE0=0: stage 0 (which writes the returned Data in full) keeps its three launches.  Its sensors (they read leaves of the kinematics and velocity stages only) follow the
   // stage kernel: in an RK4 step nothing of stage 0 writes the returned state -- the final advance is stage 3's -- so the jointpos / ballquat readers of out.qpos race nothing.
-  static const bool stage0_off = [] { const char* e = getenv("MJH_FUSE_STAGE0"); return e && e[0] == '0'; }();
-  if (m->fuse_stage && a.rk_stage >= (stage0_off ? 1 : 0) && (st & MJH_STAGE_ALL) == MJH_STAGE_ALL && a.B >= 4 && (a.B & 3) == 0 && a.cur.qM && a.cur.qLD && a.cur.qfrc_smooth && a.cur.contact_dist &&
+  if (m->fuse_stage && a.rk_stage >= (switches().fuse_stage0 ? 0 : 1) && (st & MJH_STAGE_ALL) == MJH_STAGE_ALL && a.B >= 4 && (a.B & 3) == 0 && a.cur.qM && a.cur.qLD && a.cur.qfrc_smooth && a.cur.contact_dist &&
       a.cur.efc_J && a.cur.efc_D && a.cur.efc_aref) {
     if ((rc = launch_stage<REAL>(m, a, stream))) return rc;
     if (a.M.nsensor > 0 && a.rk_stage == 0 && a.cur.sensordata) {
@@ -1179,20 +1186,12 @@ int run(const mjhModel* m, const DevModel<REAL>& M, const mjhData* in, mjhData* 
   if (!work) return fail(-22, "RK4 needs a workspace of mjh_model_work_bytes(m) * B bytes");
   DevData<REAL> scr;
   memset(&scr, 0, sizeof(scr));
-  {
-    REAL** slots = reinterpret_cast<REAL**>(&scr);
-    const char* names[] = {
-#define X(n) #n,
-        MJH_DATA_REALS(X)
-#undef X
-    };
-    for (size_t i = 0; i < m->leaf_count.size(); i++)
-      if (is_stage_leaf(names[i], M.ncvxpair > 0, M.has_fluid != 0, M.ne > 0, M.topk != 0)) {
-        // (kernel 13 keeps cinert / xipos in its arena from the kinematics to the crb and velocity stages: no later LAUNCH of a stage reads their workspace copies -- left NULL, the stores are skipped)
-        if (!(m->fuse_kcv && (!strcmp(names[i], "cinert") || !strcmp(names[i], "xipos")))) slots[i] = w;
-        w += m->leaf_count[i] * B;
-      }
-  }
+  REAL** slots = reinterpret_cast<REAL**>(&scr);
+  for (size_t i = 0; i < m->stage_leaf.size(); i++)
+    if (m->stage_leaf[i] != STAGE_NONE) {
+      if (m->stage_leaf[i] == STAGE_SLOT) slots[i] = w;
+      w += m->leaf_count[i] * B;
+    }
   a.W.qvel0 = w; w += (int64_t)M.nv * B;
   a.W.kqvel = w; w += (int64_t)M.nv * B;
   a.W.sum_qvel = w; w += (int64_t)M.nv * B;
@@ -1312,7 +1311,7 @@ int mjh_model_create(const mjhModelDesc* desc, int dtype, mjhModel** out) {
   mjhModel* m = new mjhModel();
   m->dtype = dtype;
   int rc = dtype == MJH_F64 ? build<double>(desc, m, m->m64) : build<float>(desc, m, m->m32);
-  if (rc != 0) { delete m; return rc; }
+  if (rc != 0) { mjh_model_destroy(m); return rc; }
   *out = m;
   return 0;
 }
@@ -1418,19 +1417,11 @@ int mjh_model_leaf_counts(const mjhModel* m, int64_t* counts, int max) {
   return (int)all.size();
 }
 
-static thread_local bool g_io_inner = false;
-static thread_local int g_io_stage = 0;  // 2: the accounts asked for are those of RK4 stages 1..3 alone (the stage kernel's parts)
-static int mjh_model_kernel_io_impl(const mjhModel* m, int kernel, int64_t* read_write_bytes) {
-  const bool prev = g_io_inner;
-  g_io_inner = true;
-  const int rc = mjh_model_kernel_io(m, kernel, read_write_bytes);
-  g_io_inner = prev;
-  return rc;
-}
-int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes) {
-  if (!m || !read_write_bytes) return fail(-22, "null argument");
+// mjh_model_kernel_io's account of `kernel` in a scope: `inner` -- asked for as a part of another kernel's account (kernels 13 / 14 of a model with the whole-pass kernel
+// are accounted inside it only); `stages13` -- the accounts of RK4 stages 1..3 alone (the stage kernel's parts)
+static int kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes, bool inner, bool stages13) {
   if ((kernel == MJH_KERNEL_SOL2) != (m->sol2_nmax != 0) && (kernel == MJH_KERNEL_SOL2 || kernel == MJH_KERNEL_SOL || kernel == MJH_KERNEL_SOL_GEN)) return -2;  // the solver phase runs as ONE of kernels 4 / 6 / 9
-  if (kernel == MJH_KERNEL_KCV2) return m->kcv2 ? mjh_model_kernel_io_impl(m, MJH_KERNEL_KCV, read_write_bytes) : -2;  // the two-wave form of kernel 13 moves the same bytes
+  if (kernel == MJH_KERNEL_KCV2) return m->kcv2 ? kernel_io(m, MJH_KERNEL_KCV, read_write_bytes, true, stages13) : -2;  // the two-wave form of kernel 13 moves the same bytes
   if (kernel == MJH_KERNEL_KCV && !m->fuse_kcv) return -2;  // (a model with kernel 13 reports both accounts: which one a step launches depends on the batch)
   if ((kernel == MJH_KERNEL_KV) != (m->fuse_kv != 0) && (kernel == MJH_KERNEL_KV || kernel == MJH_KERNEL_KIN || kernel == MJH_KERNEL_VEL)) return -2;  // kinematics + velocity: ONE kernel (12) or two (0, 3)
   const bool f64 = m->dtype == MJH_F64;
@@ -1440,7 +1431,7 @@ int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes
     int rc = f64 ? mjh_kernel_io<double>(m->m64, k, 1, &a[0], &a[1]) : mjh_kernel_io<float>(m->m32, k, 1, &a[0], &a[1]);
     if (rc == 0 && rk4 && k != MJH_KERNEL_SENSOR) {
       rc = f64 ? mjh_kernel_io<double>(m->m64, k, 2, &b[0], &b[1]) : mjh_kernel_io<float>(m->m32, k, 2, &b[0], &b[1]);
-      if (g_io_stage == 2) { a[0] = b[0]; a[1] = b[1]; }                      // the stage kernel: launches of stages 1..3 only
+      if (stages13) { a[0] = b[0]; a[1] = b[1]; }                             // the stage kernel: launches of stages 1..3 only
       else if (m->fuse_stage) {}                                               // ... whose model launches kernels 13 / 8 / 9 in stage 0 only
       else { a[0] = (a[0] + 3 * b[0]) / 4; a[1] = (a[1] + 3 * b[1]) / 4; }
     }
@@ -1457,30 +1448,25 @@ int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes
   if (kernel == MJH_KERNEL_PASS) {  // the whole pass in one launch: the accounts of kernels 13 and 14 (what the second half reads of the first it still reads from the leaves)
     if (!m->fuse_all) return -2;
     int64_t a13[2] = {0, 0}, a14[2] = {0, 0};
-    const mjhModel* mm = m;
-    if (mjh_model_kernel_io_impl(mm, MJH_KERNEL_KCV, a13) != 0 || mjh_model_kernel_io_impl(mm, MJH_KERNEL_CS, a14) != 0) return -2;
+    if (kernel_io(m, MJH_KERNEL_KCV, a13, true, stages13) != 0 || kernel_io(m, MJH_KERNEL_CS, a14, true, stages13) != 0) return -2;
     read_write_bytes[0] = a13[0] + a14[0]; read_write_bytes[1] = a13[1] + a14[1];
     return 0;
   }
   if (kernel == MJH_KERNEL_STAGE) {  // one RK4 stage in one launch: the stage accounts of kernel 13, the constraint phase and the register solver (what a part reads of the previous one it still reads from the workspace leaves)
     if (!m->fuse_stage) return -2;
     int64_t a13[2] = {0, 0}, a8[2] = {0, 0}, a9[2] = {0, 0};
-    const int prev = g_io_stage;
-    g_io_stage = 2;
-    const int rc = (mjh_model_kernel_io_impl(m, MJH_KERNEL_KCV, a13) != 0 || mjh_model_kernel_io_impl(m, MJH_KERNEL_CON_DIRECT, a8) != 0 || mjh_model_kernel_io_impl(m, MJH_KERNEL_SOL2, a9) != 0) ? -2 : 0;
-    g_io_stage = prev;
-    if (rc) return rc;
+    if (kernel_io(m, MJH_KERNEL_KCV, a13, true, true) != 0 || kernel_io(m, MJH_KERNEL_CON_DIRECT, a8, true, true) != 0 || kernel_io(m, MJH_KERNEL_SOL2, a9, true, true) != 0) return -2;
     read_write_bytes[0] = a13[0] + a8[0] + a9[0]; read_write_bytes[1] = a13[1] + a8[1] + a9[1];
     return 0;
   }
   if (kernel == MJH_KERNEL_TAIL) {  // the tail of a pass in one launch: the accounts of the constraint phase and the register solver
     if (!m->fuse_tail) return -2;
     int64_t a8[2] = {0, 0}, a9[2] = {0, 0};
-    if (mjh_model_kernel_io_impl(m, MJH_KERNEL_CON_DIRECT, a8) != 0 || mjh_model_kernel_io_impl(m, MJH_KERNEL_SOL2, a9) != 0) return -2;
+    if (kernel_io(m, MJH_KERNEL_CON_DIRECT, a8, true, stages13) != 0 || kernel_io(m, MJH_KERNEL_SOL2, a9, true, stages13) != 0) return -2;
     read_write_bytes[0] = a8[0] + a9[0]; read_write_bytes[1] = a8[1] + a9[1];
     return 0;
   }
-  if ((kernel == MJH_KERNEL_KCV || kernel == MJH_KERNEL_CS) && m->fuse_all && !g_io_inner) return -2;
+  if ((kernel == MJH_KERNEL_KCV || kernel == MJH_KERNEL_CS) && m->fuse_all && !inner) return -2;
   if (kernel == MJH_KERNEL_CS) {  // constraint stage + register solver: the two accounts minus what stays in the arena between them -- the dense rows of efc_J, efc_D / efc_aref, one entry per single-column row, qvel
     if (!m->fuse_cs) return -2;
     int64_t k2[2] = {0, 0}, k4[2] = {0, 0};
@@ -1503,6 +1489,10 @@ int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes
   if (io_of(k, a) != 0) return -2;  // -2: this model's step does not launch that kernel
   read_write_bytes[0] = a[0]; read_write_bytes[1] = a[1];
   return 0;
+}
+int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes) {
+  if (!m || !read_write_bytes) return fail(-22, "null argument");
+  return kernel_io(m, kernel, read_write_bytes, false, false);
 }
 
 int64_t mjh_model_work_bytes(const mjhModel* m) { return m ? m->work_reals * (m->dtype == MJH_F64 ? 8 : 4) : 0; }
