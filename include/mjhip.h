@@ -10,6 +10,7 @@
  *   mjh_step           <- forward.step(m, d, fixed_iterations)        (_src/forward.py:463-496)
  *   mjh_inverse        <- inverse.inverse(m, d)                       (_src/inverse.py:86-102)
  *   mjh_ray            <- ray.ray(m, d, pnt, vec, ...)               (_src/ray.py:375-452)
+ *   mjh_render         <- render.render_batch(m, d, camera_id, ...)   (_src/render.py:719-907)
  *
  * Conventions
  *  - every Data leaf is batch-major contiguous: shape [B, ...] exactly as
@@ -77,6 +78,7 @@ extern "C" {
 #define MJH_KERNEL_TAIL 19       /* that kernel running the constraint phase + the solver's first tier only           */
 #define MJH_KERNEL_INVERSE 20    /* the inverse-dynamics tail of mjh_inverse                                          */
 #define MJH_KERNEL_RAY 21        /* the ray kernel of mjh_ray                                                         */
+#define MJH_KERNEL_RENDER 22     /* the ray-cast renderer of mjh_render                                               */
 
 /* pair-function ids of the static collision table (collision_driver.py:106-125) */
 #define MJH_FN_PLANE_SPHERE 0
@@ -436,6 +438,49 @@ typedef struct mjhRayCands {
 int mjh_ray(const mjhModel* m, const void* geom_xpos, const void* geom_xmat, const void* pnt, int64_t pnt_env, int64_t pnt_ray, const void* vec,
             int64_t vec_env, int64_t vec_ray, int64_t B, int64_t R, const mjhRayCands* cands, void* dist, int64_t* geomid, void* hip_stream);
 
+/* the scene one mjh_render call draws, built by the caller from the model (render.py:33-114 precompute_render_data).  Every pointer is device memory.
+ * `cand`, `tri`, `geom_size`: as mjhRayCands, the VISIBLE geoms ((matid != -1 or rgba alpha != 0) and (matid == -1 or the material's alpha != 0)) in the
+ * reference's type-major order; the `nprim` primitive rows come first, the mesh rows (ascending geom id) after them.  Shadow rays test the primitive
+ * rows only, as the reference does.  `geom_rgba`: [ngeom][4] reals of the call's dtype holding float32 values (MuJoCo's type); `geom_matid`: [ngeom]
+ * int32, -1 for none; `mat_rgba`: [nmat][4] float32.  A hit geom's colour is mat_rgba[matid] when matid >= 0, else geom_rgba (first three channels).
+ * `light`: [nlight][16] reals of the call's dtype, one row per light: diffuse (3), ambient (3), specular (3), attenuation (3), cos(cutoff) of a
+ * spotlight (cutoff < 180 degrees; 2 for none), directional (1 / 0), castshadow (1 / 0), unused.  nlight must equal the model's. */
+typedef struct mjhRenderScene {
+  int64_t ncand;
+  int64_t nprim;
+  const int32_t* cand;
+  const void* tri;
+  const void* geom_size;
+  const void* geom_rgba;
+  const int32_t* geom_matid;
+  const float* mat_rgba;
+  int64_t nlight;
+  const void* light;
+} mjhRenderScene;
+
+/* one mjh_render call's settings.  camera: 0 <= camera < ncam; width, height, ssaa >= 1 (the output image is width x height, rendered at ssaa times
+ * that and averaged); half_w / half_h: the tangents of the half view angles (render.py:196-198, in the call's dtype); shading: Lambert + Phong per
+ * light when the model has lights (else the flat colour); shadows: shadow rays for the castshadow lights; background: the colour of a miss (float32
+ * values); fog: linear fog on hit samples, factor clamp((depth - fog_start) / fog_range, 0, 1) toward fog_color; rgb_f32: write rgb as float32 (else
+ * in the call's dtype); u8: write rgb as uint8, (rgb * 255) clamped to [0, 255] and truncated, from the rgb rgb_f32 selects. */
+typedef struct mjhRenderParams {
+  int32_t camera, width, height, ssaa;
+  int32_t shading, shadows, fog, rgb_f32, u8, reserved;
+  double half_w, half_h;
+  double background[3];
+  double fog_color[3];
+  double fog_start, fog_range;
+} mjhRenderParams;
+
+/* batched ray-cast rendering (render.py:719-907): one image per environment from camera `camera`.  geom_xpos [B, ngeom, 3], geom_xmat [B, ngeom, 9],
+ * cam_xpos [B, ncam, 3], cam_xmat [B, ncam, 9], light_xpos / light_xdir [B, nlight, 3]: the environments' poses (a forward pass's leaves).  Writes
+ * rgb [B, height, width, 3] (the dtype params->rgb_f32 / u8 select), depth [B, height, width] (the model's dtype; the ray distance of the nearest hit,
+ * -1 for a miss, averaged over the super-samples), seg [B, height, width] (int64 geom id of the centre super-sample, -1 for a miss).  Row 0 is the top of
+ * the image.  Returns 0 or a negative code; B == 0 is a no-op. */
+int mjh_render(const mjhModel* m, const void* geom_xpos, const void* geom_xmat, const void* cam_xpos, const void* cam_xmat, const void* light_xpos,
+               const void* light_xdir, int64_t B, const mjhRenderScene* scene, const mjhRenderParams* params, void* rgb, void* depth, int64_t* seg,
+               void* hip_stream);
+
 /* per-environment ELEMENT count of every mjhData leaf in ABI order (reals, then int32, then int64 leaves): a leaf handed to
  * mjh_forward / mjh_step / mjh_reset_where must hold exactly B * count elements.  The binding validates tensor sizes against
  * this before it passes raw pointers (the kernels index `ptr + env * count` unchecked).  Writes min(n, max) entries, returns n. */
@@ -456,7 +501,7 @@ int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsi
 int mjh_model_lds_bytes(const mjhModel* m, int arena);
 
 /* measurement aid used by bench.py for the per-kernel roofline: while enabled, every kernel launch of mjh_step / mjh_forward is
- * bracketed by HIP events on the launch stream (mjh_inverse and mjh_ray too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
+ * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray and mjh_render too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
  * the elapsed milliseconds and the kernel id (MJH_KERNEL_*).  Returns the number of launches (<= max) or a negative code. */
 int mjh_debug_phase_timing(int enable);
 int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
@@ -468,7 +513,9 @@ void mjh_debug_set_stamps(void* dev_ptr);
 /* global-memory bytes ONE launch of kernel `kernel` (MJH_KERNEL_*) reads and writes per environment in a step (MJH_KERNEL_INVERSE: in an mjh_inverse call): the library's own
  * account of its loads / stores through the Data leaves (csrc/mjh_io.h) -- the per-kernel "algorithmic bytes" of the roofline.
  * read_write_bytes[0] = read, [1] = written.  RK4 models: the mean over the four stage launches of a step (stages 1..3 write a private
- * workspace holding only the leaves a later phase reads).  Returns 0, or -2 when this model's step does not launch that kernel. */
+ * workspace holding only the leaves a later phase reads).  MJH_KERNEL_RENDER (an mjh_render call): [0] = bytes read per environment at most (the frames
+ * of every geom, one camera's pose, the light poses), [1] = bytes written per output pixel with rgb in the model's dtype (rgb, depth, seg); -2 for a
+ * model without cameras.  Returns 0, or -2 when this model's step does not launch that kernel. */
 int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes);
 
 /* last error message of the calling thread ("" if none) */

@@ -7,6 +7,7 @@
 #include "mjh_sensor.h"
 #include "mjh_inverse.h"
 #include "mjh_ray.h"
+#include "mjh_render.h"
 #include "mjh_instances.h"
 
 #define MJH_CAT_(a, b) a##b
@@ -21,4 +22,7 @@ template __global__ void mjh_inverse_kernel<MJH_INST_REAL>(InvArgs<MJH_INST_REAL
 #endif
 #if MJH_INST_GROUP == 20
 template __global__ void mjh_ray_kernel<MJH_INST_REAL>(RayArgs<MJH_INST_REAL>);
+#endif
+#if MJH_INST_GROUP == 21
+template __global__ void mjh_render_kernel<MJH_INST_REAL>(RenderArgs<MJH_INST_REAL>);
 #endif

@@ -19,6 +19,7 @@
 #include "mjh_io.h"
 #include "mjh_inverse.h"
 #include "mjh_ray.h"
+#include "mjh_render.h"
 #include "mjh_instances.h"
 
 // the kernels are compiled in their own translation units (mjh_inst.hip, one per build group): this file is the host side only
@@ -32,6 +33,8 @@ extern template __global__ void mjh_inverse_kernel<double>(InvArgs<double>);  //
 extern template __global__ void mjh_inverse_kernel<float>(InvArgs<float>);
 extern template __global__ void mjh_ray_kernel<double>(RayArgs<double>);  // (build group 20)
 extern template __global__ void mjh_ray_kernel<float>(RayArgs<float>);
+extern template __global__ void mjh_render_kernel<double>(RenderArgs<double>);  // (build group 21)
+extern template __global__ void mjh_render_kernel<float>(RenderArgs<float>);
 #undef X_
 #undef S_
 #undef C_
@@ -1298,6 +1301,54 @@ int run_ray(const mjhModel* m, const DevModel<REAL>& M, const void* geom_xpos, c
   return 0;
 }
 
+// the ray-cast renderer (render.py:719-861): one lane per (environment, output pixel), the candidates' geom frames staged in LDS (mjh_render.h)
+template <typename REAL>
+int run_render(const DevModel<REAL>& M, const void* geom_xpos, const void* geom_xmat, const void* cam_xpos, const void* cam_xmat, const void* light_xpos,
+               const void* light_xdir, int64_t B, const mjhRenderScene* sc, const mjhRenderParams* p, void* rgb, void* depth, int64_t* seg, void* stream) {
+  if (B < 0) return fail(-22, "render: B must be >= 0");
+  if (p->width < 1 || p->height < 1 || p->ssaa < 1) return fail(-22, "render: width, height and ssaa must be >= 1");
+  if ((int64_t)p->width * p->height > (1 << 24) || (int64_t)p->ssaa * p->ssaa > 4096) return fail(-22, "render: image or super-sampling too large");
+  if (p->camera < 0 || p->camera >= M.ncam) return fail(-22, "render: camera id out of range");
+  if (sc->nlight != M.nlight) return fail(-22, "render: the light table does not match the model's nlight");
+  if (sc->ncand < 0 || sc->ncand > (1 << 30) || sc->nprim < 0 || sc->nprim > sc->ncand) return fail(-22, "render: bad candidate count");
+  if (B == 0) return 0;
+  if (!geom_xpos || !geom_xmat || !cam_xpos || !cam_xmat || !rgb || !depth || !seg || (M.nlight > 0 && (!light_xpos || !light_xdir || !sc->light)) ||
+      (sc->ncand > 0 && (!sc->cand || !sc->geom_size || !sc->geom_rgba || !sc->geom_matid)))
+    return fail(-22, "render: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  timing_begin(s);
+  RenderArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+  a.geom_xpos = reinterpret_cast<const REAL*>(geom_xpos); a.geom_xmat = reinterpret_cast<const REAL*>(geom_xmat);
+  a.cam_xpos = reinterpret_cast<const REAL*>(cam_xpos); a.cam_xmat = reinterpret_cast<const REAL*>(cam_xmat);
+  a.light_xpos = reinterpret_cast<const REAL*>(light_xpos); a.light_xdir = reinterpret_cast<const REAL*>(light_xdir);
+  a.cand = sc->cand; a.tri = reinterpret_cast<const REAL*>(sc->tri); a.geom_size = reinterpret_cast<const REAL*>(sc->geom_size);
+  a.geom_rgba = reinterpret_cast<const REAL*>(sc->geom_rgba); a.geom_matid = sc->geom_matid; a.mat_rgba = sc->mat_rgba;
+  a.light = reinterpret_cast<const REAL*>(sc->light);
+  a.rgb = rgb; a.depth = reinterpret_cast<REAL*>(depth); a.seg = seg;
+  a.half_w = (REAL)p->half_w; a.half_h = (REAL)p->half_h; a.fog_start = (REAL)p->fog_start; a.fog_range = (REAL)p->fog_range;
+  for (int k = 0; k < 3; k++) { a.fog_color[k] = (REAL)p->fog_color[k]; a.bg[k] = (float)p->background[k]; }
+  a.ngeom = M.ngeom; a.ncam = M.ncam; a.nlight = M.nlight; a.cam = p->camera; a.ncand = (int)sc->ncand; a.nprim = (int)sc->nprim;
+  a.W = p->width; a.H = p->height; a.ssaa = p->ssaa;
+  a.shade = p->shading && M.nlight > 0; a.shadows = p->shadows != 0; a.fog = p->fog != 0; a.rgb_f32 = p->rgb_f32 != 0; a.u8 = p->u8 != 0;
+  // LDS: as run_ray, with R = the output pixels of one image
+  const int64_t P = (int64_t)p->width * p->height;
+  constexpr int LDS_BUDGET = 48 * 1024;
+  const int64_t span = P >= 256 ? 2 : (255 / P + 2 < 256 ? 255 / P + 2 : 256);
+  int64_t chunk = LDS_BUDGET / (span * 12 * (int64_t)sizeof(REAL));
+  if (chunk > sc->ncand) chunk = sc->ncand;
+  if (chunk < 1) chunk = 1;
+  a.chunk = (int)chunk;
+  const size_t lds = sc->ncand > 0 ? (size_t)(span * chunk * 12 * (int64_t)sizeof(REAL)) : 0;
+  if (const int rc = launch_cut(B * P, MJH_RENDER_WG, [&](int64_t first, int64_t n, unsigned grid) {
+        a.env_base = first / P; a.r_base = (int)(first % P); a.npairs = (int)n;
+        hipLaunchKernelGGL((mjh_render_kernel<REAL>), dim3(grid), dim3(MJH_RENDER_WG), lds, s, a);
+      }))
+    return rc;
+  timing_mark(s, MJH_KERNEL_RENDER);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1345,6 +1396,14 @@ int mjh_ray(const mjhModel* m, const void* geom_xpos, const void* geom_xmat, con
   if (!m || !cands) return fail(-22, "null argument");
   return m->dtype == MJH_F64 ? run_ray<double>(m, m->m64, geom_xpos, geom_xmat, pnt, pnt_env, pnt_ray, vec, vec_env, vec_ray, B, R, cands, dist, geomid, stream)
                              : run_ray<float>(m, m->m32, geom_xpos, geom_xmat, pnt, pnt_env, pnt_ray, vec, vec_env, vec_ray, B, R, cands, dist, geomid, stream);
+}
+
+int mjh_render(const mjhModel* m, const void* geom_xpos, const void* geom_xmat, const void* cam_xpos, const void* cam_xmat, const void* light_xpos,
+               const void* light_xdir, int64_t B, const mjhRenderScene* scene, const mjhRenderParams* params, void* rgb, void* depth, int64_t* seg,
+               void* stream) {
+  if (!m || !scene || !params) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_render<double>(m->m64, geom_xpos, geom_xmat, cam_xpos, cam_xmat, light_xpos, light_xdir, B, scene, params, rgb, depth, seg, stream)
+                             : run_render<float>(m->m32, geom_xpos, geom_xmat, cam_xpos, cam_xmat, light_xpos, light_xdir, B, scene, params, rgb, depth, seg, stream);
 }
 
 int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsigned char* mask, const void* qpos_rows,
@@ -1438,6 +1497,13 @@ static int kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes, b
     return rc;
   };
   int64_t a[2] = {0, 0};
+  if (kernel == MJH_KERNEL_RENDER) {  // the renderer (mjh_render), per environment and per output pixel: see include/mjhip.h
+    const int64_t R = f64 ? 8 : 4, ng = f64 ? m->m64.ngeom : m->m32.ngeom, nc = f64 ? m->m64.ncam : m->m32.ncam, nl = f64 ? m->m64.nlight : m->m32.nlight;
+    if (nc == 0) return -2;
+    read_write_bytes[0] = (12 * ng + 12 + 6 * nl) * R;
+    read_write_bytes[1] = (3 * R + R + 8);
+    return 0;
+  }
   if (kernel == MJH_KERNEL_INVERSE) {  // the inverse-dynamics tail (mjh_inverse): efc_J and qM once, efc_D / efc_aref, qacc, qfrc_bias / passive in; efc_force, qfrc_constraint, qfrc_inverse out.
     // (the discrete branch reads qM a second time and the factor's lower triangle: not counted, it depends on the call's flags)
     const int64_t R = f64 ? 8 : 4, nv = f64 ? m->m64.nv : m->m32.nv, nefc = f64 ? m->m64.nefc : m->m32.nefc;

@@ -289,3 +289,39 @@ def _ray_leaves_vmap(info, in_dims, geom_xpos, geom_xmat, pnt, vec, model_key, s
 
 
 torch.library.register_vmap(ray_leaves, _ray_leaves_vmap)
+
+
+# ---- rendering (render.py): its own operator over the six pose leaves ------------------------------------------------------------
+
+@torch.library.custom_op("mujoco_torch_amd::render_leaves", mutates_args=())
+def render_leaves(geom_xpos: torch.Tensor, geom_xmat: torch.Tensor, cam_xpos: torch.Tensor, cam_xmat: torch.Tensor, light_xpos: torch.Tensor,
+                  light_xdir: torch.Tensor, model_key: torch.Tensor, struct_uid: str, camera_id: int, width: int, height: int, shading: bool,
+                  background: list[float], shadows: bool, fog: list[float], ssaa: int, u8: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    from .render import render_native
+
+    m = _checked_model(model_key, struct_uid, "render_leaves", "render")
+    opts = (camera_id, width, height, shading, tuple(background), shadows, tuple(fog), ssaa)
+    return render_native(m, (geom_xpos, geom_xmat, cam_xpos, cam_xmat, light_xpos, light_xdir), opts, u8)
+
+
+@render_leaves.register_fake
+def _(geom_xpos, geom_xmat, cam_xpos, cam_xmat, light_xpos, light_xdir, model_key, struct_uid, camera_id, width, height, shading, background, shadows,
+      fog, ssaa, u8):
+    from .render import check_args, rgb_dtype
+
+    m = _structure(struct_uid)
+    batch = check_args(m, (geom_xpos, geom_xmat, cam_xpos, cam_xmat, light_xpos, light_xdir))
+    opts = (camera_id, width, height, shading, tuple(background), shadows, tuple(fog), ssaa)
+    return (geom_xpos.new_empty(batch + (height, width, 3), dtype=rgb_dtype(m, geom_xpos.dtype, opts, u8)),
+            geom_xpos.new_empty(batch + (height, width)), geom_xpos.new_empty(batch + (height, width), dtype=torch.int64))
+
+
+def _render_leaves_vmap(info, in_dims, geom_xpos, geom_xmat, cam_xpos, cam_xmat, light_xpos, light_xdir, model_key, struct_uid, *opts):
+    # the mapped dimension becomes the leading batch dimension of the Data; an unmapped leaf is the same for every mapped environment
+    B = info.batch_size
+    args = [t.movedim(bd, 0) if bd is not None else t.unsqueeze(0).expand(B, *t.shape)
+            for t, bd in zip((geom_xpos, geom_xmat, cam_xpos, cam_xmat, light_xpos, light_xdir), in_dims[:6])]
+    return render_leaves(*args, model_key, struct_uid, *opts), (0, 0, 0)
+
+
+torch.library.register_vmap(render_leaves, _render_leaves_vmap)

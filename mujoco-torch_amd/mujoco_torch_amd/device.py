@@ -41,6 +41,7 @@ from ._enums import (
 )
 from .container import UnbatchedTensor
 from .ray import host_tables as ray_tables
+from .render import host_tables as render_tables
 from .types import MODEL_FIELDS, Model, Option, Statistic
 
 _cache_id_counter = itertools.count(1)
@@ -204,9 +205,10 @@ def _sensor_tables(m) -> dict:
             gtype, gbody = A("geom_type"), A("geom_bodyid")
             rgba = np.asarray(getattr(m, "geom_rgba", np.ones((int(m.ngeom), 4))))
             matid = np.asarray(getattr(m, "geom_matid", -np.ones(int(m.ngeom), dtype=np.int32)))
+            mat_rgba = np.asarray(getattr(m, "mat_rgba", np.ones((0, 4)))).reshape(-1, 4)
             for gt in _RAY_GEOM_ORDER:
                 for g in range(int(m.ngeom)):
-                    visible = (matid[g] != -1) or (rgba[g, 3] != 0)  # material alpha is not modelled by the MJCF subset
+                    visible = ((matid[g] != -1) or (rgba[g, 3] != 0)) and (matid[g] == -1 or mat_rgba[matid[g], 3] != 0)  # ray.py:417-418
                     if int(gtype[g]) == int(gt) and int(gbody[g]) != body and visible:
                         out["rf_geom"].append(g)
         out["rfadr"].append(len(out["rf_geom"]))
@@ -331,6 +333,7 @@ def _build_tables(m, dtype) -> StaticTables:
     T.nlt = len(T.tendon["lim"])  # tendon limit rows
     assert len(lim) + len(lim_ball) + T.nlt == nl, (len(lim), len(lim_ball), nl)
     T.ray = ray_tables(m)  # ray casting (ray.py): what its candidate tables are built from
+    T.render = render_tables(m)  # rendering (render.py): materials, cameras, lights
     return T
 
 

@@ -477,6 +477,7 @@ class _Compiler:
         self.settotalmass = -1.0
         self.defaults = {"main": _Defaults()}
         self.meshes = {}
+        self.materials = {}  # name -> rgba, whether it names a texture (in document order: the material ids)
         self.bodies = []  # dicts
         self.joints = []
         self.geoms = []
@@ -598,6 +599,10 @@ class _Compiler:
                 a = self._merged(mesh, dict(self.defaults["main"].get("mesh")))
                 name = a.get("name") or os.path.splitext(os.path.basename(a["file"]))[0]
                 self.meshes[name] = a
+            for mat in asset.findall("material"):  # name and rgba only: textures are not compiled (ntex = 0)
+                a = self._resolve(mat, None)
+                self.materials[a.get("name", "")] = dict(rgba=_pad(_floats(a["rgba"]), 4, [1, 1, 1, 1]) if "rgba" in a else np.ones(4),
+                                                         texture="texture" in a)
         self._parse_option()
         wb = root.find("worldbody")
         world = dict(name="world", parent=0, pos=np.zeros(3), quat=np.array([1.0, 0, 0, 0]), inertial=None, mocap=False, gravcomp=0.0, id=0, joints=[], geoms=[])
@@ -1164,7 +1169,16 @@ class _Compiler:
         deff = np.array([1.0, 0.005, 0.0001])
         m.geom_friction = np.array([_pad(_floats(g["friction"]), 3, deff) if "friction" in g else deff for g in G]).reshape(-1, 3)
         m.geom_rgba = np.array([_pad(_floats(g["rgba"]), 4, [0.5, 0.5, 0.5, 1]) if "rgba" in g else [0.5, 0.5, 0.5, 1.0] for g in G], dtype=np.float32).reshape(-1, 4)
-        m.geom_matid = -np.ones(ngeom, dtype=np.int32)
+        mat_names = list(self.materials)
+        for g in G:
+            if g.get("material") is not None and g.get("material") not in self.materials:
+                raise ValueError(f"geom {g.get('name', '')!r}: unknown material {g.get('material')!r}")
+        m.geom_matid = np.array([mat_names.index(g["material"]) if g.get("material") is not None else -1 for g in G], dtype=np.int32)
+        m.nmat = len(mat_names)
+        m.ntex = 0  # textures are not compiled: a material that names one keeps its own rgba (mat_has_texture marks it)
+        if mat_names:  # (a model without materials has no mat_rgba row to index: the reference indexes mat_rgba[geom_matid] with -1)
+            m.mat_rgba = np.array([self.materials[n]["rgba"] for n in mat_names], dtype=np.float32).reshape(-1, 4)
+        m.mat_has_texture = np.array([self.materials[n]["texture"] for n in mat_names], dtype=bool)
         m.geom_sameframe = np.zeros(ngeom, dtype=np.uint8)
         m.geom_fluid = np.zeros((ngeom, 12))
         for g in G:  # the ellipsoid fluid model (per-geom interaction coefficients) is not modelled: only the inertia-box model of option density / viscosity is

@@ -217,6 +217,22 @@ class RayCands(ctypes.Structure):
     _fields_ = [("ncand", ctypes.c_int64), ("cand", ctypes.c_void_p), ("tri", ctypes.c_void_p), ("geom_size", ctypes.c_void_p)]
 
 
+class RenderScene(ctypes.Structure):
+    """include/mjhip.h mjhRenderScene: the scene tables of one mjh_render call (device pointers)."""
+
+    _fields_ = [("ncand", ctypes.c_int64), ("nprim", ctypes.c_int64), ("cand", ctypes.c_void_p), ("tri", ctypes.c_void_p), ("geom_size", ctypes.c_void_p),
+                ("geom_rgba", ctypes.c_void_p), ("geom_matid", ctypes.c_void_p), ("mat_rgba", ctypes.c_void_p), ("nlight", ctypes.c_int64),
+                ("light", ctypes.c_void_p)]
+
+
+class RenderParams(ctypes.Structure):
+    """include/mjhip.h mjhRenderParams: one mjh_render call's settings."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("camera", "width", "height", "ssaa", "shading", "shadows", "fog", "rgb_f32", "u8", "reserved")] + [
+        ("half_w", ctypes.c_double), ("half_h", ctypes.c_double), ("background", ctypes.c_double * 3), ("fog_color", ctypes.c_double * 3),
+        ("fog_start", ctypes.c_double), ("fog_range", ctypes.c_double)]
+
+
 def load_library(path: str | None = None):
     """Loads libmjhip.so (once). Raises if it has not been built: no fallback path exists."""
     global _lib
@@ -244,6 +260,10 @@ def load_library(path: str | None = None):
                                 ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(RayCands), ctypes.c_void_p, ctypes.c_void_p,
                                 ctypes.c_void_p]
         lib.mjh_ray.restype = ctypes.c_int
+    if hasattr(lib, "mjh_render"):  # (likewise a build from before rendering)
+        lib.mjh_render.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 6 + [ctypes.c_int64, ctypes.POINTER(RenderScene), ctypes.POINTER(RenderParams),
+                                                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        lib.mjh_render.restype = ctypes.c_int
     lib.mjh_reset_where.argtypes = [ctypes.c_void_p, ctypes.POINTER(DataPtrs), ctypes.POINTER(DataPtrs), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
     lib.mjh_reset_where.restype = ctypes.c_int
     lib.mjh_debug_phase_timing.argtypes = [ctypes.c_int]

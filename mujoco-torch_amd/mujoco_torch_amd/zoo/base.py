@@ -11,7 +11,8 @@ What is different, by design:
   * a masked reset (``self._dx[mask] = self._make_batch(n)``) is ONE native launch (``reset_where``, csrc/mjh_reset.h) with
     no host sync: no ``mask.any()``, no ``int(mask.sum())``, no gather of n fresh environments.  The reset states are drawn
     for every environment (``dx0 + U(-noise, noise)``, two elementwise launches) and only the masked rows are consumed;
-  * pixels are out of scope (the ray-cast renderer is not on the hot path): ``from_pixels=True`` raises.
+  * pixel observations (``from_pixels`` / ``pixel_only``) come from ONE native render of every environment (``render``, csrc/mjh_render.h),
+    written as uint8 by the kernel, instead of a Python loop of per-environment renders.
 
 Like `step`, the masked reset exists only on a HIP device (`reset_where` raises otherwise).
 """
@@ -24,7 +25,8 @@ from abc import abstractmethod
 
 import torch
 
-from .. import device_put, make_data, mjcf, reset_where, step
+from .. import device_put, make_data, mjcf, precompute_render_data, render, reset_where, step
+from ..render import render_uint8
 from ._compat import Bounded, Composite, EnvBase, TensorDict, Unbounded  # noqa: F401
 
 _MODEL_DIR = os.environ.get(
@@ -55,13 +57,15 @@ class MujocoTorchEnv(EnvBase):
     FRAME_SKIP = 1
     ADD_FLOOR = True  # inject a ground plane when the model has none (zoo/base.py:249-254)
     CARRIED_INPUTS = ("ctrl",)  # input leaves the env edits between steps: copied into the spare buffer before a frame-skip loop
+    RENDER_BACKGROUND = (0.4, 0.6, 0.8)  # sky colour of pixel observations (zoo/base.py)
 
     def __init__(self, num_envs: int = 64, max_episode_steps: int = 1000, device=None, dtype=torch.float64,
                  compile_step: bool = False, compile_kwargs: dict | None = None, auto_reset: bool = False,
                  frame_skip: int | None = None, from_pixels: bool = False, pixel_only: bool = False,
                  render_width: int = 64, render_height: int = 64):
-        if from_pixels or pixel_only:
-            raise NotImplementedError("pixel observations need the ray-cast renderer, which is outside the stepper's scope")
+        self.from_pixels = bool(from_pixels or pixel_only)  # (the reference: pixel_only implies pixels)
+        self.pixel_only = bool(pixel_only)
+        self.render_width, self.render_height = int(render_width), int(render_height)
         # compile_step / compile_kwargs are accepted for signature compatibility: there is nothing to compile, the step
         # is already a fixed sequence of native launches
         if frame_skip is not None:
@@ -82,7 +86,12 @@ class MujocoTorchEnv(EnvBase):
             self.mx = self.mx.to(device)
         nu = int(self._m_mj.nu)
 
-        self.observation_spec = Composite(**self._obs_spec_dict(num_envs, dtype, self.device), batch_size=[num_envs])
+        obs_keys = self._obs_spec_dict(num_envs, dtype, self.device)
+        if self.from_pixels:  # zoo/base.py:100-110
+            pixels = Bounded(low=0, high=255, shape=(num_envs, self.render_height, self.render_width, 3), dtype=torch.uint8, device=self.device)
+            obs_keys = {"pixels": pixels} if self.pixel_only else dict(obs_keys, pixels=pixels)
+        self.observation_spec = Composite(**obs_keys, batch_size=[num_envs])
+        self._render_precomp = precompute_render_data(self.mx)
         low, high = self._action_range()
         self.action_spec = Bounded(low=low, high=high, shape=(num_envs, nu), dtype=dtype, device=self.device)
         self.reward_spec = Unbounded(shape=(num_envs, 1), dtype=dtype, device=self.device)
@@ -126,7 +135,20 @@ class MujocoTorchEnv(EnvBase):
         return action.to(self._ctrl_dtype)
 
     def _build_obs(self) -> dict:
-        return self._make_obs()
+        obs = {} if self.pixel_only else self._make_obs()
+        if self.from_pixels:
+            obs["pixels"] = self._render_pixels()
+        return obs
+
+    def _render_pixels(self) -> torch.Tensor:
+        """(num_envs, H, W, 3) uint8 from camera 0: one native render of every environment (zoo/base.py:205-225 loops over them)."""
+        return render_uint8(self.mx, self._dx, camera_id=0, width=self.render_width, height=self.render_height, background=self.RENDER_BACKGROUND)
+
+    def render(self, width=256, height=256, camera_id=0):
+        """Environment 0's RGB as a uint8 numpy array of shape (height, width, 3) (zoo/base.py:345-360)."""
+        rgb, _, _ = render(self.mx, self._dx[0:1], camera_id=camera_id, width=width, height=height, precomp=self._render_precomp,
+                           background=self.RENDER_BACKGROUND)
+        return (rgb[0] * 255).clamp(0, 255).to(torch.uint8).cpu().numpy()
 
     @classmethod
     def _camera_xml(cls) -> str:

@@ -176,6 +176,7 @@ class _SatelliteBase(MujocoTorchEnv):
     CTRL_COST_WEIGHT = 0.01
     ANG_VEL_WEIGHT = 0.1
     ADD_FLOOR = False  # no ground in orbit (zoo/satellite.py:52-67)
+    RENDER_BACKGROUND = (0.0, 0.0, 0.05)  # space (zoo/satellite.py:42)
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)
