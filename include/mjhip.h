@@ -11,6 +11,7 @@
  *   mjh_inverse        <- inverse.inverse(m, d)                       (_src/inverse.py:86-102)
  *   mjh_ray            <- ray.ray(m, d, pnt, vec, ...)               (_src/ray.py:375-452)
  *   mjh_render         <- render.render_batch(m, d, camera_id, ...)   (_src/render.py:719-907)
+ *   mjh_support        <- support.jac / apply_ft / xfrc_accumulate, smooth.mul_m / solve_m (_src/support.py:138-194, smooth.py:335-374)
  *
  * Conventions
  *  - every Data leaf is batch-major contiguous: shape [B, ...] exactly as
@@ -79,6 +80,11 @@ extern "C" {
 #define MJH_KERNEL_INVERSE 20    /* the inverse-dynamics tail of mjh_inverse                                          */
 #define MJH_KERNEL_RAY 21        /* the ray kernel of mjh_ray                                                         */
 #define MJH_KERNEL_RENDER 22     /* the ray-cast renderer of mjh_render                                               */
+#define MJH_KERNEL_JAC 23        /* mjh_support, MJH_SUPPORT_JAC: point Jacobians                                      */
+#define MJH_KERNEL_APPLY_FT 24   /* mjh_support, MJH_SUPPORT_APPLY_FT: Cartesian force to generalized force            */
+#define MJH_KERNEL_XFRC 25       /* mjh_support, MJH_SUPPORT_XFRC: xfrc_applied summed into a generalized force        */
+#define MJH_KERNEL_MUL_M 26      /* mjh_support, MJH_SUPPORT_MUL_M: qM products                                       */
+#define MJH_KERNEL_SOLVE_M 27    /* mjh_support, MJH_SUPPORT_SOLVE_M: solves with the factor qLD                       */
 
 /* pair-function ids of the static collision table (collision_driver.py:106-125) */
 #define MJH_FN_PLANE_SPHERE 0
@@ -481,6 +487,52 @@ int mjh_render(const mjhModel* m, const void* geom_xpos, const void* geom_xmat, 
                const void* light_xdir, int64_t B, const mjhRenderScene* scene, const mjhRenderParams* params, void* rgb, void* depth, int64_t* seg,
                void* hip_stream);
 
+/* mjh_support operations (mjhSupportArgs.op); op + MJH_KERNEL_JAC is the kernel id the timing aid reports */
+#define MJH_SUPPORT_JAC 0
+#define MJH_SUPPORT_APPLY_FT 1
+#define MJH_SUPPORT_XFRC 2
+#define MJH_SUPPORT_MUL_M 3
+#define MJH_SUPPORT_SOLVE_M 4
+
+/* one mjh_support call.  Every pointer is device memory holding reals of the model's dtype, batch-major over B environments; the leaves are a finished
+ * forward pass's: cdof [B, nv, 6], subtree_com / xipos [B, nbody, 3], xfrc_applied [B, nbody, 6], qM / qLD [B, nv, nv].  Queries are addressed in element
+ * strides (0: shared by every environment or query): query p of environment e reads point[e * point_env + p * point_q + k], k = 0..2, and likewise force /
+ * torque; vector j of environment e reads vec[e * vec_env + j * vec_k + i], i = 0..nv-1.  body_id: P body ids in [0, nbody) (body_stride 1) or one id
+ * for every query (0); the library does not validate them.  Per op, what is read and written (outputs environment-major, contiguous):
+ *   JAC       cdof, subtree_com, point, body_id  -> out0 = jacp, out1 = jacr [B, P, nv, 3]   (support.py:138-153)
+ *   APPLY_FT  the same, force, torque            -> out0 = jacp force + jacr torque [B, P, nv] (J is not formed)   (support.py:169-181)
+ *   XFRC      cdof, subtree_com, xipos, xfrc_applied -> out0 [B, nv]: apply_ft of every body's xfrc_applied at its xipos, summed in body order (:184-194)
+ *   MUL_M     qM, vec                            -> out0 [B, K, nv] = qM vec_j                  (smooth.py:370-374)
+ *   SOLVE_M   qLD (lower triangle), vec          -> out0 [B, K, nv] = (L L^T)^-1 vec_j          (smooth.py:335-338, math.py:132-168)
+ * P (JAC, APPLY_FT) and K (MUL_M, SOLVE_M) are >= 1; P * nv * 3 and K * nv must stay below 2^30. */
+typedef struct mjhSupportArgs {
+  int32_t op;
+  int32_t P, K, reserved;
+  int64_t B;
+  const void* cdof;
+  const void* subtree_com;
+  const void* xipos;
+  const void* xfrc_applied;
+  const void* qM;
+  const void* qLD;
+  const int32_t* body_id;
+  int64_t body_stride;
+  const void* point;
+  int64_t point_env, point_q;
+  const void* force;
+  int64_t force_env, force_q;
+  const void* torque;
+  int64_t torque_env, torque_q;
+  const void* vec;
+  int64_t vec_env, vec_k;
+  void* out0;
+  void* out1;
+} mjhSupportArgs;
+
+/* the support functions on a finished forward pass (see mjhSupportArgs).  Runs on hip_stream without host synchronisation.  Returns 0 or a negative
+ * code; B == 0 is a no-op. */
+int mjh_support(const mjhModel* m, const mjhSupportArgs* args, void* hip_stream);
+
 /* per-environment ELEMENT count of every mjhData leaf in ABI order (reals, then int32, then int64 leaves): a leaf handed to
  * mjh_forward / mjh_step / mjh_reset_where must hold exactly B * count elements.  The binding validates tensor sizes against
  * this before it passes raw pointers (the kernels index `ptr + env * count` unchecked).  Writes min(n, max) entries, returns n. */
@@ -501,7 +553,7 @@ int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsi
 int mjh_model_lds_bytes(const mjhModel* m, int arena);
 
 /* measurement aid used by bench.py for the per-kernel roofline: while enabled, every kernel launch of mjh_step / mjh_forward is
- * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray and mjh_render too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
+ * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render and mjh_support too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
  * the elapsed milliseconds and the kernel id (MJH_KERNEL_*).  Returns the number of launches (<= max) or a negative code. */
 int mjh_debug_phase_timing(int enable);
 int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
@@ -515,7 +567,9 @@ void mjh_debug_set_stamps(void* dev_ptr);
  * read_write_bytes[0] = read, [1] = written.  RK4 models: the mean over the four stage launches of a step (stages 1..3 write a private
  * workspace holding only the leaves a later phase reads).  MJH_KERNEL_RENDER (an mjh_render call): [0] = bytes read per environment at most (the frames
  * of every geom, one camera's pose, the light poses), [1] = bytes written per output pixel with rgb in the model's dtype (rgb, depth, seg); -2 for a
- * model without cameras.  Returns 0, or -2 when this model's step does not launch that kernel. */
+ * model without cameras.  MJH_KERNEL_JAC .. MJH_KERNEL_SOLVE_M (an mjh_support call): per environment for one query point (JAC, APPLY_FT: the dof
+ * rows, the root's subtree_com, the point, force and torque; jacp + jacr or the product), the whole sum (XFRC) or one vector (MUL_M, SOLVE_M: the matrix
+ * loaded whole, the vector, the result).  Returns 0, or -2 when this model's step does not launch that kernel. */
 int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes);
 
 /* last error message of the calling thread ("" if none) */

@@ -8,6 +8,7 @@
 #include "mjh_inverse.h"
 #include "mjh_ray.h"
 #include "mjh_render.h"
+#include "mjh_support.h"
 #include "mjh_instances.h"
 
 #define MJH_CAT_(a, b) a##b
@@ -25,4 +26,11 @@ template __global__ void mjh_ray_kernel<MJH_INST_REAL>(RayArgs<MJH_INST_REAL>);
 #endif
 #if MJH_INST_GROUP == 21
 template __global__ void mjh_render_kernel<MJH_INST_REAL>(RenderArgs<MJH_INST_REAL>);
+#endif
+#if MJH_INST_GROUP == 22
+template __global__ void mjh_sup_point_kernel<MJH_INST_REAL, true>(SupArgs<MJH_INST_REAL>);
+template __global__ void mjh_sup_point_kernel<MJH_INST_REAL, false>(SupArgs<MJH_INST_REAL>);
+template __global__ void mjh_sup_xfrc_kernel<MJH_INST_REAL>(SupArgs<MJH_INST_REAL>);
+template __global__ void mjh_sup_mulm_kernel<MJH_INST_REAL>(SupArgs<MJH_INST_REAL>);
+template __global__ void mjh_sup_solvem_kernel<MJH_INST_REAL>(SupArgs<MJH_INST_REAL>);
 #endif

@@ -20,6 +20,7 @@
 #include "mjh_inverse.h"
 #include "mjh_ray.h"
 #include "mjh_render.h"
+#include "mjh_support.h"
 #include "mjh_instances.h"
 
 // the kernels are compiled in their own translation units (mjh_inst.hip, one per build group): this file is the host side only
@@ -35,6 +36,15 @@ extern template __global__ void mjh_ray_kernel<double>(RayArgs<double>);  // (bu
 extern template __global__ void mjh_ray_kernel<float>(RayArgs<float>);
 extern template __global__ void mjh_render_kernel<double>(RenderArgs<double>);  // (build group 21)
 extern template __global__ void mjh_render_kernel<float>(RenderArgs<float>);
+#define SUP_(R)                                                                                                    \
+  extern template __global__ void mjh_sup_point_kernel<R, true>(SupArgs<R>);                                       \
+  extern template __global__ void mjh_sup_point_kernel<R, false>(SupArgs<R>);                                      \
+  extern template __global__ void mjh_sup_xfrc_kernel<R>(SupArgs<R>);                                              \
+  extern template __global__ void mjh_sup_mulm_kernel<R>(SupArgs<R>);                                              \
+  extern template __global__ void mjh_sup_solvem_kernel<R>(SupArgs<R>);
+SUP_(double)  // (build group 22)
+SUP_(float)
+#undef SUP_
 #undef X_
 #undef S_
 #undef C_
@@ -1349,6 +1359,73 @@ int run_render(const DevModel<REAL>& M, const void* geom_xpos, const void* geom_
   return 0;
 }
 
+// the support functions (support.py:138-194, smooth.py:335-374) on a finished forward pass' leaves (mjh_support.h)
+template <typename REAL>
+int run_support(const mjhModel* m, const DevModel<REAL>& M, const mjhSupportArgs* x, void* stream) {
+  (void)m;
+  const int op = x->op, nv = M.nv;
+  if (op < MJH_SUPPORT_JAC || op > MJH_SUPPORT_SOLVE_M) return fail(-22, "support: unknown op");
+  if (x->B < 0) return fail(-22, "support: B must be >= 0");
+  const bool pt = op == MJH_SUPPORT_JAC || op == MJH_SUPPORT_APPLY_FT, mv = op == MJH_SUPPORT_MUL_M || op == MJH_SUPPORT_SOLVE_M;
+  if (pt && (x->P < 1 || (int64_t)x->P * nv * 3 >= (1 << 30))) return fail(-22, "support: bad query count P");
+  if (mv && (x->K < 1 || (int64_t)x->K * nv >= (1 << 30))) return fail(-22, "support: bad vector count K");
+  if (pt && x->body_stride != 0 && x->body_stride != 1) return fail(-22, "support: body_stride must be 0 or 1");
+  if (x->B == 0 || nv == 0) return 0;
+  if (!x->out0 || (op == MJH_SUPPORT_JAC && !x->out1) || ((pt || op == MJH_SUPPORT_XFRC) && (!x->cdof || !x->subtree_com)) ||
+      (pt && (!x->body_id || !x->point)) || (op == MJH_SUPPORT_APPLY_FT && (!x->force || !x->torque)) ||
+      (op == MJH_SUPPORT_XFRC && (!x->xipos || !x->xfrc_applied)) || (op == MJH_SUPPORT_MUL_M && !x->qM) || (op == MJH_SUPPORT_SOLVE_M && !x->qLD) ||
+      (mv && !x->vec))
+    return fail(-22, "support: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  timing_begin(s);
+  SupArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+  a.cdof = reinterpret_cast<const REAL*>(x->cdof); a.subtree_com = reinterpret_cast<const REAL*>(x->subtree_com);
+  a.xipos = reinterpret_cast<const REAL*>(x->xipos); a.xfrc = reinterpret_cast<const REAL*>(x->xfrc_applied);
+  a.mat = reinterpret_cast<const REAL*>(op == MJH_SUPPORT_MUL_M ? x->qM : x->qLD);
+  a.point = reinterpret_cast<const REAL*>(x->point); a.force = reinterpret_cast<const REAL*>(x->force);
+  a.torque = reinterpret_cast<const REAL*>(x->torque); a.vec = reinterpret_cast<const REAL*>(x->vec);
+  a.body = x->body_id; a.body_stride = (int)x->body_stride;
+  a.body_dofmask = M.body_dofmask; a.body_rootid = M.body_rootid;
+  a.out0 = reinterpret_cast<REAL*>(x->out0); a.out1 = reinterpret_cast<REAL*>(x->out1);
+  a.point_env = x->point_env; a.point_q = x->point_q; a.force_env = x->force_env; a.force_q = x->force_q;
+  a.torque_env = x->torque_env; a.torque_q = x->torque_q; a.vec_env = x->vec_env; a.vec_k = x->vec_k;
+  a.nv = nv; a.nbody = M.nbody; a.mask_words = M.mask_words; a.P = x->P; a.K = x->K;
+  if (pt || op == MJH_SUPPORT_XFRC) {  // one lane per output element; a launch starts at (env_base, r_base) so that the lanes index in 32 bits
+    const int64_t per_env = op == MJH_SUPPORT_JAC ? (int64_t)x->P * nv * 3 : op == MJH_SUPPORT_APPLY_FT ? (int64_t)x->P * nv : nv;
+    const int rc = launch_cut(x->B * per_env, MJH_SUP_WG, [&](int64_t first, int64_t n, unsigned grid) {
+      a.env_base = first / per_env; a.r_base = (int)(first % per_env); a.count = (int)n;
+      if (op == MJH_SUPPORT_JAC) hipLaunchKernelGGL((mjh_sup_point_kernel<REAL, true>), dim3(grid), dim3(MJH_SUP_WG), 0, s, a);
+      else if (op == MJH_SUPPORT_APPLY_FT) hipLaunchKernelGGL((mjh_sup_point_kernel<REAL, false>), dim3(grid), dim3(MJH_SUP_WG), 0, s, a);
+      else hipLaunchKernelGGL((mjh_sup_xfrc_kernel<REAL>), dim3(grid), dim3(MJH_SUP_WG), 0, s, a);
+    });
+    if (rc) return rc;
+  } else {  // one wavefront per environment, the matrix staged in LDS
+    constexpr int64_t kChunkBytes = 32 * 1024, kVecBytes = 16 * 1024, kMaxLds = 160 * 1024;
+    const int64_t rb = (int64_t)nv * sizeof(REAL);
+    int64_t lds;
+    if (op == MJH_SUPPORT_MUL_M) {  // qM rows per chunk
+      int64_t c = kChunkBytes / rb;
+      a.chunk = (int)(c < 1 ? 1 : (c > nv ? nv : c));
+      lds = a.chunk * rb;
+    } else {  // the packed triangle + vectors per chunk
+      int64_t c = kVecBytes / rb;
+      a.chunk = (int)(c < 1 ? 1 : (c > x->K ? x->K : c));
+      lds = ((int64_t)nv * (nv + 1) / 2 + (int64_t)a.chunk * nv) * sizeof(REAL);
+      if (lds > kMaxLds) return fail(-22, "support: solve_m needs more LDS than a workgroup has (nv too large)");
+      if (lds > 64 * 1024) HIP_TRY(allow_lds(&mjh_sup_solvem_kernel<REAL>, (int)lds));
+    }
+    const int rc = launch_cut(x->B, 1, [&](int64_t first, int64_t, unsigned grid) {
+      a.env_base = first;
+      if (op == MJH_SUPPORT_MUL_M) hipLaunchKernelGGL((mjh_sup_mulm_kernel<REAL>), dim3(grid), dim3(MJH_WAVE), (size_t)lds, s, a);
+      else hipLaunchKernelGGL((mjh_sup_solvem_kernel<REAL>), dim3(grid), dim3(MJH_WAVE), (size_t)lds, s, a);
+    });
+    if (rc) return rc;
+  }
+  timing_mark(s, MJH_KERNEL_JAC + op);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1404,6 +1481,11 @@ int mjh_render(const mjhModel* m, const void* geom_xpos, const void* geom_xmat, 
   if (!m || !scene || !params) return fail(-22, "null argument");
   return m->dtype == MJH_F64 ? run_render<double>(m->m64, geom_xpos, geom_xmat, cam_xpos, cam_xmat, light_xpos, light_xdir, B, scene, params, rgb, depth, seg, stream)
                              : run_render<float>(m->m32, geom_xpos, geom_xmat, cam_xpos, cam_xmat, light_xpos, light_xdir, B, scene, params, rgb, depth, seg, stream);
+}
+
+int mjh_support(const mjhModel* m, const mjhSupportArgs* args, void* stream) {
+  if (!m || !args) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_support<double>(m, m->m64, args, stream) : run_support<float>(m, m->m32, args, stream);
 }
 
 int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsigned char* mask, const void* qpos_rows,
@@ -1502,6 +1584,14 @@ static int kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes, b
     if (nc == 0) return -2;
     read_write_bytes[0] = (12 * ng + 12 + 6 * nl) * R;
     read_write_bytes[1] = (3 * R + R + 8);
+    return 0;
+  }
+  if (kernel >= MJH_KERNEL_JAC && kernel <= MJH_KERNEL_SOLVE_M) {  // the support kernels (mjh_support), per environment: see include/mjhip.h
+    const int64_t R = f64 ? 8 : 4, nv = f64 ? m->m64.nv : m->m32.nv, nb = f64 ? m->m64.nbody : m->m32.nbody;
+    if (nv == 0) return -2;
+    const int64_t io[5][2] = {{6 * nv + 3 + 3, 6 * nv}, {6 * nv + 3 + 9, nv}, {6 * nv + 3 * nb + 3 * nb + 6 * nb, nv}, {nv * nv + nv, nv}, {nv * nv + nv, nv}};
+    read_write_bytes[0] = io[kernel - MJH_KERNEL_JAC][0] * R;
+    read_write_bytes[1] = io[kernel - MJH_KERNEL_JAC][1] * R;
     return 0;
   }
   if (kernel == MJH_KERNEL_INVERSE) {  // the inverse-dynamics tail (mjh_inverse): efc_J and qM once, efc_D / efc_aref, qacc, qfrc_bias / passive in; efc_force, qfrc_constraint, qfrc_inverse out.

@@ -223,6 +223,29 @@ class ObjType(enum.IntEnum):
     TENDON = 18
 
 
+class ConstraintType(enum.IntEnum):
+    """mjtConstraint (reference types.py:353-375): the type of an efc row."""
+
+    EQUALITY = 0
+    FRICTION_DOF = 1
+    FRICTION_TENDON = 2
+    LIMIT_JOINT = 3
+    LIMIT_TENDON = 4
+    CONTACT_FRICTIONLESS = 5
+    CONTACT_PYRAMIDAL = 6
+    CONTACT_ELLIPTIC = 7
+
+
+class WrapType(enum.IntEnum):
+    """mjtWrap (reference types.py:273-289): the type of a tendon wrap object."""
+
+    JOINT = 1
+    PULLEY = 2
+    SITE = 3
+    SPHERE = 4
+    CYLINDER = 5
+
+
 # Sets the stepper supports (reference device.py:919-949 raises for the rest).
 SUPPORTED_INTEGRATORS = (IntegratorType.EULER, IntegratorType.RK4)
 SUPPORTED_SOLVERS = (SolverType.CG, SolverType.NEWTON)

@@ -325,3 +325,34 @@ def _render_leaves_vmap(info, in_dims, geom_xpos, geom_xmat, cam_xpos, cam_xmat,
 
 
 torch.library.register_vmap(render_leaves, _render_leaves_vmap)
+
+
+# ---- the support functions (support.py): one operator for the five ops, over the leaves each reads and its queries ---------------
+
+@torch.library.custom_op("mujoco_torch_amd::support_leaves", mutates_args=())
+def support_leaves(op: int, leaves: list[torch.Tensor], queries: list[torch.Tensor], model_key: torch.Tensor, struct_uid: str, body_ids: list[int],
+                   listed: bool) -> list[torch.Tensor]:
+    from .support import support_native
+
+    m = _checked_model(model_key, struct_uid, "support_leaves", "support function")
+    return support_native(m, op, leaves, queries, tuple(body_ids), listed)
+
+
+@support_leaves.register_fake
+def _(op, leaves, queries, model_key, struct_uid, body_ids, listed):
+    from .support import plan
+
+    return [leaves[0].new_empty(s) for s in plan(op, leaves, queries, tuple(body_ids), listed)[3]]
+
+
+def _support_leaves_vmap(info, in_dims, op, leaves, queries, model_key, struct_uid, body_ids, listed):
+    # the mapped dimension becomes the leading batch dimension of the Data; an unmapped leaf is broadcast, an unmapped query keeps its meaning:
+    # a 1-D one stays shared, anything else is the same for every mapped environment
+    B = info.batch_size
+    lv = [t.movedim(bd, 0) if bd is not None else t.unsqueeze(0).expand(B, *t.shape) for t, bd in zip(leaves, in_dims[1])]
+    qs = [t.movedim(bd, 0) if bd is not None else (t if t.dim() == 1 else t.unsqueeze(0).expand(B, *t.shape)) for t, bd in zip(queries, in_dims[2])]
+    outs = support_leaves(op, lv, qs, model_key, struct_uid, body_ids, listed)
+    return outs, [0] * len(outs)
+
+
+torch.library.register_vmap(support_leaves, _support_leaves_vmap)

@@ -233,6 +233,15 @@ class RenderParams(ctypes.Structure):
         ("fog_start", ctypes.c_double), ("fog_range", ctypes.c_double)]
 
 
+class SupportArgs(ctypes.Structure):
+    """include/mjhip.h mjhSupportArgs: one mjh_support call (device pointers, element strides)."""
+
+    _fields_ = [("op", ctypes.c_int32), ("P", ctypes.c_int32), ("K", ctypes.c_int32), ("reserved", ctypes.c_int32), ("B", ctypes.c_int64)] + [
+        (n, ctypes.c_void_p) for n in ("cdof", "subtree_com", "xipos", "xfrc_applied", "qM", "qLD", "body_id")] + [("body_stride", ctypes.c_int64)] + [
+        f for n in ("point", "force", "torque") for f in ((n, ctypes.c_void_p), (n + "_env", ctypes.c_int64), (n + "_q", ctypes.c_int64))] + [
+        ("vec", ctypes.c_void_p), ("vec_env", ctypes.c_int64), ("vec_k", ctypes.c_int64), ("out0", ctypes.c_void_p), ("out1", ctypes.c_void_p)]
+
+
 def load_library(path: str | None = None):
     """Loads libmjhip.so (once). Raises if it has not been built: no fallback path exists."""
     global _lib
@@ -264,6 +273,9 @@ def load_library(path: str | None = None):
         lib.mjh_render.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 6 + [ctypes.c_int64, ctypes.POINTER(RenderScene), ctypes.POINTER(RenderParams),
                                                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         lib.mjh_render.restype = ctypes.c_int
+    if hasattr(lib, "mjh_support"):  # (likewise a build from before the support functions)
+        lib.mjh_support.argtypes = [ctypes.c_void_p, ctypes.POINTER(SupportArgs), ctypes.c_void_p]
+        lib.mjh_support.restype = ctypes.c_int
     lib.mjh_reset_where.argtypes = [ctypes.c_void_p, ctypes.POINTER(DataPtrs), ctypes.POINTER(DataPtrs), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
     lib.mjh_reset_where.restype = ctypes.c_int
     lib.mjh_debug_phase_timing.argtypes = [ctypes.c_int]
