@@ -1,6 +1,7 @@
 """The support functions on the GPU: ``jac`` / ``apply_ft`` / ``xfrc_accumulate`` / ``mul_m`` / ``solve_m`` against the reference's own
 (tests/golden/support/, tools/gen_support_golden.py; the recorded leaves are fed in), their shape forms, consistency between them, zero rows,
-batch shapes, value edits, no mutation of the input, and the vmap / compile operator."""
+batch shapes, value edits, no mutation of the input, and the vmap / compile operator.  tests/test_support_edges.py goes past the goldens: launches cut on
+the host, more vectors / rows than an LDS chunk, every body of the float32 and the large models, derived error bounds (tests/_support_ref.py)."""
 import json
 import os
 

@@ -128,3 +128,68 @@ def test_the_support_operator_traces_to_its_output_shapes(hum):
         assert plan(1, [cdof, com], [torch.zeros(3), torch.zeros(4, 2, 3), torch.zeros(4, 3)], (5,), False)[3] == [(4, 2, nv)]
         assert plan(3, [fm.from_tensor(d.qM)], [torch.zeros(4, 3, nv)], (0,), False)[3] == [(4, 3, nv)]
         assert plan(4, [fm.from_tensor(d.qLD)], [torch.zeros(nv)], (0,), False)[3] == [(4, nv)]
+
+
+# ---- the tests' own numpy reference (tests/_support_ref.py), pinned on the reference project's recorded outputs -----------------------
+
+SUP_GOLD = os.path.join(GOLD, "support")
+SUP_CASES = sorted(f[:-4] for f in os.listdir(SUP_GOLD) if f.endswith(".npz"))
+
+
+def _within(got, want, allowed, what):
+    """|got - want| <= allowed per element, the difference taken in the reference module's high precision."""
+    import _support_ref as ref
+
+    err = np.abs(np.asarray(got, dtype=ref.HP) - np.asarray(want, dtype=ref.HP)).astype(np.float64)
+    allowed = np.asarray(allowed, dtype=np.float64)
+    assert err.shape == allowed.shape, (what, err.shape, allowed.shape)
+    over = err > allowed
+    i = np.unravel_index(np.argmax(err - allowed), err.shape) if err.size else ()
+    assert not over.any(), f"{what}: {int(over.sum())} of {err.size} elements beyond their bound; worst at {i}: error {err[i]:.3e}, bound {allowed[i]:.3e}"
+    return float((err / np.maximum(allowed, 1e-300)).max(initial=0.0))
+
+
+@pytest.mark.parametrize("case", SUP_CASES)
+def test_the_numpy_reference_matches_the_recorded_outputs(case):
+    """tests/_support_ref.py against the 7 goldens of the reference project, before it is trusted on the device.  jac_same (the same-dtype
+    evaluation with the mask walked from body_parentid) reproduces the recorded jacp / jacr exactly; the high-precision functions agree with the
+    recorded apply_ft / xfrc_accumulate / mul_m within (n + 2) eps S_abs, where n counts the terms of the element's sum plus the roundings its
+    inputs have taken (apply_ft: 6 products of entries that carry JACP_ROUNDINGS = 4 roundings each, n = 10; xfrc_accumulate: the same over
+    all bodies, n = 6 nbody + 4; mul_m: nv products of exact inputs, n = nv; jacp itself: 3 terms and the offset's rounding, n = 4; S_abs is
+    formed from the unrounded high-precision elementary terms), and the recorded solve_m within the two-substitution residual bound and
+    the forward bound it implies.  That the reference's own float32 and float64 results stay inside them is what makes the bounds usable on the device."""
+    import _support_ref as ref
+
+    assert len(SUP_CASES) == 7
+    z = np.load(os.path.join(SUP_GOLD, case + ".npz"))
+    meta = json.loads(str(z["meta"]))
+    a = {k: np.stack([z[f"{e}/{k}"] for e in range(meta["nenv"])]) for k in sorted({f.split("/", 1)[1] for f in z.files if "/" in f})}
+    dtype = getattr(torch, meta["dtype"])
+    eps = torch.finfo(dtype).eps
+    mx = load_model(meta["xml"], dtype=dtype)
+    nv, nb, ids = int(mx.nv), int(mx.nbody), meta["body_id"]
+    assert (nv, nb) == (meta["nv"], meta["nbody"]) and a["cdof"].dtype == np.dtype(meta["dtype"])
+    root = np.asarray(mx.body_rootid)
+    mask = ref.ancestor_mask(mx.body_parentid, mx.dof_bodyid)
+    assert mask.shape == (nb, nv) and not mask[0].any()
+    geo = (a["cdof"], a["subtree_com"], root, mask)
+
+    jp, jr = ref.jac_same(*geo, a["point"], ids)
+    assert jp.dtype == a["jacp"].dtype and np.array_equal(jp, a["jacp"]) and np.array_equal(jr, a["jacr"]), case
+    (hp, ap), (hr, ar) = ref.jac_hp(*geo, a["point"], ids)
+    _within(a["jacp"], hp, ref.bound(4, eps, ap), f"{case} jacp")
+    assert np.array_equal(np.asarray(a["jacr"], dtype=ref.HP), hr)  # a copy of cdof or zero: no rounding at all
+
+    val, s = ref.apply_ft_hp(*geo, a["point"], a["force"], a["torque"], ids)
+    _within(a["apply_ft"], val, ref.bound(6 + ref.JACP_ROUNDINGS, eps, s), f"{case} apply_ft")
+    val, s = ref.xfrc_hp(a["cdof"], a["subtree_com"], a["xipos"], a["xfrc_applied"], root, mask)
+    _within(a["xfrc_accumulate"], val, ref.bound(6 * nb + ref.JACP_ROUNDINGS, eps, s), f"{case} xfrc_accumulate")
+    val, s = ref.mul_m_hp(a["qM"], a["vec"])
+    _within(a["mul_m"], val, ref.bound(nv, eps, s), f"{case} mul_m")
+
+    res, scale = ref.solve_m_residual(a["qLD"], a["vec"], a["solve_m"])
+    _within(res, np.zeros_like(res), ref.solve_m_factor(nv, eps) * scale, f"{case} solve_m residual")
+    x, _ = ref.solve_m_hp(a["qLD"], a["vec"])
+    _within(a["solve_m"], x, ref.solve_m_forward_bound(a["qLD"], a["solve_m"], eps), f"{case} solve_m")
+    res, scale = ref.solve_m_residual(a["qLD"], a["vec"], x)  # ... and the substitution of the reference module solves the system it states
+    _within(res, np.zeros_like(res), ref.solve_m_factor(nv, ref.EPS_HP) * scale, f"{case} solve_m_hp residual")
