@@ -11,6 +11,7 @@
  *   mjh_inverse        <- inverse.inverse(m, d)                       (_src/inverse.py:86-102)
  *   mjh_ray            <- ray.ray(m, d, pnt, vec, ...)               (_src/ray.py:375-452)
  *   mjh_render         <- render.render_batch(m, d, camera_id, ...)   (_src/render.py:719-907)
+ *   mjh_fd_perturb / mjh_fd_difference <- the two ends of a finite-difference transition Jacobian (MuJoCo's mjd_transitionFD; the reference has no counterpart)
  *   mjh_support        <- support.jac / apply_ft / xfrc_accumulate, smooth.mul_m / solve_m (_src/support.py:138-194, smooth.py:335-374)
  *
  * Conventions
@@ -37,7 +38,7 @@
 extern "C" {
 #endif
 
-#define MJH_ABI_VERSION 14
+#define MJH_ABI_VERSION 15
 
 /* ---- dtype / flags ------------------------------------------------------------------- */
 #define MJH_F64 0
@@ -85,6 +86,8 @@ extern "C" {
 #define MJH_KERNEL_XFRC 25       /* mjh_support, MJH_SUPPORT_XFRC: xfrc_applied summed into a generalized force        */
 #define MJH_KERNEL_MUL_M 26      /* mjh_support, MJH_SUPPORT_MUL_M: qM products                                       */
 #define MJH_KERNEL_SOLVE_M 27    /* mjh_support, MJH_SUPPORT_SOLVE_M: solves with the factor qLD                       */
+#define MJH_KERNEL_FD_PERTURB 28 /* mjh_fd_perturb: the perturbed input leaves of a chunk of finite-difference columns */
+#define MJH_KERNEL_FD_DIFFERENCE 29 /* mjh_fd_difference: the columns of A, B, C, D from the stepped chunk            */
 
 /* pair-function ids of the static collision table (collision_driver.py:106-125) */
 #define MJH_FN_PLANE_SPHERE 0
@@ -533,6 +536,27 @@ typedef struct mjhSupportArgs {
  * code; B == 0 is a no-op. */
 int mjh_support(const mjhModel* m, const mjhSupportArgs* args, void* hip_stream);
 
+/* Finite-difference transition Jacobians (MuJoCo's mjd_transitionFD), as two launches around an mjh_step of the caller's own.  State x = (qpos in
+ * tangent space: nv, qvel: nv, act: na), ns = 2 nv + na; column c in [0, ns) nudges entry c of x, column ns + i nudges ctrl[i].  A call serves the
+ * columns [col0, col0 + ncol) of all B environments.  Each column of an environment owns nside = (centered ? 2 : 1) environments ("slots") of a
+ * scratch batch of B * ncol * nside environments, slot (e * ncol + (c - col0)) * nside + side; side 0 carries the nudge +eps, side 1 the nudge -eps.
+ * A ctrl nudge is taken only if ctrl and the nudged ctrl both lie inside actuator_ctrlrange when actuator_ctrllimited; the backward one only when
+ * centered or when the forward one was refused.  One-sided, the single slot of a ctrl column carries the forward nudge if taken, else the backward
+ * one, else ctrl unchanged; centered, a refused side carries ctrl unchanged.
+ *
+ * mjh_fd_perturb: for every slot, copies every leaf that is non-NULL in `scratch` from environment e of `in` (which must carry it) and applies the
+ * slot's nudge: addition, or for the rotational dofs of ball / free joints the rotation of the quaternion by eps about the dof's local axis
+ * (quat_integrate, math.py:377).  scratch.qpos / qvel must be non-NULL, act / ctrl when na / nu > 0.
+ * mjh_fd_difference: reads qpos / qvel / act (and sensordata when C, D are given) of `nominal` (the step of `in`, B environments) and of `stepped`
+ * (the step of the scratch batch) and in.ctrl, and writes the columns [col0, col0 + ncol) of A [B, ns, ns] and Bm [B, ns, nu] (C [B, nsensordata, ns],
+ * D [B, nsensordata, nu]; both NULL or both given): rows = next state, qpos rows differenced in tangent space (subtraction, or the rotation vector
+ * of q0^-1 q1, math.py:276).  One side: (y+ - y0) / eps or (y0 - y-) / eps; centered state columns: (y+ - y-) / (2 eps); a ctrl column with both
+ * sides: the mean of the two one-sided differences; with neither: zeros.  Bm / D may be NULL when nu == 0.
+ * Both run on hip_stream without host synchronisation; eps is rounded to the model's dtype.  Return 0 or a negative code; B == 0 is a no-op. */
+int mjh_fd_perturb(const mjhModel* m, const mjhData* in, mjhData* scratch, int64_t B, int col0, int ncol, double eps, int centered, void* hip_stream);
+int mjh_fd_difference(const mjhModel* m, const mjhData* in, const mjhData* nominal, const mjhData* stepped, int64_t B, int col0, int ncol, double eps,
+                      int centered, void* A, void* Bm, void* C, void* D, void* hip_stream);
+
 /* per-environment ELEMENT count of every mjhData leaf in ABI order (reals, then int32, then int64 leaves): a leaf handed to
  * mjh_forward / mjh_step / mjh_reset_where must hold exactly B * count elements.  The binding validates tensor sizes against
  * this before it passes raw pointers (the kernels index `ptr + env * count` unchecked).  Writes min(n, max) entries, returns n. */
@@ -553,7 +577,7 @@ int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsi
 int mjh_model_lds_bytes(const mjhModel* m, int arena);
 
 /* measurement aid used by bench.py for the per-kernel roofline: while enabled, every kernel launch of mjh_step / mjh_forward is
- * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render and mjh_support too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
+ * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb and mjh_fd_difference too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
  * the elapsed milliseconds and the kernel id (MJH_KERNEL_*).  Returns the number of launches (<= max) or a negative code. */
 int mjh_debug_phase_timing(int enable);
 int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
@@ -569,7 +593,8 @@ void mjh_debug_set_stamps(void* dev_ptr);
  * of every geom, one camera's pose, the light poses), [1] = bytes written per output pixel with rgb in the model's dtype (rgb, depth, seg); -2 for a
  * model without cameras.  MJH_KERNEL_JAC .. MJH_KERNEL_SOLVE_M (an mjh_support call): per environment for one query point (JAC, APPLY_FT: the dof
  * rows, the root's subtree_com, the point, force and torque; jacp + jacr or the product), the whole sum (XFRC) or one vector (MUL_M, SOLVE_M: the matrix
- * loaded whole, the vector, the result).  Returns 0, or -2 when this model's step does not launch that kernel. */
+ * loaded whole, the vector, the result).  MJH_KERNEL_FD_PERTURB / MJH_KERNEL_FD_DIFFERENCE: per slot, the input leaves a step of this model can read,
+ * read and written (an upper bound: the caller's Data may lack some), and one slot's qpos, qvel, act and sensordata read, with [1] = one column of A and C.  Returns 0, or -2 when this model's step does not launch that kernel. */
 int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes);
 
 /* last error message of the calling thread ("" if none) */

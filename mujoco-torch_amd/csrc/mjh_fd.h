@@ -1,0 +1,183 @@
+// mjh_fd.h -- the two kernels around the steps of a finite-difference transition Jacobian (mjh_fd_perturb, mjh_fd_difference; MuJoCo's
+// mjd_transitionFD).  The steps themselves are plain mjh_step calls over the perturbed environments.
+//
+// Columns: c in [0, nv) nudges qpos along dof c (tangent space), [nv, 2 nv) qvel, [2 nv, ns) act, ns = 2 nv + na, and [ns, ns + nu) ctrl.  A call
+// serves the columns [col0, col0 + ncol) of every environment.  Column c of environment e owns nside (1, centered: 2) perturbed environments,
+// "slots", at index  w = (e * ncol + (c - col0)) * nside + side  of the scratch batch: environment-major, so every leaf of the scratch batch is
+// written and read in address order.  Which column a slot is, and which way it is nudged, is decoded from w here: there is no column list in memory.
+//
+// mjh_fd_perturb_kernel: one workgroup per slot.  It streams every listed input leaf of environment e into slot w (4-byte words, consecutive lanes on
+//   consecutive addresses), then one lane nudges the slot's entry: x + h for qvel / act / ctrl and slide / hinge / free-translation dofs;
+//   quat_integrate(q, e_k, h) (mjh_device.h, forward.py:231-252) for the rotational dofs of ball / free joints; h = +eps on side 0, -eps on side 1.
+// ctrl (fd_ctrl_sides): with actuator_ctrllimited, a nudge is taken only when ctrl and the nudged ctrl both lie inside actuator_ctrlrange; the
+//   backward nudge only when centered or when the forward one was refused.  One-sided, the single slot carries the forward nudge, else the backward
+//   one, else the caller's ctrl unchanged; centered, a refused side carries it unchanged.  The flags depend on each environment's own ctrl and are
+//   formed again, from the same values by the same function, in the difference kernel.
+// mjh_fd_difference_kernel: one lane per (environment, row, column of the chunk), column fastest, so that a wave's stores run along a row of A / B /
+//   C / D for as many columns as the chunk holds.  Rows [0, nv): qpos differenced in tangent space -- subtraction, or quat_sub(q1, q0), the rotation
+//   vector of q0^-1 q1 -- then qvel, act and, with C / D, sensordata.  Forward (y+ - y0) / eps, backward (y0 - y-) / eps, centered state columns
+//   (y+ - y-) / (2 eps); a ctrl column with both sides taken is the mean of its forward and backward difference; with none, zero.
+// Both move far fewer bytes than the steps between them (a slot's inputs and four of its output leaves against the ~50 KB a humanoid step writes).
+#pragma once
+#include "mjh_device.h"
+
+#define MJH_FD_PERTURB_WG 64
+#define MJH_FD_DIFF_WG 256
+#define MJH_FD_MAX_LEAVES 24
+
+struct FdLeaf {
+  unsigned* dst;        // [slots, words]
+  const unsigned* src;  // [B, words]
+  int words;            // 4-byte words per environment
+  int pad_;
+};
+
+// what both kernels read of the model and of the call
+template <typename REAL>
+struct FdCommon {
+  const int *dof_jntid, *jnt_type, *jnt_qposadr, *jnt_dofadr, *act_ctrllimited;
+  const REAL* act_ctrlrange;
+  const REAL* ctrl;     // the caller's [B, nu]
+  REAL eps;
+  int nq, nv, na, nu, nsd;
+  int centered, col0, ncol;
+  int64_t first;        // first unit (slot / output element) of this launch
+  int64_t total;        // units of the call
+};
+
+template <typename REAL>
+struct FdPerturbArgs {
+  FdCommon<REAL> c;
+  const REAL *qpos, *qvel, *act;          // the caller's
+  REAL *p_qpos, *p_qvel, *p_act, *p_ctrl; // the scratch batch's
+  int nleaf, pad_;
+  FdLeaf leaf[MJH_FD_MAX_LEAVES];
+};
+
+template <typename REAL>
+struct FdState {
+  const REAL *qpos, *qvel, *act, *sens;
+};
+
+template <typename REAL>
+struct FdDiffArgs {
+  FdCommon<REAL> c;
+  FdState<REAL> y0;  // the nominal step's result [B, ...]
+  FdState<REAL> y;   // the perturbed steps' results [slots, ...]
+  REAL *A, *Bm, *C, *D;
+};
+
+// bit 0: the forward nudge is taken, bit 1: the backward one
+template <typename REAL>
+__device__ __forceinline__ int fd_ctrl_sides(const FdCommon<REAL>& c, int64_t e, int i) {
+  const bool lim = c.act_ctrllimited[i] != 0;
+  const REAL u = c.ctrl[e * c.nu + i], lo = c.act_ctrlrange[2 * i], hi = c.act_ctrlrange[2 * i + 1];
+  const REAL up = u + c.eps, um = u - c.eps;
+  const bool in0 = u >= lo && u <= hi;
+  const bool fwd = !lim || (in0 && up >= lo && up <= hi);
+  const bool bwd = (c.centered || !fwd) && (!lim || (in0 && um >= lo && um <= hi));
+  return (fwd ? 1 : 0) | (bwd ? 2 : 0);
+}
+
+// where dof d lives in qpos: its joint's type, the address of the entry (or of the quaternion) and, for a rotational dof, its axis (else -1)
+__device__ __forceinline__ void fd_dof(const int* dof_jntid, const int* jnt_type, const int* jnt_qposadr, const int* jnt_dofadr, int d, int& adr, int& axis) {
+  const int j = dof_jntid[d], t = jnt_type[j], qa = jnt_qposadr[j], k = d - jnt_dofadr[j];
+  if (t == JNT_FREE && k >= 3) { adr = qa + 3; axis = k - 3; }
+  else if (t == JNT_BALL) { adr = qa; axis = k; }
+  else { adr = qa + k; axis = -1; }
+}
+
+template <typename REAL>
+__global__ __launch_bounds__(MJH_FD_PERTURB_WG) void mjh_fd_perturb_kernel(FdPerturbArgs<REAL> a) {
+  const FdCommon<REAL>& c = a.c;
+  const int64_t w = c.first + blockIdx.x;
+  if (w >= c.total) return;
+  const int nside = c.centered ? 2 : 1, nslot = c.ncol * nside;
+  const int64_t e = w / nslot;
+  const int sl = (int)(w - e * nslot);
+  for (int l = 0; l < a.nleaf; l++) {
+    const FdLeaf L = a.leaf[l];
+    unsigned* dst = L.dst + w * L.words;
+    const unsigned* src = L.src + e * L.words;
+    for (int i = threadIdx.x; i < L.words; i += MJH_FD_PERTURB_WG) dst[i] = src[i];
+  }
+  __syncthreads();  // the nudged entry is stored over its copy
+  if (threadIdx.x != 0) return;
+  const int col = c.col0 + sl / nside, side = sl - (sl / nside) * nside;
+  const int nv = c.nv, ns = 2 * nv + c.na;
+  REAL h = side ? -c.eps : c.eps;
+  if (col < nv) {
+    int adr, axis;
+    fd_dof(c.dof_jntid, c.jnt_type, c.jnt_qposadr, c.jnt_dofadr, col, adr, axis);
+    const REAL* q = a.qpos + e * c.nq + adr;
+    REAL* o = a.p_qpos + w * c.nq + adr;
+    if (axis < 0) {
+      o[0] = q[0] + h;
+    } else {
+      const REAL q4[4] = {q[0], q[1], q[2], q[3]}, t[3] = {(REAL)(axis == 0), (REAL)(axis == 1), (REAL)(axis == 2)};
+      REAL r[4];
+      quat_integrate(q4, t, h, r);
+#pragma unroll
+      for (int i = 0; i < 4; i++) o[i] = r[i];
+    }
+  } else if (col < 2 * nv) {
+    const int d = col - nv;
+    a.p_qvel[w * nv + d] = a.qvel[e * nv + d] + h;
+  } else if (col < ns) {
+    const int i = col - 2 * nv;
+    a.p_act[w * c.na + i] = a.act[e * c.na + i] + h;
+  } else {
+    const int i = col - ns, sides = fd_ctrl_sides(c, e, i);
+    bool take;
+    if (c.centered) take = side ? (sides & 2) != 0 : (sides & 1) != 0;
+    else { take = sides != 0; if (!(sides & 1)) h = -c.eps; }
+    if (take) a.p_ctrl[w * c.nu + i] = c.ctrl[e * c.nu + i] + h;
+  }
+}
+
+// element `row` of  y1 - y0  in tangent space
+template <typename REAL>
+__device__ __forceinline__ REAL fd_sub(const FdCommon<REAL>& c, const FdState<REAL>& s1, int64_t e1, const FdState<REAL>& s0, int64_t e0, int row) {
+  const int nv = c.nv, ns = 2 * nv + c.na;
+  if (row < nv) {
+    int adr, axis;
+    fd_dof(c.dof_jntid, c.jnt_type, c.jnt_qposadr, c.jnt_dofadr, row, adr, axis);
+    const REAL *q1 = s1.qpos + e1 * c.nq + adr, *q0 = s0.qpos + e0 * c.nq + adr;
+    if (axis < 0) return q1[0] - q0[0];
+    const REAL u[4] = {q1[0], q1[1], q1[2], q1[3]}, v[4] = {q0[0], q0[1], q0[2], q0[3]};
+    REAL r[3];
+    quat_sub(u, v, r);
+    return axis == 0 ? r[0] : (axis == 1 ? r[1] : r[2]);
+  }
+  if (row < 2 * nv) return s1.qvel[e1 * nv + (row - nv)] - s0.qvel[e0 * nv + (row - nv)];
+  if (row < ns) return s1.act[e1 * c.na + (row - 2 * nv)] - s0.act[e0 * c.na + (row - 2 * nv)];
+  return s1.sens[e1 * c.nsd + (row - ns)] - s0.sens[e0 * c.nsd + (row - ns)];
+}
+
+template <typename REAL>
+__global__ __launch_bounds__(MJH_FD_DIFF_WG) void mjh_fd_difference_kernel(FdDiffArgs<REAL> a) {
+  const FdCommon<REAL>& c = a.c;
+  const int64_t g = c.first + (int64_t)blockIdx.x * MJH_FD_DIFF_WG + threadIdx.x;
+  if (g >= c.total) return;
+  const int nv = c.nv, ns = 2 * nv + c.na, nrow = ns + (a.C ? c.nsd : 0), nside = c.centered ? 2 : 1;
+  const int64_t t = g / c.ncol;
+  const int cl = (int)(g - t * c.ncol);
+  const int64_t e = t / nrow;
+  const int row = (int)(t - e * nrow), col = c.col0 + cl;
+  const int64_t wp = (e * c.ncol + cl) * nside, wm = wp + nside - 1;  // the slots of the forward and of the backward nudge
+  const bool is_ctrl = col >= ns;
+  const int sides = is_ctrl ? fd_ctrl_sides(c, e, col - ns) : (c.centered ? 3 : 1);
+  const REAL h = c.eps;
+  REAL v = 0;
+  if (sides == 1) v = fd_sub(c, a.y, wp, a.y0, e, row) / h;
+  else if (sides == 2) v = fd_sub(c, a.y0, e, a.y, wm, row) / h;
+  else if (sides == 3 && !is_ctrl) v = fd_sub(c, a.y, wp, a.y, wm, row) / (2 * h);
+  else if (sides == 3) v = (fd_sub(c, a.y, wp, a.y0, e, row) / h + fd_sub(c, a.y0, e, a.y, wm, row) / h) * (REAL)0.5;
+  if (row < ns) {
+    if (!is_ctrl) a.A[(e * ns + row) * ns + col] = v;
+    else a.Bm[(e * ns + row) * c.nu + (col - ns)] = v;
+  } else {
+    if (!is_ctrl) a.C[(e * c.nsd + (row - ns)) * ns + col] = v;
+    else a.D[(e * c.nsd + (row - ns)) * c.nu + (col - ns)] = v;
+  }
+}

@@ -9,6 +9,7 @@
 #include "mjh_ray.h"
 #include "mjh_render.h"
 #include "mjh_support.h"
+#include "mjh_fd.h"
 #include "mjh_instances.h"
 
 #define MJH_CAT_(a, b) a##b
@@ -33,4 +34,8 @@ template __global__ void mjh_sup_point_kernel<MJH_INST_REAL, false>(SupArgs<MJH_
 template __global__ void mjh_sup_xfrc_kernel<MJH_INST_REAL>(SupArgs<MJH_INST_REAL>);
 template __global__ void mjh_sup_mulm_kernel<MJH_INST_REAL>(SupArgs<MJH_INST_REAL>);
 template __global__ void mjh_sup_solvem_kernel<MJH_INST_REAL>(SupArgs<MJH_INST_REAL>);
+#endif
+#if MJH_INST_GROUP == 23
+template __global__ void mjh_fd_perturb_kernel<MJH_INST_REAL>(FdPerturbArgs<MJH_INST_REAL>);
+template __global__ void mjh_fd_difference_kernel<MJH_INST_REAL>(FdDiffArgs<MJH_INST_REAL>);
 #endif

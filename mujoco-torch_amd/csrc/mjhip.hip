@@ -21,6 +21,7 @@
 #include "mjh_ray.h"
 #include "mjh_render.h"
 #include "mjh_support.h"
+#include "mjh_fd.h"
 #include "mjh_instances.h"
 
 // the kernels are compiled in their own translation units (mjh_inst.hip, one per build group): this file is the host side only
@@ -45,6 +46,10 @@ extern template __global__ void mjh_render_kernel<float>(RenderArgs<float>);
 SUP_(double)  // (build group 22)
 SUP_(float)
 #undef SUP_
+extern template __global__ void mjh_fd_perturb_kernel<double>(FdPerturbArgs<double>);  // (build group 23)
+extern template __global__ void mjh_fd_perturb_kernel<float>(FdPerturbArgs<float>);
+extern template __global__ void mjh_fd_difference_kernel<double>(FdDiffArgs<double>);
+extern template __global__ void mjh_fd_difference_kernel<float>(FdDiffArgs<float>);
 #undef X_
 #undef S_
 #undef C_
@@ -1426,6 +1431,103 @@ int run_support(const mjhModel* m, const DevModel<REAL>& M, const mjhSupportArgs
   return 0;
 }
 
+// ---- finite-difference transition Jacobians (mjh_fd.h): the launches on either side of the caller's mjh_step over the perturbed environments ----
+
+// 4-byte words per environment of every mjhData slot, in struct order: reals, int32, int64, then the trailing input-only leaves
+template <typename REAL>
+std::vector<int64_t> data_words(const mjhModel* m, const DevModel<REAL>& M) {
+  const int64_t rw = sizeof(REAL) / 4, ncon = M.ncon, nb = M.nbody;
+  std::vector<int64_t> w;
+  for (int64_t c : m->leaf_count) w.push_back(c * rw);
+  const int64_t tail[] = {ncon /* contact_dim */, M.neq /* eq_active */, 2 * ncon, 2 * ncon, 4 * ncon, 2 * ncon /* geom1, geom2, geom, efc_address (int64) */,
+                          6 * nb * rw, 6 * nb * rw, 3 * nb * rw, 3 * nb * rw /* cacc, cfrc_int, subtree_linvel, subtree_angmom */};
+  w.insert(w.end(), tail, tail + 10);
+  return w;
+}
+
+template <typename REAL>
+int fd_common(const DevModel<REAL>& M, const mjhData* in, int64_t B, int col0, int ncol, double eps, int centered, FdCommon<REAL>& c) {
+  const int ns = 2 * M.nv + M.na;
+  if (B < 0) return fail(-22, "fd: B must be >= 0");
+  if (!(eps > 0) || !((REAL)eps > 0)) return fail(-22, "fd: eps must be positive in the model's dtype");
+  if (col0 < 0 || ncol < 1 || col0 + ncol > ns + M.nu) return fail(-22, "fd: columns outside [0, 2 nv + na + nu)");
+  if ((int64_t)ncol * 2 * (ns + M.nsensordata + 1) >= ((int64_t)1 << 31)) return fail(-22, "fd: too many columns in one call");
+  if (col0 + ncol > ns && !in->ctrl) return fail(-22, "fd: in.ctrl is required for the ctrl columns");
+  c.dof_jntid = M.dof_jntid; c.jnt_type = M.jnt_type; c.jnt_qposadr = M.jnt_qposadr; c.jnt_dofadr = M.jnt_dofadr;
+  c.act_ctrllimited = M.act_ctrllimited; c.act_ctrlrange = M.act_ctrlrange;
+  c.ctrl = reinterpret_cast<const REAL*>(in->ctrl);
+  c.eps = (REAL)eps;
+  c.nq = M.nq; c.nv = M.nv; c.na = M.na; c.nu = M.nu; c.nsd = M.nsensordata;
+  c.centered = centered ? 1 : 0; c.col0 = col0; c.ncol = ncol;
+  return 0;
+}
+
+template <typename REAL>
+int run_fd_perturb(const mjhModel* m, const DevModel<REAL>& M, const mjhData* in, mjhData* scratch, int64_t B, int col0, int ncol, double eps, int centered, void* stream) {
+  static_assert(sizeof(FdPerturbArgs<REAL>) <= 4096, "kernel arguments exceed the 4 KiB kernarg segment");
+  FdPerturbArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+  if (const int rc = fd_common(M, in, B, col0, ncol, eps, centered, a.c)) return rc;
+  if (B == 0) return 0;
+  if (!in->qpos || !in->qvel || !scratch->qpos || !scratch->qvel || (M.na > 0 && !(in->act && scratch->act)) || (M.nu > 0 && !(in->ctrl && scratch->ctrl)))
+    return fail(-22, "fd_perturb: qpos, qvel, act and ctrl are required in both Data");
+  const std::vector<int64_t> words = data_words(m, M);
+  if (words.size() * sizeof(void*) != sizeof(mjhData)) return fail(-22, "fd_perturb: leaf table out of sync with mjhData");
+  void* const* dp = reinterpret_cast<void* const*>(scratch);
+  void* const* sp = reinterpret_cast<void* const*>(in);
+  for (size_t i = 0; i < words.size(); i++) {
+    if (!dp[i] || words[i] == 0) continue;
+    if (!sp[i]) return fail(-22, "fd_perturb: a leaf of the scratch Data is missing from the input Data");
+    if (a.nleaf == MJH_FD_MAX_LEAVES) return fail(-22, "fd_perturb: too many leaves in the scratch Data (input leaves only)");
+    FdLeaf& L = a.leaf[a.nleaf++];
+    L.dst = (unsigned*)dp[i]; L.src = (const unsigned*)sp[i]; L.words = (int)words[i];
+  }
+  a.qpos = reinterpret_cast<const REAL*>(in->qpos); a.qvel = reinterpret_cast<const REAL*>(in->qvel); a.act = reinterpret_cast<const REAL*>(in->act);
+  a.p_qpos = reinterpret_cast<REAL*>(scratch->qpos); a.p_qvel = reinterpret_cast<REAL*>(scratch->qvel);
+  a.p_act = reinterpret_cast<REAL*>(scratch->act); a.p_ctrl = reinterpret_cast<REAL*>(scratch->ctrl);
+  a.c.total = B * ncol * (centered ? 2 : 1);
+  hipStream_t s = (hipStream_t)stream;
+  timing_begin(s);
+  if (const int rc = launch_cut(a.c.total, 1, [&](int64_t first, int64_t, unsigned grid) {
+        a.c.first = first;
+        hipLaunchKernelGGL((mjh_fd_perturb_kernel<REAL>), dim3(grid), dim3(MJH_FD_PERTURB_WG), 0, s, a);
+      }))
+    return rc;
+  timing_mark(s, MJH_KERNEL_FD_PERTURB);
+  return 0;
+}
+
+template <typename REAL>
+int run_fd_difference(const DevModel<REAL>& M, const mjhData* in, const mjhData* nominal, const mjhData* stepped, int64_t B, int col0, int ncol, double eps,
+                      int centered, void* A, void* Bm, void* C, void* D, void* stream) {
+  FdDiffArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+  if (const int rc = fd_common(M, in, B, col0, ncol, eps, centered, a.c)) return rc;
+  const int ns = 2 * M.nv + M.na;
+  if (B == 0 || ns == 0) return 0;
+  const bool sens = C != nullptr && M.nsensordata > 0;
+  if ((C && !D && M.nu > 0) || (!C && D)) return fail(-22, "fd_difference: C and D go together");
+  if (!A || (M.nu > 0 && !Bm)) return fail(-22, "fd_difference: A and Bm are required");
+  auto state = [&](const mjhData* d, FdState<REAL>& y) {
+    y.qpos = reinterpret_cast<const REAL*>(d->qpos); y.qvel = reinterpret_cast<const REAL*>(d->qvel);
+    y.act = reinterpret_cast<const REAL*>(d->act); y.sens = reinterpret_cast<const REAL*>(d->sensordata);
+    return y.qpos && y.qvel && (M.na == 0 || y.act) && (!sens || y.sens);
+  };
+  if (!state(nominal, a.y0) || !state(stepped, a.y)) return fail(-22, "fd_difference: qpos, qvel, act (and sensordata for C, D) are required in both stepped Data");
+  a.A = reinterpret_cast<REAL*>(A); a.Bm = reinterpret_cast<REAL*>(Bm);
+  a.C = sens ? reinterpret_cast<REAL*>(C) : nullptr; a.D = sens ? reinterpret_cast<REAL*>(D) : nullptr;
+  a.c.total = B * (ns + (sens ? M.nsensordata : 0)) * ncol;
+  hipStream_t s = (hipStream_t)stream;
+  timing_begin(s);
+  if (const int rc = launch_cut(a.c.total, MJH_FD_DIFF_WG, [&](int64_t first, int64_t, unsigned grid) {
+        a.c.first = first;
+        hipLaunchKernelGGL((mjh_fd_difference_kernel<REAL>), dim3(grid), dim3(MJH_FD_DIFF_WG), 0, s, a);
+      }))
+    return rc;
+  timing_mark(s, MJH_KERNEL_FD_DIFFERENCE);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1486,6 +1588,19 @@ int mjh_render(const mjhModel* m, const void* geom_xpos, const void* geom_xmat, 
 int mjh_support(const mjhModel* m, const mjhSupportArgs* args, void* stream) {
   if (!m || !args) return fail(-22, "null argument");
   return m->dtype == MJH_F64 ? run_support<double>(m, m->m64, args, stream) : run_support<float>(m, m->m32, args, stream);
+}
+
+int mjh_fd_perturb(const mjhModel* m, const mjhData* in, mjhData* scratch, int64_t B, int col0, int ncol, double eps, int centered, void* stream) {
+  if (!m || !in || !scratch) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_fd_perturb<double>(m, m->m64, in, scratch, B, col0, ncol, eps, centered, stream)
+                             : run_fd_perturb<float>(m, m->m32, in, scratch, B, col0, ncol, eps, centered, stream);
+}
+
+int mjh_fd_difference(const mjhModel* m, const mjhData* in, const mjhData* nominal, const mjhData* stepped, int64_t B, int col0, int ncol, double eps,
+                      int centered, void* A, void* Bm, void* C, void* D, void* stream) {
+  if (!m || !in || !nominal || !stepped) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_fd_difference<double>(m->m64, in, nominal, stepped, B, col0, ncol, eps, centered, A, Bm, C, D, stream)
+                             : run_fd_difference<float>(m->m32, in, nominal, stepped, B, col0, ncol, eps, centered, A, Bm, C, D, stream);
 }
 
 int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsigned char* mask, const void* qpos_rows,
@@ -1592,6 +1707,17 @@ static int kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes, b
     const int64_t io[5][2] = {{6 * nv + 3 + 3, 6 * nv}, {6 * nv + 3 + 9, nv}, {6 * nv + 3 * nb + 3 * nb + 6 * nb, nv}, {nv * nv + nv, nv}, {nv * nv + nv, nv}};
     read_write_bytes[0] = io[kernel - MJH_KERNEL_JAC][0] * R;
     read_write_bytes[1] = io[kernel - MJH_KERNEL_JAC][1] * R;
+    return 0;
+  }
+  if (kernel == MJH_KERNEL_FD_PERTURB || kernel == MJH_KERNEL_FD_DIFFERENCE) {  // the finite-difference kernels (mjh_fd.h), per slot: see include/mjhip.h
+    const int64_t R = f64 ? 8 : 4, nq = f64 ? m->m64.nq : m->m32.nq, nv = f64 ? m->m64.nv : m->m32.nv, na = f64 ? m->m64.na : m->m32.na, nu = f64 ? m->m64.nu : m->m32.nu;
+    const int64_t nb = f64 ? m->m64.nbody : m->m32.nbody, nmo = f64 ? m->m64.nmocap : m->m32.nmocap, nsd = f64 ? m->m64.nsensordata : m->m32.nsensordata, neq = f64 ? m->m64.neq : m->m32.neq;
+    if (kernel == MJH_KERNEL_FD_PERTURB) {  // time qpos qvel act qacc_warmstart ctrl qfrc_applied xfrc_applied mocap_* subtree_com qfrc_gravcomp actuator_force qfrc_constraint sensordata, the four trailing leaves, eq_active
+      read_write_bytes[0] = read_write_bytes[1] = (1 + nq + 5 * nv + na + 2 * nu + 6 * nb + 7 * nmo + 3 * nb + nsd + 18 * nb) * R + 4 * neq;
+    } else {
+      read_write_bytes[0] = (nq + nv + na + nsd) * R;
+      read_write_bytes[1] = (2 * nv + na + nsd) * R;
+    }
     return 0;
   }
   if (kernel == MJH_KERNEL_INVERSE) {  // the inverse-dynamics tail (mjh_inverse): efc_J and qM once, efc_D / efc_aref, qacc, qfrc_bias / passive in; efc_force, qfrc_constraint, qfrc_inverse out.
