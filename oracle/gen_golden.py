@@ -149,7 +149,19 @@ CASES = {
     # model with three 64-bit mask words (129 dofs, dof 128 alone on word 2: CG without eulerdamp, the only solver setting that fits it)
     "centipede_84_newton_f32": ("centipede_84", {}, "float32", 2, 2, "centipede"),
     "centipede_129_f32": ("centipede_129", {}, "float32", 2, 2, "centipede"),
+    # convex hulls larger than one wavefront of the pair kernel (tools/make_convex_large.py: 100 vertices / 196 faces / 294 edges, 18 vertices per
+    # face, 88 vertices with subsampled caps) in every convex pair function; poses drawn per environment so that each of the eleven pairs is in
+    # contact in some environments and apart in others (tests/test_convex_large_host.py asserts that on the recording)
+    # (eight environments were the plan: 34 contacts x 42 dofs make the recording 69 KB per environment in float64, and no golden is to outgrow the largest one
+    # already here, centipede_83_f64 at 350 KB -- so environments were dropped, not pairs: five in float64, six in float32)
+    "convex_large_f64": ("convex_large", {}, "float64", 5, 2, "convex_large"),
+    "convex_large_f32": ("convex_large", {}, "float32", 6, 2, "convex_large"),
 }
+
+# seed of the `convex_large` recipe: the first of 0, 1, 2, ... that tools/find_convex_large_seed.py keeps -- every pair in contact at least twice and apart at
+# least once in both dtypes, recordings no larger than the largest golden before them, and no narrow-phase tie outcome in float64 (seeds 9, 18 and 22 pass the
+# first criterion and show one tie pair each)
+CONVEX_LARGE_SEED = 111
 
 INPUT_LEAVES = ["time", "qpos", "qvel", "act", "qacc_warmstart", "ctrl", "qfrc_applied", "xfrc_applied", "qacc", "subtree_com", "mocap_pos", "mocap_quat"]
 
@@ -186,6 +198,15 @@ def make_inputs(recipe, lite, env):
             if int(lite.jnt_type[j]) == 0 and env > 0:
                 q[a : a + 3] += 0.01 * rng.randn(3)
                 q[a + 3 : a + 7] += 0.03 * rng.randn(4)  # un-normalised on purpose
+        out["qpos"] = q
+        out["qvel"] = 0.2 * rng.randn(nv)
+    elif recipe == "convex_large":  # every free body: its XML position jittered, a random orientation (un-normalised quaternion on purpose), velocities
+        rng = np.random.RandomState(7000 + 100 * CONVEX_LARGE_SEED + env)
+        q = lite.qpos0.copy()
+        for j in range(lite.njnt):
+            a = int(lite.jnt_qposadr[j])
+            q[a : a + 3] += 0.012 * rng.randn(3)
+            q[a + 3 : a + 7] = rng.randn(4)
         out["qpos"] = q
         out["qvel"] = 0.2 * rng.randn(nv)
     elif recipe == "topk":  # free bodies, every environment jittered (no two candidate contacts at exactly the same distance)
@@ -271,6 +292,12 @@ def make_inputs(recipe, lite, env):
     return out
 
 
+def model_path(xml):
+    """A bundled model, or a test-only one kept next to its recordings (tests/golden/convex_large.xml)."""
+    p = os.path.join(REPO, "mujoco-torch_amd", "mujoco_torch_amd", "test_data", xml + ".xml")
+    return p if os.path.exists(p) else os.path.join(REPO, "tests", "golden", xml + ".xml")
+
+
 def leaf(d, name):
     obj = d
     for p in native.DATA_PATH[name]:
@@ -288,7 +315,7 @@ def main(only=None):
         if only and case not in only:
             continue
         dtype = getattr(torch, dtype_s)
-        lite = mjcf.from_xml_path(os.path.join(REPO, "mujoco-torch_amd", "mujoco_torch_amd", "test_data", xml + ".xml"))
+        lite = mjcf.from_xml_path(model_path(xml))
         for k, v in overrides.items():
             if k.startswith("model."):  # an edit of the compiled model itself (tests/_util.load_model applies the same)
                 setattr(lite, k[6:], np.array(v, dtype=np.asarray(getattr(lite, k[6:])).dtype) if isinstance(v, list) else v)

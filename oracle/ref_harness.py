@@ -74,5 +74,7 @@ def put_model(ref, lite, dtype=None, keep_sensors=True):
         for k in ("sensor_type", "sensor_dim", "sensor_adr", "sensor_objid", "sensor_objtype", "sensor_needstage", "sensor_datatype", "sensor_reftype", "sensor_refid"):
             setattr(lite, k, np.zeros(0, dtype=np.int32))
         lite.sensor_cutoff = np.zeros(0)
+    if not hasattr(lite, "name_meshadr"):  # read only by mesh.py's warning about a face of more than 20 vertices (the stub's name table is empty)
+        lite.name_meshadr = np.zeros(int(getattr(lite, "nmesh", 0)), dtype=np.int32)
     mj = ref.mujoco.MjModel(lite)
     return ref.device.device_put(mj, dtype=dtype)

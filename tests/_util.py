@@ -45,8 +45,14 @@ def strip_sensors(lite):
     return lite
 
 
+def model_path(xml):
+    """A bundled model, or a test-only one kept under tests/golden/ (convex_large: its hulls are binary test vectors)."""
+    p = mt.test_data_path(xml + ".xml")
+    return p if os.path.exists(p) else os.path.join(GOLD, xml + ".xml")
+
+
 def load_model(xml, overrides=None, dtype=torch.float64, keep_sensors=True):
-    lite = mt.mjcf.from_xml_path(mt.test_data_path(xml + ".xml"))
+    lite = mt.mjcf.from_xml_path(model_path(xml))
     for k, v in (overrides or {}).items():
         if k.startswith("model."):  # an edit of the compiled model itself (integer arrays keep their dtype): {"model.wrap_type": [...]}
             cur = getattr(lite, k[6:])
