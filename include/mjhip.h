@@ -12,6 +12,7 @@
  *   mjh_ray            <- ray.ray(m, d, pnt, vec, ...)               (_src/ray.py:375-452)
  *   mjh_render         <- render.render_batch(m, d, camera_id, ...)   (_src/render.py:719-907)
  *   mjh_fd_perturb / mjh_fd_difference <- the two ends of a finite-difference transition Jacobian (MuJoCo's mjd_transitionFD; the reference has no counterpart)
+ *   mjh_fd_vjp / mjh_fd_tangent        <- its vector-Jacobian product and the quaternion coordinate maps of a gradient through one step
  *   mjh_support        <- support.jac / apply_ft / xfrc_accumulate, smooth.mul_m / solve_m (_src/support.py:138-194, smooth.py:335-374)
  *
  * Conventions
@@ -88,6 +89,8 @@ extern "C" {
 #define MJH_KERNEL_SOLVE_M 27    /* mjh_support, MJH_SUPPORT_SOLVE_M: solves with the factor qLD                       */
 #define MJH_KERNEL_FD_PERTURB 28 /* mjh_fd_perturb: the perturbed input leaves of a chunk of finite-difference columns */
 #define MJH_KERNEL_FD_DIFFERENCE 29 /* mjh_fd_difference: the columns of A, B, C, D from the stepped chunk            */
+#define MJH_KERNEL_FD_VJP 30     /* mjh_fd_vjp: those columns contracted with a cotangent instead of stored            */
+#define MJH_KERNEL_FD_TANGENT 31 /* mjh_fd_tangent: cotangents between qpos coordinates and the tangent space          */
 
 /* pair-function ids of the static collision table (collision_driver.py:106-125) */
 #define MJH_FN_PLANE_SPHERE 0
@@ -557,6 +560,25 @@ int mjh_fd_perturb(const mjhModel* m, const mjhData* in, mjhData* scratch, int64
 int mjh_fd_difference(const mjhModel* m, const mjhData* in, const mjhData* nominal, const mjhData* stepped, int64_t B, int col0, int ncol, double eps,
                       int centered, void* A, void* Bm, void* C, void* D, void* hip_stream);
 
+/* The vector-Jacobian product of those Jacobians, in place of mjh_fd_difference after the same mjh_fd_perturb and mjh_step: for the columns
+ * [col0, col0 + ncol),  out[e, c] = sum_row g[e, row] * J[e, row, c]  with J[e, row, c] exactly the value mjh_fd_difference would store and
+ * g = g_state [B, ns] (cotangent of the next state in the order of x) followed, when g_sens is given, by g_sens [B, nsensordata]: gx [B, ns] receives
+ * the columns c < ns (A^T g_state + C^T g_sens), gu [B, nu] the ctrl columns (B^T g_state + D^T g_sens; may be NULL when nu == 0).  Only the columns
+ * of the call are written.  The additions of one sum happen in an order that depends on the number of rows alone: a result is the same bits from run
+ * to run and for every way of cutting the columns into calls. */
+int mjh_fd_vjp(const mjhModel* m, const mjhData* in, const mjhData* nominal, const mjhData* stepped, int64_t B, int col0, int ncol, double eps, int centered,
+               const void* g_state, const void* g_sens, void* gx, void* gu, void* hip_stream);
+
+/* Cotangents between qpos coordinates (nq) and the tangent space (nv) at `qpos` [B, nq], under q(d) = q (x) exp(d / 2) for the quaternions of ball / free
+ * joints (the convention of mjh_fd_perturb / mjh_fd_difference) and the identity elsewhere.
+ * MJH_FD_TANGENT_PULL: g_in [B, nq] -> g_out [B, nv]; a rotational dof k gives <g_in[quaternion], q (x) (0, e_k)> / 2.
+ * MJH_FD_TANGENT_PUSH: g_in [B, nv] -> g_out [B, nq]; a quaternion receives 2 sum_k g_in[k] q (x) (0, e_k) / |q|^2: the cotangent whose pull is g_in and
+ * whose component along q is zero (how a step depends on a quaternion's norm is not differentiated); zeros for an all-zero quaternion, which no
+ * perturbation of mjh_fd_perturb moves.  Every entry of g_out is written. */
+#define MJH_FD_TANGENT_PULL 0
+#define MJH_FD_TANGENT_PUSH 1
+int mjh_fd_tangent(const mjhModel* m, const void* qpos, const void* g_in, void* g_out, int64_t B, int mode, void* hip_stream);
+
 /* per-environment ELEMENT count of every mjhData leaf in ABI order (reals, then int32, then int64 leaves): a leaf handed to
  * mjh_forward / mjh_step / mjh_reset_where must hold exactly B * count elements.  The binding validates tensor sizes against
  * this before it passes raw pointers (the kernels index `ptr + env * count` unchecked).  Writes min(n, max) entries, returns n. */
@@ -577,7 +599,7 @@ int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsi
 int mjh_model_lds_bytes(const mjhModel* m, int arena);
 
 /* measurement aid used by bench.py for the per-kernel roofline: while enabled, every kernel launch of mjh_step / mjh_forward is
- * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb and mjh_fd_difference too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
+ * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp and mjh_fd_tangent too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
  * the elapsed milliseconds and the kernel id (MJH_KERNEL_*).  Returns the number of launches (<= max) or a negative code. */
 int mjh_debug_phase_timing(int enable);
 int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
@@ -594,7 +616,9 @@ void mjh_debug_set_stamps(void* dev_ptr);
  * model without cameras.  MJH_KERNEL_JAC .. MJH_KERNEL_SOLVE_M (an mjh_support call): per environment for one query point (JAC, APPLY_FT: the dof
  * rows, the root's subtree_com, the point, force and torque; jacp + jacr or the product), the whole sum (XFRC) or one vector (MUL_M, SOLVE_M: the matrix
  * loaded whole, the vector, the result).  MJH_KERNEL_FD_PERTURB / MJH_KERNEL_FD_DIFFERENCE: per slot, the input leaves a step of this model can read,
- * read and written (an upper bound: the caller's Data may lack some), and one slot's qpos, qvel, act and sensordata read, with [1] = one column of A and C.  Returns 0, or -2 when this model's step does not launch that kernel. */
+ * read and written (an upper bound: the caller's Data may lack some), and one slot's qpos, qvel, act and sensordata read, with [1] = one column of A and C.  MJH_KERNEL_FD_VJP: per (environment, column), one slot's and the nominal
+ * qpos, qvel, act and sensordata (an upper bound: a one-sided column reads the nominal, a centered state column its two slots) and the cotangent, with
+ * [1] = one entry of gx / gu; MJH_KERNEL_FD_TANGENT: per environment, qpos and a cotangent of at most nq entries read, one written.  Returns 0, or -2 when this model's step does not launch that kernel. */
 int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes);
 
 /* last error message of the calling thread ("" if none) */

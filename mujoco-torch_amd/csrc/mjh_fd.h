@@ -1,5 +1,6 @@
-// mjh_fd.h -- the two kernels around the steps of a finite-difference transition Jacobian (mjh_fd_perturb, mjh_fd_difference; MuJoCo's
-// mjd_transitionFD).  The steps themselves are plain mjh_step calls over the perturbed environments.
+// mjh_fd.h -- the kernels around the steps of a finite-difference transition Jacobian (mjh_fd_perturb, mjh_fd_difference; MuJoCo's
+// mjd_transitionFD) and of its vector-Jacobian product (mjh_fd_vjp, mjh_fd_tangent).  The steps themselves are plain mjh_step calls over the
+// perturbed environments.
 //
 // Columns: c in [0, nv) nudges qpos along dof c (tangent space), [nv, 2 nv) qvel, [2 nv, ns) act, ns = 2 nv + na, and [ns, ns + nu) ctrl.  A call
 // serves the columns [col0, col0 + ncol) of every environment.  Column c of environment e owns nside (1, centered: 2) perturbed environments,
@@ -17,12 +18,19 @@
 //   C / D for as many columns as the chunk holds.  Rows [0, nv): qpos differenced in tangent space -- subtraction, or quat_sub(q1, q0), the rotation
 //   vector of q0^-1 q1 -- then qvel, act and, with C / D, sensordata.  Forward (y+ - y0) / eps, backward (y0 - y-) / eps, centered state columns
 //   (y+ - y-) / (2 eps); a ctrl column with both sides taken is the mean of its forward and backward difference; with none, zero.
-// Both move far fewer bytes than the steps between them (a slot's inputs and four of its output leaves against the ~50 KB a humanoid step writes).
+// mjh_fd_vjp_kernel: the same entries contracted with a cotangent instead of stored: one wavefront per (environment, column of the chunk), lane l
+//   sums g[row] * v(row, column) over row = l, l + 64, ... in ascending order, one xor butterfly adds the 64 partial sums, lane 0 stores.  The order
+//   of the additions depends on the number of rows alone: the result is the same bits from run to run and whatever the chunking.  fd_entry is the
+//   expression both kernels share.
+// mjh_fd_tangent_kernel: the two coordinate maps between a cotangent of qpos (nq) and one of the tangent space (nv); see there.
+// The first two move far fewer bytes than the steps between them (a slot's inputs and four of its output leaves against the ~50 KB a humanoid step writes).
 #pragma once
 #include "mjh_device.h"
 
 #define MJH_FD_PERTURB_WG 64
 #define MJH_FD_DIFF_WG 256
+#define MJH_FD_VJP_WG 256      // four wavefronts, one (environment, column) each
+#define MJH_FD_TANGENT_WG 256
 #define MJH_FD_MAX_LEAVES 24
 
 struct FdLeaf {
@@ -65,6 +73,25 @@ struct FdDiffArgs {
   FdState<REAL> y0;  // the nominal step's result [B, ...]
   FdState<REAL> y;   // the perturbed steps' results [slots, ...]
   REAL *A, *Bm, *C, *D;
+};
+
+template <typename REAL>
+struct FdVjpArgs {
+  FdCommon<REAL> c;
+  FdState<REAL> y0, y;        // as in FdDiffArgs
+  const REAL *g_state;        // [B, ns]  cotangent of the next state, tangent-space order
+  const REAL *g_sens;         // [B, nsd] cotangent of sensordata, or null
+  REAL *gx, *gu;              // [B, ns], [B, nu]
+};
+
+template <typename REAL>
+struct FdTangentArgs {
+  const int *dof_jntid, *jnt_type, *jnt_qposadr, *jnt_dofadr;
+  const REAL *qpos;           // [B, nq]
+  const REAL *g_in;           // pull: [B, nq], push: [B, nv]
+  REAL *g_out;                // pull: [B, nv], push: [B, nq]
+  int nq, nv, mode, pad_;
+  int64_t first, total;       // units (environment, dof) of this launch / of the call
 };
 
 // bit 0: the forward nudge is taken, bit 1: the backward one
@@ -154,30 +181,107 @@ __device__ __forceinline__ REAL fd_sub(const FdCommon<REAL>& c, const FdState<RE
   return s1.sens[e1 * c.nsd + (row - ns)] - s0.sens[e0 * c.nsd + (row - ns)];
 }
 
+// entry (row, col0 + cl) of environment e's A / B / C / D: `sides` is fd_ctrl_sides of a ctrl column, else 3 when centered and 1 when not
+template <typename REAL>
+__device__ __forceinline__ REAL fd_entry(const FdCommon<REAL>& c, const FdState<REAL>& y0, const FdState<REAL>& y, int64_t e, int cl, int row, bool is_ctrl, int sides) {
+  const int nside = c.centered ? 2 : 1;
+  const int64_t wp = (e * c.ncol + cl) * nside, wm = wp + nside - 1;  // the slots of the forward and of the backward nudge
+  const REAL h = c.eps;
+  REAL v = 0;
+  if (sides == 1) v = fd_sub(c, y, wp, y0, e, row) / h;
+  else if (sides == 2) v = fd_sub(c, y0, e, y, wm, row) / h;
+  else if (sides == 3 && !is_ctrl) v = fd_sub(c, y, wp, y, wm, row) / (2 * h);
+  else if (sides == 3) v = (fd_sub(c, y, wp, y0, e, row) / h + fd_sub(c, y0, e, y, wm, row) / h) * (REAL)0.5;
+  return v;
+}
+
 template <typename REAL>
 __global__ __launch_bounds__(MJH_FD_DIFF_WG) void mjh_fd_difference_kernel(FdDiffArgs<REAL> a) {
   const FdCommon<REAL>& c = a.c;
   const int64_t g = c.first + (int64_t)blockIdx.x * MJH_FD_DIFF_WG + threadIdx.x;
   if (g >= c.total) return;
-  const int nv = c.nv, ns = 2 * nv + c.na, nrow = ns + (a.C ? c.nsd : 0), nside = c.centered ? 2 : 1;
+  const int nv = c.nv, ns = 2 * nv + c.na, nrow = ns + (a.C ? c.nsd : 0);
   const int64_t t = g / c.ncol;
   const int cl = (int)(g - t * c.ncol);
   const int64_t e = t / nrow;
   const int row = (int)(t - e * nrow), col = c.col0 + cl;
-  const int64_t wp = (e * c.ncol + cl) * nside, wm = wp + nside - 1;  // the slots of the forward and of the backward nudge
   const bool is_ctrl = col >= ns;
   const int sides = is_ctrl ? fd_ctrl_sides(c, e, col - ns) : (c.centered ? 3 : 1);
-  const REAL h = c.eps;
-  REAL v = 0;
-  if (sides == 1) v = fd_sub(c, a.y, wp, a.y0, e, row) / h;
-  else if (sides == 2) v = fd_sub(c, a.y0, e, a.y, wm, row) / h;
-  else if (sides == 3 && !is_ctrl) v = fd_sub(c, a.y, wp, a.y, wm, row) / (2 * h);
-  else if (sides == 3) v = (fd_sub(c, a.y, wp, a.y0, e, row) / h + fd_sub(c, a.y0, e, a.y, wm, row) / h) * (REAL)0.5;
+  const REAL v = fd_entry(c, a.y0, a.y, e, cl, row, is_ctrl, sides);
   if (row < ns) {
     if (!is_ctrl) a.A[(e * ns + row) * ns + col] = v;
     else a.Bm[(e * ns + row) * c.nu + (col - ns)] = v;
   } else {
     if (!is_ctrl) a.C[(e * c.nsd + (row - ns)) * ns + col] = v;
     else a.D[(e * c.nsd + (row - ns)) * c.nu + (col - ns)] = v;
+  }
+}
+
+template <typename REAL>
+__global__ __launch_bounds__(MJH_FD_VJP_WG) void mjh_fd_vjp_kernel(FdVjpArgs<REAL> a) {
+  const FdCommon<REAL>& c = a.c;
+  const int lane = threadIdx.x & (MJH_WAVE - 1);
+  const int64_t u = c.first + (int64_t)blockIdx.x * (MJH_FD_VJP_WG / MJH_WAVE) + threadIdx.x / MJH_WAVE;  // the same for all lanes of a wavefront
+  if (u >= c.total) return;
+  const int nv = c.nv, ns = 2 * nv + c.na, nrow = ns + (a.g_sens ? c.nsd : 0);
+  const int64_t e = u / c.ncol;
+  const int cl = (int)(u - e * c.ncol), col = c.col0 + cl;
+  const bool is_ctrl = col >= ns;
+  const int sides = is_ctrl ? fd_ctrl_sides(c, e, col - ns) : (c.centered ? 3 : 1);
+  REAL acc = 0;
+  for (int row = lane; row < nrow; row += MJH_WAVE) {
+    const REAL g = row < ns ? a.g_state[e * ns + row] : a.g_sens[e * c.nsd + (row - ns)];
+    acc = acc + g * fd_entry(c, a.y0, a.y, e, cl, row, is_ctrl, sides);
+  }
+#pragma unroll
+  for (int m = MJH_WAVE / 2; m >= 1; m >>= 1) acc = acc + __shfl_xor(acc, m, MJH_WAVE);  // (every lane ends with the same sum: a + b == b + a)
+  if (lane != 0) return;
+  if (!is_ctrl) a.gx[e * ns + col] = acc;
+  else a.gu[e * c.nu + (col - ns)] = acc;
+}
+
+// b = q (x) (0, e_k): the direction qpos moves in when the quaternion q turns about its local axis k (q (x) exp(d / 2) = q + b d / 2 + ...)
+template <typename REAL>
+__device__ __forceinline__ void fd_quat_dir(const REAL* q, int k, REAL* b) {
+  if (k == 0) { b[0] = -q[1]; b[1] = q[0]; b[2] = q[3]; b[3] = -q[2]; }
+  else if (k == 1) { b[0] = -q[2]; b[1] = -q[3]; b[2] = q[0]; b[3] = q[1]; }
+  else { b[0] = -q[3]; b[1] = q[2]; b[2] = -q[1]; b[3] = q[0]; }
+}
+
+// One lane per (environment, dof).  mode 0, pull: the cotangent g_in of qpos [B, nq] to the tangent space at qpos, g_out [B, nv]: the entry itself
+// for slide / hinge / free-translation dofs, <g_in[quaternion], b_k> / 2 for the rotational dof k of a ball / free joint (the adjoint of
+// d -> q (x) exp(d / 2)).  mode 1, push: a tangent cotangent g_in [B, nv] to qpos coordinates, g_out [B, nq]: the entry itself, or for a quaternion
+// 2 sum_k g_in[k] b_k / |q|^2 (zero for an all-zero quaternion) -- the cotangent with no component along q (a step's dependence on a quaternion's norm is not differentiated) whose
+// pull is g_in.  The lane of a quaternion's first rotational dof writes all four entries; every entry of qpos belongs to exactly one joint.
+template <typename REAL>
+__global__ __launch_bounds__(MJH_FD_TANGENT_WG) void mjh_fd_tangent_kernel(FdTangentArgs<REAL> a) {
+  const int64_t g = a.first + (int64_t)blockIdx.x * MJH_FD_TANGENT_WG + threadIdx.x;
+  if (g >= a.total) return;
+  const int64_t e = g / a.nv;
+  const int d = (int)(g - e * a.nv);
+  int adr, axis;
+  fd_dof(a.dof_jntid, a.jnt_type, a.jnt_qposadr, a.jnt_dofadr, d, adr, axis);
+  const REAL* q = a.qpos + e * a.nq + adr;
+  if (a.mode == 0) {
+    const REAL* gq = a.g_in + e * a.nq + adr;
+    if (axis < 0) { a.g_out[e * a.nv + d] = gq[0]; return; }
+    const REAL q4[4] = {q[0], q[1], q[2], q[3]};
+    REAL b[4];
+    fd_quat_dir(q4, axis, b);
+    a.g_out[e * a.nv + d] = (REAL)0.5 * (((gq[0] * b[0] + gq[1] * b[1]) + gq[2] * b[2]) + gq[3] * b[3]);
+  } else {
+    const REAL* gt = a.g_in + e * a.nv + d;
+    REAL* o = a.g_out + e * a.nq + adr;
+    if (axis < 0) { o[0] = gt[0]; return; }
+    if (axis != 0) return;
+    const REAL q4[4] = {q[0], q[1], q[2], q[3]};
+    REAL n2 = ((q4[0] * q4[0] + q4[1] * q4[1]) + q4[2] * q4[2]) + q4[3] * q4[3];
+    n2 = n2 + (REAL)(n2 == 0);  // an all-zero quaternion stays zero under normalize_n and quat_integrate: no rotation changes the step, the cotangent is zero
+    REAL b0[4], b1[4], b2[4];
+    fd_quat_dir(q4, 0, b0);
+    fd_quat_dir(q4, 1, b1);
+    fd_quat_dir(q4, 2, b2);
+#pragma unroll
+    for (int i = 0; i < 4; i++) o[i] = (REAL)2 * ((gt[0] * b0[i] + gt[1] * b1[i]) + gt[2] * b2[i]) / n2;
   }
 }

@@ -38,4 +38,6 @@ template __global__ void mjh_sup_solvem_kernel<MJH_INST_REAL>(SupArgs<MJH_INST_R
 #if MJH_INST_GROUP == 23
 template __global__ void mjh_fd_perturb_kernel<MJH_INST_REAL>(FdPerturbArgs<MJH_INST_REAL>);
 template __global__ void mjh_fd_difference_kernel<MJH_INST_REAL>(FdDiffArgs<MJH_INST_REAL>);
+template __global__ void mjh_fd_vjp_kernel<MJH_INST_REAL>(FdVjpArgs<MJH_INST_REAL>);
+template __global__ void mjh_fd_tangent_kernel<MJH_INST_REAL>(FdTangentArgs<MJH_INST_REAL>);
 #endif

@@ -50,6 +50,10 @@ extern template __global__ void mjh_fd_perturb_kernel<double>(FdPerturbArgs<doub
 extern template __global__ void mjh_fd_perturb_kernel<float>(FdPerturbArgs<float>);
 extern template __global__ void mjh_fd_difference_kernel<double>(FdDiffArgs<double>);
 extern template __global__ void mjh_fd_difference_kernel<float>(FdDiffArgs<float>);
+extern template __global__ void mjh_fd_vjp_kernel<double>(FdVjpArgs<double>);
+extern template __global__ void mjh_fd_vjp_kernel<float>(FdVjpArgs<float>);
+extern template __global__ void mjh_fd_tangent_kernel<double>(FdTangentArgs<double>);
+extern template __global__ void mjh_fd_tangent_kernel<float>(FdTangentArgs<float>);
 #undef X_
 #undef S_
 #undef C_
@@ -1528,6 +1532,59 @@ int run_fd_difference(const DevModel<REAL>& M, const mjhData* in, const mjhData*
   return 0;
 }
 
+template <typename REAL>
+int run_fd_vjp(const DevModel<REAL>& M, const mjhData* in, const mjhData* nominal, const mjhData* stepped, int64_t B, int col0, int ncol, double eps,
+               int centered, const void* g_state, const void* g_sens, void* gx, void* gu, void* stream) {
+  FdVjpArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+  if (const int rc = fd_common(M, in, B, col0, ncol, eps, centered, a.c)) return rc;
+  const int ns = 2 * M.nv + M.na;
+  if (B == 0 || ns == 0) return 0;
+  const bool sens = g_sens != nullptr && M.nsensordata > 0;
+  if (!g_state || !gx || (M.nu > 0 && !gu)) return fail(-22, "fd_vjp: g_state, gx and gu are required");
+  auto state = [&](const mjhData* d, FdState<REAL>& y) {
+    y.qpos = reinterpret_cast<const REAL*>(d->qpos); y.qvel = reinterpret_cast<const REAL*>(d->qvel);
+    y.act = reinterpret_cast<const REAL*>(d->act); y.sens = reinterpret_cast<const REAL*>(d->sensordata);
+    return y.qpos && y.qvel && (M.na == 0 || y.act) && (!sens || y.sens);
+  };
+  if (!state(nominal, a.y0) || !state(stepped, a.y)) return fail(-22, "fd_vjp: qpos, qvel, act (and sensordata with g_sens) are required in both stepped Data");
+  a.g_state = reinterpret_cast<const REAL*>(g_state); a.g_sens = sens ? reinterpret_cast<const REAL*>(g_sens) : nullptr;
+  a.gx = reinterpret_cast<REAL*>(gx); a.gu = reinterpret_cast<REAL*>(gu);
+  a.c.total = B * ncol;
+  hipStream_t s = (hipStream_t)stream;
+  timing_begin(s);
+  if (const int rc = launch_cut(a.c.total, MJH_FD_VJP_WG / MJH_WAVE, [&](int64_t first, int64_t, unsigned grid) {
+        a.c.first = first;
+        hipLaunchKernelGGL((mjh_fd_vjp_kernel<REAL>), dim3(grid), dim3(MJH_FD_VJP_WG), 0, s, a);
+      }))
+    return rc;
+  timing_mark(s, MJH_KERNEL_FD_VJP);
+  return 0;
+}
+
+template <typename REAL>
+int run_fd_tangent(const DevModel<REAL>& M, const void* qpos, const void* g_in, void* g_out, int64_t B, int mode, void* stream) {
+  if (B < 0) return fail(-22, "fd_tangent: B must be >= 0");
+  if (mode != MJH_FD_TANGENT_PULL && mode != MJH_FD_TANGENT_PUSH) return fail(-22, "fd_tangent: mode must be MJH_FD_TANGENT_PULL or MJH_FD_TANGENT_PUSH");
+  if (B == 0 || M.nv == 0) return 0;
+  if (!qpos || !g_in || !g_out) return fail(-22, "fd_tangent: qpos, g_in and g_out are required");
+  FdTangentArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+  a.dof_jntid = M.dof_jntid; a.jnt_type = M.jnt_type; a.jnt_qposadr = M.jnt_qposadr; a.jnt_dofadr = M.jnt_dofadr;
+  a.qpos = reinterpret_cast<const REAL*>(qpos); a.g_in = reinterpret_cast<const REAL*>(g_in); a.g_out = reinterpret_cast<REAL*>(g_out);
+  a.nq = M.nq; a.nv = M.nv; a.mode = mode;
+  a.total = B * M.nv;
+  hipStream_t s = (hipStream_t)stream;
+  timing_begin(s);
+  if (const int rc = launch_cut(a.total, MJH_FD_TANGENT_WG, [&](int64_t first, int64_t, unsigned grid) {
+        a.first = first;
+        hipLaunchKernelGGL((mjh_fd_tangent_kernel<REAL>), dim3(grid), dim3(MJH_FD_TANGENT_WG), 0, s, a);
+      }))
+    return rc;
+  timing_mark(s, MJH_KERNEL_FD_TANGENT);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1601,6 +1658,19 @@ int mjh_fd_difference(const mjhModel* m, const mjhData* in, const mjhData* nomin
   if (!m || !in || !nominal || !stepped) return fail(-22, "null argument");
   return m->dtype == MJH_F64 ? run_fd_difference<double>(m->m64, in, nominal, stepped, B, col0, ncol, eps, centered, A, Bm, C, D, stream)
                              : run_fd_difference<float>(m->m32, in, nominal, stepped, B, col0, ncol, eps, centered, A, Bm, C, D, stream);
+}
+
+int mjh_fd_vjp(const mjhModel* m, const mjhData* in, const mjhData* nominal, const mjhData* stepped, int64_t B, int col0, int ncol, double eps, int centered,
+               const void* g_state, const void* g_sens, void* gx, void* gu, void* stream) {
+  if (!m || !in || !nominal || !stepped) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_fd_vjp<double>(m->m64, in, nominal, stepped, B, col0, ncol, eps, centered, g_state, g_sens, gx, gu, stream)
+                             : run_fd_vjp<float>(m->m32, in, nominal, stepped, B, col0, ncol, eps, centered, g_state, g_sens, gx, gu, stream);
+}
+
+int mjh_fd_tangent(const mjhModel* m, const void* qpos, const void* g_in, void* g_out, int64_t B, int mode, void* stream) {
+  if (!m) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_fd_tangent<double>(m->m64, qpos, g_in, g_out, B, mode, stream)
+                             : run_fd_tangent<float>(m->m32, qpos, g_in, g_out, B, mode, stream);
 }
 
 int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsigned char* mask, const void* qpos_rows,
@@ -1717,6 +1787,19 @@ static int kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes, b
     } else {
       read_write_bytes[0] = (nq + nv + na + nsd) * R;
       read_write_bytes[1] = (2 * nv + na + nsd) * R;
+    }
+    return 0;
+  }
+  if (kernel == MJH_KERNEL_FD_VJP || kernel == MJH_KERNEL_FD_TANGENT) {  // per (environment, column) and per environment: see include/mjhip.h
+    const int64_t R = f64 ? 8 : 4, nq = f64 ? m->m64.nq : m->m32.nq, nv = f64 ? m->m64.nv : m->m32.nv, na = f64 ? m->m64.na : m->m32.na;
+    const int64_t nsd = f64 ? m->m64.nsensordata : m->m32.nsensordata;
+    if (nv == 0) return -2;
+    if (kernel == MJH_KERNEL_FD_VJP) {
+      read_write_bytes[0] = ((nq + nv + na + nsd) + (2 * nv + na + nsd)) * R;
+      read_write_bytes[1] = R;
+    } else {
+      read_write_bytes[0] = 2 * nq * R;
+      read_write_bytes[1] = nq * R;
     }
     return 0;
   }
