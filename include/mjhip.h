@@ -14,6 +14,7 @@
  *   mjh_fd_perturb / mjh_fd_difference <- the two ends of a finite-difference transition Jacobian (MuJoCo's mjd_transitionFD; the reference has no counterpart)
  *   mjh_fd_vjp / mjh_fd_tangent        <- its vector-Jacobian product and the quaternion coordinate maps of a gradient through one step
  *   mjh_support        <- support.jac / apply_ft / xfrc_accumulate, smooth.mul_m / solve_m (_src/support.py:138-194, smooth.py:335-374)
+ *   mjh_postconstraint <- MuJoCo's mj_rnePostConstraint / mj_subtreeVel (MJX smooth.rne_postconstraint / subtree_vel; the reference has no counterpart)
  *
  * Conventions
  *  - every Data leaf is batch-major contiguous: shape [B, ...] exactly as
@@ -39,7 +40,7 @@
 extern "C" {
 #endif
 
-#define MJH_ABI_VERSION 15
+#define MJH_ABI_VERSION 16
 
 /* ---- dtype / flags ------------------------------------------------------------------- */
 #define MJH_F64 0
@@ -91,6 +92,7 @@ extern "C" {
 #define MJH_KERNEL_FD_DIFFERENCE 29 /* mjh_fd_difference: the columns of A, B, C, D from the stepped chunk            */
 #define MJH_KERNEL_FD_VJP 30     /* mjh_fd_vjp: those columns contracted with a cotangent instead of stored            */
 #define MJH_KERNEL_FD_TANGENT 31 /* mjh_fd_tangent: cotangents between qpos coordinates and the tangent space          */
+#define MJH_KERNEL_POSTCON 32    /* mjh_postconstraint: cacc, cfrc_int, cfrc_ext, subtree_linvel, subtree_angmom       */
 
 /* pair-function ids of the static collision table (collision_driver.py:106-125) */
 #define MJH_FN_PLANE_SPHERE 0
@@ -370,7 +372,8 @@ typedef struct mjhModelDesc {
 
 /* Input-only real leaves that NO stage of the reference writes -- they hold what make_data put there (zeros) or what the caller did -- but its sensor functions
  * read: cacc (accelerometer, sensor.py:383-392), cfrc_int (force / torque, :399-416), subtree_linvel / subtree_angmom (:261-266).  They trail the struct, outside
- * the leaf lists above (no kernel writes them, the goldens' key sets do not change); NULL = zeros.  [B, nbody*6], [B, nbody*6], [B, nbody*3], [B, nbody*3]. */
+ * the leaf lists above (no kernel of a pass writes them, the goldens' key sets do not change); NULL = zeros.  [B, nbody*6], [B, nbody*6], [B, nbody*3], [B, nbody*3].
+ * mjh_postconstraint computes them from a finished pass, into buffers of the caller's. */
 #define MJH_DATA_EXTRA_IN(X) X(cacc) X(cfrc_int) X(subtree_linvel) X(subtree_angmom)
 
 #define MJH_DATA_I32(X) X(contact_dim) /* ncon */ X(eq_active) /* neq: input, enable / disable each equality constraint (types.py:1103) */
@@ -539,6 +542,37 @@ typedef struct mjhSupportArgs {
  * code; B == 0 is a no-op. */
 int mjh_support(const mjhModel* m, const mjhSupportArgs* args, void* hip_stream);
 
+/* mjh_postconstraint flags: what one launch computes */
+#define MJH_POSTCON_RNE 1     /* cacc, cfrc_int, cfrc_ext (MuJoCo's mj_rnePostConstraint)                                        */
+#define MJH_POSTCON_SUBTREE 2 /* subtree_linvel, subtree_angmom (mj_subtreeVel)                                                  */
+#define MJH_POSTCON_SENSORS 4 /* ... and the sensordata slots that read those leaves; needs both bits above                     */
+
+/* one mjh_postconstraint call.  Every pointer is device memory, batch-major over B environments; reals are of the model's dtype.  The inputs are the leaves of a
+ * finished forward pass: qvel (the velocity the pass ran on) / qacc [B, nv], cdof / cdof_dot [B, nv, 6], cvel / xfrc_applied [B, nbody, 6], cinert [B, nbody, 10],
+ * xipos / subtree_com [B, nbody, 3], ximat [B, nbody, 9], efc_force [B, nefc], contact_pos [B, ncon, 3], contact_frame [B, ncon, 9], contact_friction [B, ncon, 5],
+ * contact_dim [B, ncon] (int32), contact_geom [B, ncon, 2] / contact_efc_address [B, ncon] (int64), site_xpos [B, nsite, 3], site_xmat [B, nsite, 9], sensordata_in
+ * [B, nsensordata]; body_subtreemass [nbody] is the model's.  RNE reads qvel .. cinert, xipos, subtree_com, xfrc_applied, efc_force (nefc > 0) and the contact leaves
+ * (ncon > 0) and writes cacc, cfrc_int, cfrc_ext [B, nbody, 6]; SUBTREE reads cvel, xipos, ximat, subtree_com, body_subtreemass and writes subtree_linvel,
+ * subtree_angmom [B, nbody, 3]; SENSORS also reads site_xpos / site_xmat and sensordata_in and writes sensordata [B, nsensordata]: the slots of accelerometer, force,
+ * torque, subtreelinvel and subtreeangmom sensors from the fresh leaves, every other slot copied.  Spatial vectors are [rotational, translational] in the world frame
+ * about subtree_com[body_rootid[b]]; cfrc_ext holds xfrc_applied and the contact forces only (equality, limit and frictionloss forces stay joint-space).  A contact slot
+ * whose geom ids are not in [0, ngeom), or whose rows do not lie inside efc_force, is skipped.  No output may alias an input. */
+typedef struct mjhPostconArgs {
+  int32_t flags, reserved;
+  int64_t B;
+  const void *qvel, *qacc, *cdof, *cdof_dot, *cvel, *cinert, *xipos, *ximat, *subtree_com, *xfrc_applied, *efc_force;
+  const void *contact_pos, *contact_frame, *contact_friction;
+  const int32_t* contact_dim;
+  const int64_t *contact_geom, *contact_efc_address;
+  const void *site_xpos, *site_xmat, *sensordata_in;
+  const void* body_subtreemass;
+  void *cacc, *cfrc_int, *cfrc_ext, *subtree_linvel, *subtree_angmom, *sensordata;
+} mjhPostconArgs;
+
+/* body accelerations and forces of a finished forward pass (see mjhPostconArgs) as ONE launch.  Runs on hip_stream without host synchronisation.  Returns 0 or a
+ * negative code (a model whose bodies and contacts do not fit the LDS of a workgroup is refused); B == 0 is a no-op. */
+int mjh_postconstraint(const mjhModel* m, const mjhPostconArgs* args, void* hip_stream);
+
 /* Finite-difference transition Jacobians (MuJoCo's mjd_transitionFD), as two launches around an mjh_step of the caller's own.  State x = (qpos in
  * tangent space: nv, qvel: nv, act: na), ns = 2 nv + na; column c in [0, ns) nudges entry c of x, column ns + i nudges ctrl[i].  A call serves the
  * columns [col0, col0 + ncol) of all B environments.  Each column of an environment owns nside = (centered ? 2 : 1) environments ("slots") of a
@@ -599,7 +633,7 @@ int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsi
 int mjh_model_lds_bytes(const mjhModel* m, int arena);
 
 /* measurement aid used by bench.py for the per-kernel roofline: while enabled, every kernel launch of mjh_step / mjh_forward is
- * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp and mjh_fd_tangent too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
+ * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent and mjh_postconstraint too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
  * the elapsed milliseconds and the kernel id (MJH_KERNEL_*).  Returns the number of launches (<= max) or a negative code. */
 int mjh_debug_phase_timing(int enable);
 int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
@@ -618,7 +652,8 @@ void mjh_debug_set_stamps(void* dev_ptr);
  * loaded whole, the vector, the result).  MJH_KERNEL_FD_PERTURB / MJH_KERNEL_FD_DIFFERENCE: per slot, the input leaves a step of this model can read,
  * read and written (an upper bound: the caller's Data may lack some), and one slot's qpos, qvel, act and sensordata read, with [1] = one column of A and C.  MJH_KERNEL_FD_VJP: per (environment, column), one slot's and the nominal
  * qpos, qvel, act and sensordata (an upper bound: a one-sided column reads the nominal, a centered state column its two slots) and the cotangent, with
- * [1] = one entry of gx / gu; MJH_KERNEL_FD_TANGENT: per environment, qpos and a cotangent of at most nq entries read, one written.  Returns 0, or -2 when this model's step does not launch that kernel. */
+ * [1] = one entry of gx / gu; MJH_KERNEL_FD_TANGENT: per environment, qpos and a cotangent of at most nq entries read, one written.  MJH_KERNEL_POSTCON (an
+ * mjh_postconstraint call with all three flags): per environment, every input leaf of mjhPostconArgs once, from the leaf extents, and the six outputs.  Returns 0, or -2 when this model's step does not launch that kernel. */
 int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes);
 
 /* last error message of the calling thread ("" if none) */

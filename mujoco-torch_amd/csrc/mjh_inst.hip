@@ -10,6 +10,7 @@
 #include "mjh_render.h"
 #include "mjh_support.h"
 #include "mjh_fd.h"
+#include "mjh_postcon.h"
 #include "mjh_instances.h"
 
 #define MJH_CAT_(a, b) a##b
@@ -40,4 +41,7 @@ template __global__ void mjh_fd_perturb_kernel<MJH_INST_REAL>(FdPerturbArgs<MJH_
 template __global__ void mjh_fd_difference_kernel<MJH_INST_REAL>(FdDiffArgs<MJH_INST_REAL>);
 template __global__ void mjh_fd_vjp_kernel<MJH_INST_REAL>(FdVjpArgs<MJH_INST_REAL>);
 template __global__ void mjh_fd_tangent_kernel<MJH_INST_REAL>(FdTangentArgs<MJH_INST_REAL>);
+#endif
+#if MJH_INST_GROUP == 24
+template __global__ void mjh_postcon_kernel<MJH_INST_REAL>(PostconArgs<MJH_INST_REAL>);
 #endif

@@ -22,6 +22,7 @@
 #include "mjh_render.h"
 #include "mjh_support.h"
 #include "mjh_fd.h"
+#include "mjh_postcon.h"
 #include "mjh_instances.h"
 
 // the kernels are compiled in their own translation units (mjh_inst.hip, one per build group): this file is the host side only
@@ -54,6 +55,8 @@ extern template __global__ void mjh_fd_vjp_kernel<double>(FdVjpArgs<double>);
 extern template __global__ void mjh_fd_vjp_kernel<float>(FdVjpArgs<float>);
 extern template __global__ void mjh_fd_tangent_kernel<double>(FdTangentArgs<double>);
 extern template __global__ void mjh_fd_tangent_kernel<float>(FdTangentArgs<float>);
+extern template __global__ void mjh_postcon_kernel<double>(PostconArgs<double>);  // (build group 24)
+extern template __global__ void mjh_postcon_kernel<float>(PostconArgs<float>);
 #undef X_
 #undef S_
 #undef C_
@@ -127,6 +130,7 @@ struct mjhModel {
   int fuse_all = 0;                        // ... and the whole pass as ONE kernel (SOL2_PASS, MJH_KERNEL_PASS): kernel 13's stages in front of kernel 14's, one arena of max(AR_KCV, AR_CS)
   int lds_all = 0;
   int inv_lanes = 0, inv_envs = 0, inv_chunk = 0, inv_lds_env = 0;  // inverse-dynamics tail (mjh_inverse_kernel): lanes per environment, environments per workgroup, rows per LDS chunk, REALs per environment
+  int pc_lanes = 0, pc_envs = 0, pc_lds_env = 0;  // body accelerations and forces (mjh_postcon_kernel): lanes per environment, environments per workgroup, REALs per environment; pc_envs == 0: the model does not fit
   int any_damping = 0;                     // some dof_damping != 0 (discrete_acc's eulerdamp re-solve applies)
   int fuse_stage = 0;                      // every RK4 stage of a small Newton model runs as ONE launch (SOL2_STAGE, MJH_KERNEL_STAGE; stage 0 too unless MJH_FUSE_STAGE0=0): kernel 13's stages, the constraint phase (kernel 8) and the register solver's first tier
   int lds_stage = 0;                       // ... dynamic LDS of one of its four-environment workgroups
@@ -715,6 +719,16 @@ int plan(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
     out->inv_chunk = chunk;
     out->inv_lds_env = (3 * nv + chunk + chunk * nv + 1) & ~1;
   }
+  {  // body accelerations and forces (mjh_postcon.h): one environment per 16 / 32 / 64 lanes (from nbody), up to 256 lanes per workgroup; an environment keeps seven
+     // per-body arrays (30 reals a body) and the contacts' moved wrenches (14 reals a contact) in LDS.  A workgroup is planned for kLdsWg bytes; an environment that
+     // needs more than that runs alone, and one that does not fit a CU's LDS is refused by mjh_postconstraint (the rest of the library still serves the model).
+    const int nb = d->nbody;
+    out->pc_lanes = nb <= 16 ? 16 : (nb <= 32 ? 32 : 64);
+    out->pc_lds_env = (30 * nb + 14 * d->ncon + 1) & ~1;
+    const int64_t env_bytes = (int64_t)out->pc_lds_env * (int64_t)sizeof(REAL);
+    const int fit = (int)std::min<int64_t>(MJH_POSTCON_WG / out->pc_lanes, kLdsWg / std::max<int64_t>(env_bytes, 1));
+    out->pc_envs = env_bytes > kLdsCu ? 0 : std::max(fit, 1);
+  }
   // phases that are register-bound (not LDS-bound) run two environments per wavefront, 32 lanes each: the same
   // VGPR budget then keeps twice as many environments in flight (mjh_kernels.h, Env<REAL, W>)
   out->pack2[AR_KIN] = 2 * out->lds(AR_KIN) <= kLdsWg;
@@ -860,6 +874,7 @@ int grant_lds(const mjhModel* m) {
   }
   if (m->fuse_stage || m->fuse_tail) HIP_TRY(allow_sol2_lds<REAL>(SOL2_STAGE, std::max(m->lds_stage, m->lds_tail)));
   HIP_TRY(allow_lds(&mjh_inverse_kernel<REAL>, kLdsWg));  // (the inverse tail's LDS_BUDGET plus the rounding of lds_env)
+  if (m->pc_envs > 0) HIP_TRY(allow_lds(&mjh_postcon_kernel<REAL>, std::max(kLdsWg, m->pc_envs * m->pc_lds_env * (int)sizeof(REAL))));
   return 0;
 }
 
@@ -1435,6 +1450,57 @@ int run_support(const mjhModel* m, const DevModel<REAL>& M, const mjhSupportArgs
   return 0;
 }
 
+// body accelerations and forces of a finished forward pass (mjh_postcon.h): MuJoCo's mj_rnePostConstraint / mj_subtreeVel and the sensors that read them, one launch
+template <typename REAL>
+int run_postcon(const mjhModel* m, const DevModel<REAL>& M, const mjhPostconArgs* x, void* stream) {
+  const int f = x->flags;
+  if (f <= 0 || f > (MJH_POSTCON_RNE | MJH_POSTCON_SUBTREE | MJH_POSTCON_SENSORS)) return fail(-22, "postconstraint: unknown flags");
+  if ((f & MJH_POSTCON_SENSORS) && (f & (MJH_POSTCON_RNE | MJH_POSTCON_SUBTREE)) != (MJH_POSTCON_RNE | MJH_POSTCON_SUBTREE))
+    return fail(-22, "postconstraint: the sensors need both the rne and the subtree part");
+  if (x->B < 0) return fail(-22, "postconstraint: B must be >= 0");
+  if (x->B == 0) return 0;
+  if (m->pc_envs == 0) return fail(-12, "postconstraint: the model's bodies and contacts do not fit the LDS of one workgroup");
+  const bool rne = f & MJH_POSTCON_RNE, sub = f & MJH_POSTCON_SUBTREE, sns = (f & MJH_POSTCON_SENSORS) && M.nsensordata > 0;
+  if (!x->cvel || !x->xipos || !x->subtree_com) return fail(-22, "postconstraint: null pointer (cvel / xipos / subtree_com)");
+  if (rne && (!x->cinert || !x->xfrc_applied || !x->cacc || !x->cfrc_int || !x->cfrc_ext || (M.nv > 0 && (!x->qvel || !x->qacc || !x->cdof || !x->cdof_dot)) ||
+              (M.ncon > 0 && M.nefc > 0 && (!x->efc_force || !x->contact_pos || !x->contact_frame || !x->contact_friction || !x->contact_dim || !x->contact_geom || !x->contact_efc_address))))
+    return fail(-22, "postconstraint: null pointer (rne leaves)");
+  if (sub && (!x->ximat || !x->body_subtreemass || !x->subtree_linvel || !x->subtree_angmom)) return fail(-22, "postconstraint: null pointer (subtree leaves)");
+  if (sns && (!x->sensordata_in || !x->sensordata || (M.nsite > 0 && (!x->site_xpos || !x->site_xmat)))) return fail(-22, "postconstraint: null pointer (sensor leaves)");
+  hipStream_t s = (hipStream_t)stream;
+  timing_begin(s);
+  PostconArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+#define P_(n) a.n = reinterpret_cast<const REAL*>(x->n);
+  P_(qvel) P_(qacc) P_(cdof) P_(cdof_dot) P_(cvel) P_(cinert) P_(xipos) P_(ximat) P_(subtree_com) P_(efc_force) P_(contact_pos) P_(contact_frame) P_(contact_friction)
+  P_(site_xpos) P_(site_xmat) P_(sensordata_in) P_(body_subtreemass)
+#undef P_
+  a.xfrc = reinterpret_cast<const REAL*>(x->xfrc_applied);
+  a.contact_dim = x->contact_dim; a.contact_geom = x->contact_geom; a.contact_efc_address = x->contact_efc_address;
+  a.body_parentid = M.body_parentid; a.body_rootid = M.body_rootid; a.body_dofadr = M.body_dofadr; a.body_dofnum = M.body_dofnum; a.body_depth = M.body_depth;
+  a.body_chain = M.body_chain; a.body_subtree_end = M.body_subtree_end; a.geom_bodyid = M.geom_bodyid;
+  a.sns_type = M.sns_type; a.sns_adr = M.sns_adr; a.sns_objid = M.sns_objid; a.sns_bodyid = M.sns_bodyid; a.sns_rootid = M.sns_rootid; a.sns_datatype = M.sns_datatype;
+  a.slot_sensor = M.slot_sensor; a.body_mass = M.body_mass; a.body_inertia = M.body_inertia; a.sns_cutoff = M.sns_cutoff;
+#define O_(n) a.n = reinterpret_cast<REAL*>(x->n);
+  O_(cacc) O_(cfrc_int) O_(cfrc_ext) O_(subtree_linvel) O_(subtree_angmom) O_(sensordata)
+#undef O_
+  const bool nograv = M.disableflags & DSBL_GRAVITY;
+  for (int k = 0; k < 3; k++) a.cacc0[k] = nograv ? (REAL)0 : -M.gravity[k];
+  a.nbody = M.nbody; a.nv = M.nv; a.nefc = M.nefc; a.ngeom = M.ngeom; a.nsite = M.nsite; a.nsensordata = M.nsensordata; a.max_depth = M.max_depth;
+  a.ncon = M.nefc > 0 ? M.ncon : 0;  // (without constraint rows there is no force to gather)
+  a.pyramidal = M.cone != CONE_ELLIPTIC;
+  a.flags = (rne ? MJH_POSTCON_RNE : 0) | (sub ? MJH_POSTCON_SUBTREE : 0) | (sns ? MJH_POSTCON_SENSORS : 0);
+  a.lanes = m->pc_lanes; a.envs = m->pc_envs; a.lds_env = m->pc_lds_env;
+  const size_t lds = (size_t)a.envs * a.lds_env * sizeof(REAL);
+  if (const int rc = launch_cut(x->B, a.envs, [&](int64_t first, int64_t n, unsigned grid) {
+        a.env_begin = first; a.env_count = n;
+        hipLaunchKernelGGL((mjh_postcon_kernel<REAL>), dim3(grid), dim3(a.envs * a.lanes), lds, s, a);
+      }))
+    return rc;
+  timing_mark(s, MJH_KERNEL_POSTCON);
+  return 0;
+}
+
 // ---- finite-difference transition Jacobians (mjh_fd.h): the launches on either side of the caller's mjh_step over the perturbed environments ----
 
 // 4-byte words per environment of every mjhData slot, in struct order: reals, int32, int64, then the trailing input-only leaves
@@ -1647,6 +1713,11 @@ int mjh_support(const mjhModel* m, const mjhSupportArgs* args, void* stream) {
   return m->dtype == MJH_F64 ? run_support<double>(m, m->m64, args, stream) : run_support<float>(m, m->m32, args, stream);
 }
 
+int mjh_postconstraint(const mjhModel* m, const mjhPostconArgs* args, void* stream) {
+  if (!m || !args) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_postcon<double>(m, m->m64, args, stream) : run_postcon<float>(m, m->m32, args, stream);
+}
+
 int mjh_fd_perturb(const mjhModel* m, const mjhData* in, mjhData* scratch, int64_t B, int col0, int ncol, double eps, int centered, void* stream) {
   if (!m || !in || !scratch) return fail(-22, "null argument");
   return m->dtype == MJH_F64 ? run_fd_perturb<double>(m, m->m64, in, scratch, B, col0, ncol, eps, centered, stream)
@@ -1801,6 +1872,15 @@ static int kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes, b
       read_write_bytes[0] = 2 * nq * R;
       read_write_bytes[1] = nq * R;
     }
+    return 0;
+  }
+  if (kernel == MJH_KERNEL_POSTCON) {  // body accelerations and forces (mjh_postconstraint, all three flags): every input leaf once, the six outputs
+    const int64_t R = f64 ? 8 : 4, nv = f64 ? m->m64.nv : m->m32.nv, nb = f64 ? m->m64.nbody : m->m32.nbody, nefc = f64 ? m->m64.nefc : m->m32.nefc;
+    const int64_t ncon = nefc > 0 ? (f64 ? m->m64.ncon : m->m32.ncon) : 0, ns = f64 ? m->m64.nsite : m->m32.nsite, nsd = f64 ? m->m64.nsensordata : m->m32.nsensordata;
+    if (m->pc_envs == 0) return -2;
+    // qvel qacc cdof cdof_dot | cvel cinert xipos ximat subtree_com xfrc_applied | efc_force | contact pos frame friction | dim, geom, efc_address | sites, sensordata
+    read_write_bytes[0] = (14 * nv + (6 + 10 + 3 + 9 + 3 + 6) * nb + nefc + 17 * ncon + 12 * ns + nsd) * R + ncon * (4 + 16 + 8);
+    read_write_bytes[1] = (24 * nb + nsd) * R;
     return 0;
   }
   if (kernel == MJH_KERNEL_INVERSE) {  // the inverse-dynamics tail (mjh_inverse): efc_J and qM once, efc_D / efc_aref, qacc, qfrc_bias / passive in; efc_force, qfrc_constraint, qfrc_inverse out.

@@ -2,7 +2,7 @@
 
 Drop-in for the hot path of vmoens/mujoco-torch (``mujoco_torch/__init__.py:41-136``):
 ``step``, ``forward``, ``inverse``, ``transition_fd``, ``transition_vjp``, ``differentiable_step``, ``tangent_pull``, ``tangent_push``, ``ray``, ``ray_geom``, ``render``, ``render_batch``, ``precompute_render_data``,
-``jac``, ``apply_ft``, ``xfrc_accumulate``, ``mul_m``, ``solve_m``, ``full_m``, ``device_put``, ``make_data`` and the ``Model`` / ``Data`` / ``Contact`` /
+``rne_postconstraint``, ``subtree_vel``, ``fwd_postconstraint``, ``jac``, ``apply_ft``, ``xfrc_accumulate``, ``mul_m``, ``solve_m``, ``full_m``, ``device_put``, ``make_data`` and the ``Model`` / ``Data`` / ``Contact`` /
 ``Option`` schema.  Use as ``import mujoco_torch_amd as mujoco_torch``.
 """
 
@@ -32,6 +32,7 @@ from .device import device_get_into, device_put  # noqa: F401
 from .forward import forward, inverse, reset_where, step  # noqa: F401
 from .derivative import differentiable_step, tangent_pull, tangent_push, transition_fd, transition_vjp  # noqa: F401
 from .io import make_data  # noqa: F401
+from .postconstraint import fwd_postconstraint, rne_postconstraint, subtree_vel  # noqa: F401
 from .ray import ray, ray_geom  # noqa: F401
 from .render import precompute_render_data, render, render_batch  # noqa: F401
 from .support import apply_ft, full_m, jac, mul_m, solve_m, xfrc_accumulate  # noqa: F401

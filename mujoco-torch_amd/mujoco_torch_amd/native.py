@@ -242,6 +242,15 @@ class SupportArgs(ctypes.Structure):
         ("vec", ctypes.c_void_p), ("vec_env", ctypes.c_int64), ("vec_k", ctypes.c_int64), ("out0", ctypes.c_void_p), ("out1", ctypes.c_void_p)]
 
 
+class PostconArgs(ctypes.Structure):
+    """include/mjhip.h mjhPostconArgs: one mjh_postconstraint call (device pointers)."""
+
+    _fields_ = [("flags", ctypes.c_int32), ("reserved", ctypes.c_int32), ("B", ctypes.c_int64)] + [(n, ctypes.c_void_p) for n in (
+        "qvel", "qacc", "cdof", "cdof_dot", "cvel", "cinert", "xipos", "ximat", "subtree_com", "xfrc_applied", "efc_force", "contact_pos", "contact_frame",
+        "contact_friction", "contact_dim", "contact_geom", "contact_efc_address", "site_xpos", "site_xmat", "sensordata_in", "body_subtreemass", "cacc", "cfrc_int",
+        "cfrc_ext", "subtree_linvel", "subtree_angmom", "sensordata")]
+
+
 def load_library(path: str | None = None):
     """Loads libmjhip.so (once). Raises if it has not been built: no fallback path exists."""
     global _lib
@@ -276,6 +285,9 @@ def load_library(path: str | None = None):
     if hasattr(lib, "mjh_support"):  # (likewise a build from before the support functions)
         lib.mjh_support.argtypes = [ctypes.c_void_p, ctypes.POINTER(SupportArgs), ctypes.c_void_p]
         lib.mjh_support.restype = ctypes.c_int
+    if hasattr(lib, "mjh_postconstraint"):  # (likewise a build from before rne_postconstraint / subtree_vel)
+        lib.mjh_postconstraint.argtypes = [ctypes.c_void_p, ctypes.POINTER(PostconArgs), ctypes.c_void_p]
+        lib.mjh_postconstraint.restype = ctypes.c_int
     lib.mjh_reset_where.argtypes = [ctypes.c_void_p, ctypes.POINTER(DataPtrs), ctypes.POINTER(DataPtrs), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
     lib.mjh_reset_where.restype = ctypes.c_int
     lib.mjh_debug_phase_timing.argtypes = [ctypes.c_int]
