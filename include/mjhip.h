@@ -15,6 +15,7 @@
  *   mjh_fd_vjp / mjh_fd_tangent        <- its vector-Jacobian product and the quaternion coordinate maps of a gradient through one step
  *   mjh_support        <- support.jac / apply_ft / xfrc_accumulate, smooth.mul_m / solve_m (_src/support.py:138-194, smooth.py:335-374)
  *   mjh_postconstraint <- MuJoCo's mj_rnePostConstraint / mj_subtreeVel (MJX smooth.rne_postconstraint / subtree_vel; the reference has no counterpart)
+ *   mjh_contact_sensors <- MuJoCo's mj_contactForce (MJX support.contact_force) and its touch / framelinacc / frameangacc sensors (the reference evaluates none of them)
  *
  * Conventions
  *  - every Data leaf is batch-major contiguous: shape [B, ...] exactly as
@@ -40,7 +41,7 @@
 extern "C" {
 #endif
 
-#define MJH_ABI_VERSION 16
+#define MJH_ABI_VERSION 17
 
 /* ---- dtype / flags ------------------------------------------------------------------- */
 #define MJH_F64 0
@@ -93,6 +94,7 @@ extern "C" {
 #define MJH_KERNEL_FD_VJP 30     /* mjh_fd_vjp: those columns contracted with a cotangent instead of stored            */
 #define MJH_KERNEL_FD_TANGENT 31 /* mjh_fd_tangent: cotangents between qpos coordinates and the tangent space          */
 #define MJH_KERNEL_POSTCON 32    /* mjh_postconstraint: cacc, cfrc_int, cfrc_ext, subtree_linvel, subtree_angmom       */
+#define MJH_KERNEL_CONSENS 33    /* mjh_contact_sensors: contact forces, touch / framelinacc / frameangacc sensors     */
 
 /* pair-function ids of the static collision table (collision_driver.py:106-125) */
 #define MJH_FN_PLANE_SPHERE 0
@@ -573,6 +575,38 @@ typedef struct mjhPostconArgs {
  * negative code (a model whose bodies and contacts do not fit the LDS of a workgroup is refused); B == 0 is a no-op. */
 int mjh_postconstraint(const mjhModel* m, const mjhPostconArgs* args, void* hip_stream);
 
+/* mjh_contact_sensors flags: what one launch computes */
+#define MJH_CONSENS_FORCES 1  /* the force of every contact slot, [B, ncon, 6] (MuJoCo's mj_contactForce)                          */
+#define MJH_CONSENS_SENSORS 2 /* the sensordata slots of the touch, framelinacc and frameangacc sensors listed in sns                */
+#define MJH_CONSENS_WORLD 4   /* with FORCES: rows in the world frame, [frame^T w[0:3], frame^T w[3:6]], instead of the contact frame */
+
+/* one mjh_contact_sensors call.  Every pointer is device memory; the leaves are batch-major over B environments, reals are of the model's dtype.  FORCES reads
+ * efc_force [B, nefc], contact_pos [B, ncon, 3], contact_frame [B, ncon, 9], contact_friction [B, ncon, 5], contact_dim [B, ncon] (int32), contact_geom [B, ncon, 2] /
+ * contact_efc_address [B, ncon] (int64) and writes force [B, ncon, 6]: per slot [force(3), torque(3)] in the contact frame, decoded from efc_force as mjh_postconstraint
+ * decodes it; a slot whose geom ids are not in [0, ngeom), or whose rows do not lie inside efc_force, gives zeros.  SENSORS evaluates the nsens sensors of sns
+ * ([nsens, 8] int32: sensor type (0 touch, 33 framelinacc, 34 frameangacc), sensordata address, object id, leaf kind of the object's point (0 xipos, 1 xpos, 2 geom_xpos,
+ * 3 site_xpos, 4 cam_xpos), the body the object rides on, that body's root, datatype, the site's geom type for touch) with sns_cutoff [nsens] (reals) and writes ONLY their
+ * slots of sensordata [B, nsensordata]: touch reads the contact leaves above, site_xpos [B, nsite, 3], site_xmat [B, nsite, 9] and site_size [nsite, 3] (the caller's
+ * Model); the frame sensors read cvel / cacc [B, nbody, 6] (cacc: mjh_postconstraint's), subtree_com [B, nbody, 3] and the leaf of their kind (xipos, xpos [B, nbody, 3],
+ * geom_xpos [B, ngeom, 3], site_xpos, cam_xpos [B, ncam, 3]).  The definitions are in csrc/mjh_contact_sensors.h.  sns rows must address this model (the kernel does not
+ * check them).  No output may alias an input. */
+typedef struct mjhContactSensorArgs {
+  int32_t flags, nsens;
+  int64_t B;
+  const void *efc_force, *contact_pos, *contact_frame, *contact_friction;
+  const int32_t* contact_dim;
+  const int64_t *contact_geom, *contact_efc_address;
+  const void *site_xpos, *site_xmat, *cvel, *cacc, *subtree_com, *xipos, *xpos, *geom_xpos, *cam_xpos;
+  const void* site_size;
+  const int32_t* sns;
+  const void* sns_cutoff;
+  void *force, *sensordata;
+} mjhContactSensorArgs;
+
+/* contact forces and / or the touch, framelinacc and frameangacc sensors of a finished forward pass (see mjhContactSensorArgs) as ONE launch.  Runs on hip_stream
+ * without host synchronisation.  Returns 0 or a negative code (a model whose contacts do not fit the LDS of a workgroup is refused); B == 0 is a no-op. */
+int mjh_contact_sensors(const mjhModel* m, const mjhContactSensorArgs* args, void* hip_stream);
+
 /* Finite-difference transition Jacobians (MuJoCo's mjd_transitionFD), as two launches around an mjh_step of the caller's own.  State x = (qpos in
  * tangent space: nv, qvel: nv, act: na), ns = 2 nv + na; column c in [0, ns) nudges entry c of x, column ns + i nudges ctrl[i].  A call serves the
  * columns [col0, col0 + ncol) of all B environments.  Each column of an environment owns nside = (centered ? 2 : 1) environments ("slots") of a
@@ -633,7 +667,7 @@ int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsi
 int mjh_model_lds_bytes(const mjhModel* m, int arena);
 
 /* measurement aid used by bench.py for the per-kernel roofline: while enabled, every kernel launch of mjh_step / mjh_forward is
- * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent and mjh_postconstraint too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
+ * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_postconstraint and mjh_contact_sensors too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
  * the elapsed milliseconds and the kernel id (MJH_KERNEL_*).  Returns the number of launches (<= max) or a negative code. */
 int mjh_debug_phase_timing(int enable);
 int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);

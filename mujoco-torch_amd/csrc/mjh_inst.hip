@@ -11,6 +11,7 @@
 #include "mjh_support.h"
 #include "mjh_fd.h"
 #include "mjh_postcon.h"
+#include "mjh_contact_sensors.h"
 #include "mjh_instances.h"
 
 #define MJH_CAT_(a, b) a##b
@@ -44,4 +45,7 @@ template __global__ void mjh_fd_tangent_kernel<MJH_INST_REAL>(FdTangentArgs<MJH_
 #endif
 #if MJH_INST_GROUP == 24
 template __global__ void mjh_postcon_kernel<MJH_INST_REAL>(PostconArgs<MJH_INST_REAL>);
+#endif
+#if MJH_INST_GROUP == 25
+template __global__ void mjh_consens_kernel<MJH_INST_REAL>(ConSensArgs<MJH_INST_REAL>);
 #endif

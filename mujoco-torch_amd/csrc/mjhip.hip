@@ -23,6 +23,7 @@
 #include "mjh_support.h"
 #include "mjh_fd.h"
 #include "mjh_postcon.h"
+#include "mjh_contact_sensors.h"
 #include "mjh_instances.h"
 
 // the kernels are compiled in their own translation units (mjh_inst.hip, one per build group): this file is the host side only
@@ -57,6 +58,8 @@ extern template __global__ void mjh_fd_tangent_kernel<double>(FdTangentArgs<doub
 extern template __global__ void mjh_fd_tangent_kernel<float>(FdTangentArgs<float>);
 extern template __global__ void mjh_postcon_kernel<double>(PostconArgs<double>);  // (build group 24)
 extern template __global__ void mjh_postcon_kernel<float>(PostconArgs<float>);
+extern template __global__ void mjh_consens_kernel<double>(ConSensArgs<double>);  // (build group 25)
+extern template __global__ void mjh_consens_kernel<float>(ConSensArgs<float>);
 #undef X_
 #undef S_
 #undef C_
@@ -131,6 +134,7 @@ struct mjhModel {
   int lds_all = 0;
   int inv_lanes = 0, inv_envs = 0, inv_chunk = 0, inv_lds_env = 0;  // inverse-dynamics tail (mjh_inverse_kernel): lanes per environment, environments per workgroup, rows per LDS chunk, REALs per environment
   int pc_lanes = 0, pc_envs = 0, pc_lds_env = 0;  // body accelerations and forces (mjh_postcon_kernel): lanes per environment, environments per workgroup, REALs per environment; pc_envs == 0: the model does not fit
+  int cs_lds_env = 0, cs_ok = 0;  // contact forces and their sensors (mjh_consens_kernel): REALs per environment (a multiple of 4); cs_ok == 0: the model's contacts do not fit
   int any_damping = 0;                     // some dof_damping != 0 (discrete_acc's eulerdamp re-solve applies)
   int fuse_stage = 0;                      // every RK4 stage of a small Newton model runs as ONE launch (SOL2_STAGE, MJH_KERNEL_STAGE; stage 0 too unless MJH_FUSE_STAGE0=0): kernel 13's stages, the constraint phase (kernel 8) and the register solver's first tier
   int lds_stage = 0;                       // ... dynamic LDS of one of its four-environment workgroups
@@ -729,6 +733,11 @@ int plan(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
     const int fit = (int)std::min<int64_t>(MJH_POSTCON_WG / out->pc_lanes, kLdsWg / std::max<int64_t>(env_bytes, 1));
     out->pc_envs = env_bytes > kLdsCu ? 0 : std::max(fit, 1);
   }
+  {  // contact forces and their sensors (mjh_contact_sensors.h): an environment keeps MJH_CONSENS_LDS_CONTACT reals a contact slot in LDS; the lanes per environment
+     // and the environments per workgroup follow from the call's sensor count (run_consens)
+    out->cs_lds_env = std::max(4, (MJH_CONSENS_LDS_CONTACT * d->ncon + 3) & ~3);
+    out->cs_ok = (int64_t)out->cs_lds_env * (int64_t)sizeof(REAL) <= kLdsCu;
+  }
   // phases that are register-bound (not LDS-bound) run two environments per wavefront, 32 lanes each: the same
   // VGPR budget then keeps twice as many environments in flight (mjh_kernels.h, Env<REAL, W>)
   out->pack2[AR_KIN] = 2 * out->lds(AR_KIN) <= kLdsWg;
@@ -875,6 +884,7 @@ int grant_lds(const mjhModel* m) {
   if (m->fuse_stage || m->fuse_tail) HIP_TRY(allow_sol2_lds<REAL>(SOL2_STAGE, std::max(m->lds_stage, m->lds_tail)));
   HIP_TRY(allow_lds(&mjh_inverse_kernel<REAL>, kLdsWg));  // (the inverse tail's LDS_BUDGET plus the rounding of lds_env)
   if (m->pc_envs > 0) HIP_TRY(allow_lds(&mjh_postcon_kernel<REAL>, std::max(kLdsWg, m->pc_envs * m->pc_lds_env * (int)sizeof(REAL))));
+  if (m->cs_ok) HIP_TRY(allow_lds(&mjh_consens_kernel<REAL>, std::max(kLdsWg, m->cs_lds_env * (int)sizeof(REAL))));
   return 0;
 }
 
@@ -1501,6 +1511,56 @@ int run_postcon(const mjhModel* m, const DevModel<REAL>& M, const mjhPostconArgs
   return 0;
 }
 
+// contact forces and the touch / framelinacc / frameangacc sensors of a finished forward pass (mjh_contact_sensors.h), one launch
+template <typename REAL>
+int run_consens(const mjhModel* m, const DevModel<REAL>& M, const mjhContactSensorArgs* x, void* stream) {
+  const int f = x->flags;
+  if (f <= 0 || f > (MJH_CONSENS_FORCES | MJH_CONSENS_SENSORS | MJH_CONSENS_WORLD) || !(f & (MJH_CONSENS_FORCES | MJH_CONSENS_SENSORS)))
+    return fail(-22, "contact_sensors: unknown flags");
+  if ((f & MJH_CONSENS_WORLD) && !(f & MJH_CONSENS_FORCES)) return fail(-22, "contact_sensors: the world frame applies to the forces");
+  if (x->B < 0 || x->nsens < 0) return fail(-22, "contact_sensors: B and nsens must be >= 0");
+  if (x->B == 0) return 0;
+  if (!m->cs_ok) return fail(-12, "contact_sensors: the model's contacts do not fit the LDS of one workgroup");
+  const int ncon = M.nefc > 0 ? M.ncon : 0;  // (without constraint rows there is no force to decode)
+  const bool forces = (f & MJH_CONSENS_FORCES) && ncon > 0, sns = (f & MJH_CONSENS_SENSORS) && x->nsens > 0 && M.nsensordata > 0;
+  if (!forces && !sns) return 0;
+  if (ncon > 0 && (!x->efc_force || !x->contact_pos || !x->contact_frame || !x->contact_friction || !x->contact_dim || !x->contact_geom || !x->contact_efc_address))
+    return fail(-22, "contact_sensors: null pointer (contact leaves)");
+  if (forces && !x->force) return fail(-22, "contact_sensors: null pointer (force)");
+  if (sns && (!x->sns || !x->sns_cutoff || !x->sensordata || !x->cvel || !x->cacc || !x->subtree_com || !x->xipos || !x->xpos || (M.ngeom > 0 && !x->geom_xpos) ||
+              (M.nsite > 0 && (!x->site_xpos || !x->site_xmat || !x->site_size)) || (M.ncam > 0 && !x->cam_xpos)))
+    return fail(-22, "contact_sensors: null pointer (sensor leaves)");
+  hipStream_t s = (hipStream_t)stream;
+  timing_begin(s);
+  ConSensArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+#define P_(n) a.n = reinterpret_cast<const REAL*>(x->n);
+  P_(efc_force) P_(contact_pos) P_(contact_frame) P_(contact_friction) P_(site_xpos) P_(site_xmat) P_(cvel) P_(cacc) P_(subtree_com) P_(xipos) P_(xpos) P_(geom_xpos)
+  P_(cam_xpos) P_(site_size) P_(sns_cutoff)
+#undef P_
+  a.contact_dim = x->contact_dim; a.contact_geom = x->contact_geom; a.contact_efc_address = x->contact_efc_address;
+  a.geom_bodyid = M.geom_bodyid; a.sns = x->sns;
+  a.force = reinterpret_cast<REAL*>(x->force); a.sensordata = reinterpret_cast<REAL*>(x->sensordata);
+  a.nbody = M.nbody; a.ncon = ncon; a.nefc = M.nefc; a.ngeom = M.ngeom; a.nsite = M.nsite; a.ncam = M.ncam; a.nsensordata = M.nsensordata;
+  a.nsens = sns ? x->nsens : 0;
+  a.pyramidal = M.cone != CONE_ELLIPTIC;
+  a.flags = (forces ? (f & (MJH_CONSENS_FORCES | MJH_CONSENS_WORLD)) : 0) | (sns ? MJH_CONSENS_SENSORS : 0);
+  a.contacts = ncon > 0;
+  const int widest = std::max(ncon, a.nsens);
+  a.lanes = widest <= 16 ? 16 : (widest <= 32 ? 32 : 64);
+  a.lds_env = m->cs_lds_env;
+  const int64_t env_bytes = (int64_t)a.lds_env * (int64_t)sizeof(REAL);
+  a.envs = (int)std::max<int64_t>(1, std::min<int64_t>(MJH_CONSENS_WG / a.lanes, kLdsWg / env_bytes));
+  const size_t lds = (size_t)a.envs * a.lds_env * sizeof(REAL);
+  if (const int rc = launch_cut(x->B, a.envs, [&](int64_t first, int64_t n, unsigned grid) {
+        a.env_begin = first; a.env_count = n;
+        hipLaunchKernelGGL((mjh_consens_kernel<REAL>), dim3(grid), dim3(a.envs * a.lanes), lds, s, a);
+      }))
+    return rc;
+  timing_mark(s, MJH_KERNEL_CONSENS);
+  return 0;
+}
+
 // ---- finite-difference transition Jacobians (mjh_fd.h): the launches on either side of the caller's mjh_step over the perturbed environments ----
 
 // 4-byte words per environment of every mjhData slot, in struct order: reals, int32, int64, then the trailing input-only leaves
@@ -1716,6 +1776,11 @@ int mjh_support(const mjhModel* m, const mjhSupportArgs* args, void* stream) {
 int mjh_postconstraint(const mjhModel* m, const mjhPostconArgs* args, void* stream) {
   if (!m || !args) return fail(-22, "null argument");
   return m->dtype == MJH_F64 ? run_postcon<double>(m, m->m64, args, stream) : run_postcon<float>(m, m->m32, args, stream);
+}
+
+int mjh_contact_sensors(const mjhModel* m, const mjhContactSensorArgs* args, void* stream) {
+  if (!m || !args) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_consens<double>(m, m->m64, args, stream) : run_consens<float>(m, m->m32, args, stream);
 }
 
 int mjh_fd_perturb(const mjhModel* m, const mjhData* in, mjhData* scratch, int64_t B, int col0, int ncol, double eps, int centered, void* stream) {

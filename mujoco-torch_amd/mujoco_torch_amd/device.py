@@ -216,6 +216,44 @@ def _sensor_tables(m) -> dict:
     return out
 
 
+# mjtObj -> (the Data leaf that holds the object's point, the Model table of the body it rides on): the objects of framelinacc / frameangacc
+_CS_LEAVES = {1: ("xipos", None), 2: ("xpos", None), 5: ("geom_xpos", "geom_bodyid"), 6: ("site_xpos", "site_bodyid"), 7: ("cam_xpos", "cam_bodyid")}
+CONTACT_SENSOR_LEAVES = ("xipos", "xpos", "geom_xpos", "site_xpos", "cam_xpos")  # leaf kind = index here
+CONTACT_SENSOR_COLUMNS = ("type", "adr", "objid", "kind", "bodyid", "rootid", "datatype", "sitetype")
+
+
+def _contact_sensor_tables(m) -> dict:
+    """The sensors that sit on contact forces and on cacc -- touch, framelinacc, frameangacc (contact_sensors.py, csrc/mjh_contact_sensors.h) --, one row per
+    sensor in sensor order: type, adr, object id, leaf kind (index into CONTACT_SENSOR_LEAVES; touch: site_xpos), the body the object rides on, its root,
+    datatype, the site's type (touch; else -1), and the cutoff.  No pass evaluates them (``tables.sensors`` does not list them): ``sensor_postconstraint`` does.
+    A reference frame (reftype / refid) on framelinacc / frameangacc is ignored, as MuJoCo ignores it."""
+    ns = int(getattr(m, "nsensor", 0) or 0)
+    out = dict(rows=np.zeros((0, len(CONTACT_SENSOR_COLUMNS)), dtype=np.int32), cutoff=np.zeros(0, dtype=np.float64))
+    if ns == 0 or (int(m.opt.disableflags) & DisableBit.SENSOR):
+        return out
+    A = lambda name: np.asarray(getattr(m, name))
+    stype, sobj, body_rootid = A("sensor_type"), A("sensor_objid"), A("body_rootid")
+    sobjtype = A("sensor_objtype") if hasattr(m, "sensor_objtype") else np.zeros(ns, dtype=np.int32)
+    rows, cutoff = [], []
+    for i in range(ns):
+        t, oid = int(stype[i]), int(sobj[i])
+        if t == int(_ST.TOUCH):
+            kind, body, sitetype = CONTACT_SENSOR_LEAVES.index("site_xpos"), int(A("site_bodyid")[oid]), int(A("site_type")[oid])
+        elif t in (int(_ST.FRAMELINACC), int(_ST.FRAMEANGACC)):
+            ot = int(sobjtype[i])
+            if ot not in _CS_LEAVES:
+                raise NotImplementedError(f"sensor {i}: frame sensors take body / xbody / geom / site / camera objects (objtype {ot})")
+            leaf, table = _CS_LEAVES[ot]
+            kind, body, sitetype = CONTACT_SENSOR_LEAVES.index(leaf), (oid if table is None else int(A(table)[oid])), -1
+        else:
+            continue
+        rows.append([t, int(A("sensor_adr")[i]), oid, kind, body, int(body_rootid[body]), int(A("sensor_datatype")[i]), sitetype])
+        cutoff.append(float(A("sensor_cutoff")[i]))
+    if rows:
+        out = dict(rows=np.array(rows, dtype=np.int32), cutoff=np.array(cutoff, dtype=np.float64))
+    return out
+
+
 class StaticTables:
     """Everything about a model that is constant across steps and environments.
 
@@ -328,6 +366,7 @@ def _build_tables(m, dtype) -> StaticTables:
     T.eq = _equality_tables(m, flags)
     assert T.eq["nrow"] == ne, (T.eq["nrow"], ne)
     T.sensors = _sensor_tables(m)
+    T.contact_sensors = _contact_sensor_tables(m)  # touch / framelinacc / frameangacc: evaluated by sensor_postconstraint, never by a pass
     T.lim_jnt = np.array(lim, dtype=np.int32)
     T.tendon = _tendon_tables(m, flags)
     T.nlt = len(T.tendon["lim"])  # tendon limit rows

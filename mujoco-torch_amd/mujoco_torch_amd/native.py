@@ -251,6 +251,14 @@ class PostconArgs(ctypes.Structure):
         "cfrc_ext", "subtree_linvel", "subtree_angmom", "sensordata")]
 
 
+class ContactSensorArgs(ctypes.Structure):
+    """include/mjhip.h mjhContactSensorArgs: one mjh_contact_sensors call (device pointers)."""
+
+    _fields_ = [("flags", ctypes.c_int32), ("nsens", ctypes.c_int32), ("B", ctypes.c_int64)] + [(n, ctypes.c_void_p) for n in (
+        "efc_force", "contact_pos", "contact_frame", "contact_friction", "contact_dim", "contact_geom", "contact_efc_address", "site_xpos", "site_xmat", "cvel", "cacc",
+        "subtree_com", "xipos", "xpos", "geom_xpos", "cam_xpos", "site_size", "sns", "sns_cutoff", "force", "sensordata")]
+
+
 def load_library(path: str | None = None):
     """Loads libmjhip.so (once). Raises if it has not been built: no fallback path exists."""
     global _lib
@@ -288,6 +296,9 @@ def load_library(path: str | None = None):
     if hasattr(lib, "mjh_postconstraint"):  # (likewise a build from before rne_postconstraint / subtree_vel)
         lib.mjh_postconstraint.argtypes = [ctypes.c_void_p, ctypes.POINTER(PostconArgs), ctypes.c_void_p]
         lib.mjh_postconstraint.restype = ctypes.c_int
+    if hasattr(lib, "mjh_contact_sensors"):  # (likewise a build from before contact_force / sensor_postconstraint)
+        lib.mjh_contact_sensors.argtypes = [ctypes.c_void_p, ctypes.POINTER(ContactSensorArgs), ctypes.c_void_p]
+        lib.mjh_contact_sensors.restype = ctypes.c_int
     lib.mjh_reset_where.argtypes = [ctypes.c_void_p, ctypes.POINTER(DataPtrs), ctypes.POINTER(DataPtrs), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
     lib.mjh_reset_where.restype = ctypes.c_int
     lib.mjh_debug_phase_timing.argtypes = [ctypes.c_int]
