@@ -16,6 +16,7 @@
  *   mjh_support        <- support.jac / apply_ft / xfrc_accumulate, smooth.mul_m / solve_m (_src/support.py:138-194, smooth.py:335-374)
  *   mjh_postconstraint <- MuJoCo's mj_rnePostConstraint / mj_subtreeVel (MJX smooth.rne_postconstraint / subtree_vel; the reference has no counterpart)
  *   mjh_contact_sensors <- MuJoCo's mj_contactForce (MJX support.contact_force) and its touch / framelinacc / frameangacc sensors (the reference evaluates none of them)
+ *   mjh_energy         <- MuJoCo's mj_energyPos / mj_energyVel and its joint / tendon limit and energy sensors (the reference evaluates none of them)
  *
  * Conventions
  *  - every Data leaf is batch-major contiguous: shape [B, ...] exactly as
@@ -41,7 +42,7 @@
 extern "C" {
 #endif
 
-#define MJH_ABI_VERSION 17
+#define MJH_ABI_VERSION 18
 
 /* ---- dtype / flags ------------------------------------------------------------------- */
 #define MJH_F64 0
@@ -95,6 +96,7 @@ extern "C" {
 #define MJH_KERNEL_FD_TANGENT 31 /* mjh_fd_tangent: cotangents between qpos coordinates and the tangent space          */
 #define MJH_KERNEL_POSTCON 32    /* mjh_postconstraint: cacc, cfrc_int, cfrc_ext, subtree_linvel, subtree_angmom       */
 #define MJH_KERNEL_CONSENS 33    /* mjh_contact_sensors: contact forces, touch / framelinacc / frameangacc sensors     */
+#define MJH_KERNEL_ENERGY 34     /* mjh_energy: potential / kinetic energy, joint / tendon limit and energy sensors     */
 
 /* pair-function ids of the static collision table (collision_driver.py:106-125) */
 #define MJH_FN_PLANE_SPHERE 0
@@ -607,6 +609,35 @@ typedef struct mjhContactSensorArgs {
  * without host synchronisation.  Returns 0 or a negative code (a model whose contacts do not fit the LDS of a workgroup is refused); B == 0 is a no-op. */
 int mjh_contact_sensors(const mjhModel* m, const mjhContactSensorArgs* args, void* hip_stream);
 
+/* mjh_energy flags: what one launch computes */
+#define MJH_ENERGY_POS 1     /* the potential energy, energy[:, 0] (MuJoCo's mj_energyPos)                                                   */
+#define MJH_ENERGY_VEL 2     /* the kinetic energy, energy[:, 1] (mj_energyVel)                                                             */
+#define MJH_ENERGY_SENSORS 4 /* the sensordata slots of the joint / tendon limit and energy sensors listed in sns                            */
+
+/* one mjh_energy call.  Every pointer is device memory; the leaves are batch-major over B environments, reals are of the model's dtype.  The MODEL VALUES are
+ * arguments of the call (the caller's Model, not the blob): gravity [3], body_mass [nbody], jnt_stiffness [njnt], qpos_spring [nq], jnt_range [njnt, 2],
+ * jnt_margin [njnt], tendon_stiffness [ntendon], tendon_lengthspring [ntendon, 2], tendon_range [ntendon, 2], tendon_margin [ntendon], sns_cutoff [nsens].
+ * POS reads xipos [B, nbody, 3], qpos [B, nq] and ten_length [B, ntendon] -- the state the pass ran on -- and writes energy[:, 0]; VEL reads qvel [B, nv] and the
+ * pass's dense qM [B, nv, nv] and writes energy[:, 1] = 1/2 qvel^T (qM qvel); energy is [B, 2] and may be NULL in a call for the sensors.  SENSORS evaluates the
+ * nsens sensors of sns -- nsens is the size of the model's table in EVERY call, also one without SENSORS: it enters the lanes per environment, so that the energies of
+ * the two kinds of call are the same bits -- ([nsens, 6] int32: sensor type (20 .. 25 jointlimitpos / vel / frc, tendonlimitpos / vel / frc, 43 e_potential, 44 e_kinetic), sensordata
+ * address, object id, the row of the object's limit in efc_J / efc_force or -1, datatype, the joint's type) and writes ONLY their slots of sensordata
+ * [B, nsensordata]; it reads qpos, qvel, ten_length, efc_J [B, nefc, nv] and efc_force [B, nefc]; an e_potential / e_kinetic row needs POS / VEL in the same call
+ * (0 without).  The definitions are in csrc/mjh_energy.h.  sns rows must address this model (the kernel does not check them).  No output may alias an input. */
+typedef struct mjhEnergyArgs {
+  int32_t flags, nsens;
+  int64_t B;
+  const void *qpos, *qvel, *xipos, *ten_length, *qM, *efc_J, *efc_force;
+  const void *gravity, *body_mass, *jnt_stiffness, *qpos_spring, *jnt_range, *jnt_margin, *tendon_stiffness, *tendon_lengthspring, *tendon_range, *tendon_margin;
+  const int32_t* sns;
+  const void* sns_cutoff;
+  void *energy, *sensordata;
+} mjhEnergyArgs;
+
+/* the energies and / or the joint / tendon limit and energy sensors of a finished forward pass (see mjhEnergyArgs) as ONE launch.  Runs on hip_stream without host
+ * synchronisation.  Returns 0 or a negative code; B == 0 is a no-op. */
+int mjh_energy(const mjhModel* m, const mjhEnergyArgs* args, void* hip_stream);
+
 /* Finite-difference transition Jacobians (MuJoCo's mjd_transitionFD), as two launches around an mjh_step of the caller's own.  State x = (qpos in
  * tangent space: nv, qvel: nv, act: na), ns = 2 nv + na; column c in [0, ns) nudges entry c of x, column ns + i nudges ctrl[i].  A call serves the
  * columns [col0, col0 + ncol) of all B environments.  Each column of an environment owns nside = (centered ? 2 : 1) environments ("slots") of a
@@ -667,7 +698,7 @@ int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsi
 int mjh_model_lds_bytes(const mjhModel* m, int arena);
 
 /* measurement aid used by bench.py for the per-kernel roofline: while enabled, every kernel launch of mjh_step / mjh_forward is
- * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_postconstraint and mjh_contact_sensors too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
+ * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_postconstraint, mjh_contact_sensors and mjh_energy too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
  * the elapsed milliseconds and the kernel id (MJH_KERNEL_*).  Returns the number of launches (<= max) or a negative code. */
 int mjh_debug_phase_timing(int enable);
 int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
@@ -687,7 +718,8 @@ void mjh_debug_set_stamps(void* dev_ptr);
  * read and written (an upper bound: the caller's Data may lack some), and one slot's qpos, qvel, act and sensordata read, with [1] = one column of A and C.  MJH_KERNEL_FD_VJP: per (environment, column), one slot's and the nominal
  * qpos, qvel, act and sensordata (an upper bound: a one-sided column reads the nominal, a centered state column its two slots) and the cotangent, with
  * [1] = one entry of gx / gu; MJH_KERNEL_FD_TANGENT: per environment, qpos and a cotangent of at most nq entries read, one written.  MJH_KERNEL_POSTCON (an
- * mjh_postconstraint call with all three flags): per environment, every input leaf of mjhPostconArgs once, from the leaf extents, and the six outputs.  Returns 0, or -2 when this model's step does not launch that kernel. */
+ * mjh_postconstraint call with all three flags): per environment, every input leaf of mjhPostconArgs once, from the leaf extents, and the six outputs.  MJH_KERNEL_ENERGY
+ * (an mjh_energy call with MJH_ENERGY_POS | MJH_ENERGY_VEL): per environment, qpos, qvel, xipos, ten_length and qM once, the two energies written.  Returns 0, or -2 when this model's step does not launch that kernel. */
 int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes);
 
 /* last error message of the calling thread ("" if none) */

@@ -12,6 +12,7 @@
 #include "mjh_fd.h"
 #include "mjh_postcon.h"
 #include "mjh_contact_sensors.h"
+#include "mjh_energy.h"
 #include "mjh_instances.h"
 
 #define MJH_CAT_(a, b) a##b
@@ -48,4 +49,7 @@ template __global__ void mjh_postcon_kernel<MJH_INST_REAL>(PostconArgs<MJH_INST_
 #endif
 #if MJH_INST_GROUP == 25
 template __global__ void mjh_consens_kernel<MJH_INST_REAL>(ConSensArgs<MJH_INST_REAL>);
+#endif
+#if MJH_INST_GROUP == 26
+template __global__ void mjh_energy_kernel<MJH_INST_REAL>(EnergyArgs<MJH_INST_REAL>);
 #endif

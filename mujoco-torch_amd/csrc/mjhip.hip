@@ -24,6 +24,7 @@
 #include "mjh_fd.h"
 #include "mjh_postcon.h"
 #include "mjh_contact_sensors.h"
+#include "mjh_energy.h"
 #include "mjh_instances.h"
 
 // the kernels are compiled in their own translation units (mjh_inst.hip, one per build group): this file is the host side only
@@ -60,6 +61,8 @@ extern template __global__ void mjh_postcon_kernel<double>(PostconArgs<double>);
 extern template __global__ void mjh_postcon_kernel<float>(PostconArgs<float>);
 extern template __global__ void mjh_consens_kernel<double>(ConSensArgs<double>);  // (build group 25)
 extern template __global__ void mjh_consens_kernel<float>(ConSensArgs<float>);
+extern template __global__ void mjh_energy_kernel<double>(EnergyArgs<double>);  // (build group 26)
+extern template __global__ void mjh_energy_kernel<float>(EnergyArgs<float>);
 #undef X_
 #undef S_
 #undef C_
@@ -885,6 +888,7 @@ int grant_lds(const mjhModel* m) {
   HIP_TRY(allow_lds(&mjh_inverse_kernel<REAL>, kLdsWg));  // (the inverse tail's LDS_BUDGET plus the rounding of lds_env)
   if (m->pc_envs > 0) HIP_TRY(allow_lds(&mjh_postcon_kernel<REAL>, std::max(kLdsWg, m->pc_envs * m->pc_lds_env * (int)sizeof(REAL))));
   if (m->cs_ok) HIP_TRY(allow_lds(&mjh_consens_kernel<REAL>, std::max(kLdsWg, m->cs_lds_env * (int)sizeof(REAL))));
+  HIP_TRY(allow_lds(&mjh_energy_kernel<REAL>, kLdsWg));  // (run_energy's LDS_BUDGET plus the rounding of lds_env)
   return 0;
 }
 
@@ -1561,6 +1565,62 @@ int run_consens(const mjhModel* m, const DevModel<REAL>& M, const mjhContactSens
   return 0;
 }
 
+// the energies and the joint / tendon limit and energy sensors of a finished forward pass (mjh_energy.h), one launch
+template <typename REAL>
+int run_energy(const mjhModel* m, const DevModel<REAL>& M, const mjhEnergyArgs* x, void* stream) {
+  const int f = x->flags;
+  if (f <= 0 || f > (MJH_ENERGY_POS | MJH_ENERGY_VEL | MJH_ENERGY_SENSORS)) return fail(-22, "energy: unknown flags");
+  if (x->B < 0 || x->nsens < 0) return fail(-22, "energy: B and nsens must be >= 0");
+  if (x->B == 0) return 0;
+  const bool pos = f & MJH_ENERGY_POS, vel = f & MJH_ENERGY_VEL, sns = (f & MJH_ENERGY_SENSORS) && x->nsens > 0 && M.nsensordata > 0;
+  if (!(f & MJH_ENERGY_SENSORS) && !x->energy) return fail(-22, "energy: null pointer (energy)");
+  if (!x->energy && !sns) return 0;
+  const bool springs = !(M.disableflags & (DSBL_SPRING | DSBL_DAMPER));
+  if (pos && (!x->gravity || !x->body_mass || !x->xipos || (springs && M.njnt > 0 && (!x->qpos || !x->jnt_stiffness || !x->qpos_spring)) ||
+              (springs && M.ntendon > 0 && (!x->ten_length || !x->tendon_stiffness || !x->tendon_lengthspring))))
+    return fail(-22, "energy: null pointer (potential leaves)");
+  if (vel && M.nv > 0 && (!x->qvel || !x->qM)) return fail(-22, "energy: null pointer (kinetic leaves)");
+  if (sns && (!x->sns || !x->sns_cutoff || !x->sensordata || (M.nq > 0 && !x->qpos) || (M.nv > 0 && !x->qvel) || (M.njnt > 0 && (!x->jnt_range || !x->jnt_margin)) ||
+              (M.ntendon > 0 && (!x->ten_length || !x->tendon_range || !x->tendon_margin)) || (M.nefc > 0 && M.nv > 0 && (!x->efc_J || !x->efc_force))))
+    return fail(-22, "energy: null pointer (sensor leaves)");
+  EnergyArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+#define P_(n) a.n = reinterpret_cast<const REAL*>(x->n);
+  P_(qpos) P_(qvel) P_(xipos) P_(ten_length) P_(qM) P_(efc_J) P_(efc_force) P_(gravity) P_(body_mass) P_(jnt_stiffness) P_(qpos_spring) P_(jnt_range) P_(jnt_margin)
+  P_(tendon_stiffness) P_(tendon_lengthspring) P_(tendon_range) P_(tendon_margin) P_(sns_cutoff)
+#undef P_
+  a.jnt_type = M.jnt_type; a.jnt_qposadr = M.jnt_qposadr; a.sns = x->sns;
+  a.energy = reinterpret_cast<REAL*>(x->energy); a.sensordata = reinterpret_cast<REAL*>(x->sensordata);
+  a.nq = M.nq; a.nv = M.nv; a.nbody = M.nbody; a.njnt = M.njnt; a.ntendon = M.ntendon; a.nefc = M.nefc; a.nsensordata = M.nsensordata;
+  a.nsens = sns ? x->nsens : 0;
+  a.flags = (pos ? MJH_ENERGY_POS : 0) | (vel ? MJH_ENERGY_VEL : 0) | (sns ? MJH_ENERGY_SENSORS : 0);
+  a.gravity_on = !(M.disableflags & DSBL_GRAVITY);
+  a.spring_on = springs;
+  // lanes, environments per workgroup and the chunk of qM rows follow from the model and the size of its sensor table alone (nsens is that size in EVERY call, with
+  // or without MJH_ENERGY_SENSORS, so the energies of the two kinds of call are the same bits): LDS_BUDGET bytes per workgroup shared by its environments, an
+  // environment's share holding qvel, the lanes' partial sums, the two results and the chunk
+  constexpr int LDS_BUDGET = 52 * 1024;  // three workgroups per CU (160 KB)
+  const int nv = M.nv, widest = std::max(std::max(M.nbody, nv), x->nsens);
+  a.lanes = widest <= 16 ? 16 : (widest <= 32 ? 32 : 64);
+  a.envs = MJH_ENERGY_WG / a.lanes;
+  const int reals = LDS_BUDGET / a.envs / (int)sizeof(REAL), fixed = ((nv + 3) & ~3) + 2 * a.lanes + 4;
+  int chunk = (reals - fixed) / std::max(nv, 1);
+  if (chunk > nv) chunk = std::max(nv, 1);
+  if (chunk < 1) return fail(-12, "energy: nv too large for the LDS chunk of one environment");
+  a.chunk = chunk;
+  a.lds_env = (fixed + chunk * nv + 3) & ~3;
+  const size_t lds = (size_t)a.envs * a.lds_env * sizeof(REAL);
+  hipStream_t s = (hipStream_t)stream;
+  timing_begin(s);  // (behind the last refusal)
+  if (const int rc = launch_cut(x->B, a.envs, [&](int64_t first, int64_t n, unsigned grid) {
+        a.env_begin = first; a.env_count = n;
+        hipLaunchKernelGGL((mjh_energy_kernel<REAL>), dim3(grid), dim3(a.envs * a.lanes), lds, s, a);
+      }))
+    return rc;
+  timing_mark(s, MJH_KERNEL_ENERGY);
+  return 0;
+}
+
 // ---- finite-difference transition Jacobians (mjh_fd.h): the launches on either side of the caller's mjh_step over the perturbed environments ----
 
 // 4-byte words per environment of every mjhData slot, in struct order: reals, int32, int64, then the trailing input-only leaves
@@ -1783,6 +1843,11 @@ int mjh_contact_sensors(const mjhModel* m, const mjhContactSensorArgs* args, voi
   return m->dtype == MJH_F64 ? run_consens<double>(m, m->m64, args, stream) : run_consens<float>(m, m->m32, args, stream);
 }
 
+int mjh_energy(const mjhModel* m, const mjhEnergyArgs* args, void* stream) {
+  if (!m || !args) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_energy<double>(m, m->m64, args, stream) : run_energy<float>(m, m->m32, args, stream);
+}
+
 int mjh_fd_perturb(const mjhModel* m, const mjhData* in, mjhData* scratch, int64_t B, int col0, int ncol, double eps, int centered, void* stream) {
   if (!m || !in || !scratch) return fail(-22, "null argument");
   return m->dtype == MJH_F64 ? run_fd_perturb<double>(m, m->m64, in, scratch, B, col0, ncol, eps, centered, stream)
@@ -1946,6 +2011,12 @@ static int kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes, b
     // qvel qacc cdof cdof_dot | cvel cinert xipos ximat subtree_com xfrc_applied | efc_force | contact pos frame friction | dim, geom, efc_address | sites, sensordata
     read_write_bytes[0] = (14 * nv + (6 + 10 + 3 + 9 + 3 + 6) * nb + nefc + 17 * ncon + 12 * ns + nsd) * R + ncon * (4 + 16 + 8);
     read_write_bytes[1] = (24 * nb + nsd) * R;
+    return 0;
+  }
+  if (kernel == MJH_KERNEL_ENERGY) {  // both energies (mjh_energy, MJH_ENERGY_POS | MJH_ENERGY_VEL): qpos, qvel, xipos, ten_length and qM once, two reals out
+    const int64_t R = f64 ? 8 : 4, nq = f64 ? m->m64.nq : m->m32.nq, nv = f64 ? m->m64.nv : m->m32.nv, nb = f64 ? m->m64.nbody : m->m32.nbody, nt = f64 ? m->m64.ntendon : m->m32.ntendon;
+    read_write_bytes[0] = (nq + nv + 3 * nb + nt + nv * nv) * R;
+    read_write_bytes[1] = 2 * R;
     return 0;
   }
   if (kernel == MJH_KERNEL_INVERSE) {  // the inverse-dynamics tail (mjh_inverse): efc_J and qM once, efc_D / efc_aref, qacc, qfrc_bias / passive in; efc_force, qfrc_constraint, qfrc_inverse out.

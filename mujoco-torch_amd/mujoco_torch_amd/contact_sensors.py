@@ -14,7 +14,8 @@ for bit -- with, in addition, the slots of the touch, framelinacc and frameangac
 output).  A touch sensor sums the normal forces of the contacts of its site's body whose ray from the contact point along the normal, pointing out of that body,
 meets the site's shape (sphere, capsule, ellipsoid, cylinder or box; ``Model.site_size`` is read at each call, so value edits take effect).  framelinacc / frameangacc are in the world
 frame; a reference frame (``reftype`` / ``refname``) on these two types is ignored, as MuJoCo ignores it.  With ``DisableBit.SENSOR``, or a model without
-these sensors, the result is ``fwd_postconstraint``'s.
+these sensors, the result is ``fwd_postconstraint``'s.  ``all_sensors=True`` also writes the slots of the joint / tendon limit sensors and the energy sensors
+(jointlimitpos / vel / frc, tendonlimitpos / vel / frc, e_potential, e_kinetic; ``energy.py``) by one more launch; every other slot is as without it.
 
 Every leading dimension of a leaf is the batch (S); the input is never written and every other leaf of the result aliases it.  The calls run on the caller's
 current stream.  ``torch.vmap`` / ``torch.compile``: there is no operator for these functions; they raise ``NotImplementedError``.
@@ -185,15 +186,30 @@ def _refuse_zones(name, m):
                                       f"{' / '.join(_ZONES.values())} site")
 
 
-def sensor_postconstraint(m, d, qvel=None):
+def sensor_postconstraint(m, d, qvel=None, *, all_sensors: bool = False):
     """``fwd_postconstraint(m, d, qvel, sensors=True)`` -- the five leaves and the ``sensordata`` slots it writes or copies, bit for bit -- plus the slots of the
     touch, framelinacc and frameangacc sensors, evaluated from the pass's contact forces and the fresh ``cacc`` by one more launch.  ``qvel``: as for
-    ``rne_postconstraint``.  A reference frame on framelinacc / frameangacc is ignored, as MuJoCo ignores it."""
-    from .postconstraint import RNE, SENSORS as PC_SENSORS, SUBTREE, _run
+    ``rne_postconstraint``.  A reference frame on framelinacc / frameangacc is ignored, as MuJoCo ignores it.
 
+    ``all_sensors=True``: the same ``Data`` with, in addition, the slots of the jointlimitpos / vel / frc, tendonlimitpos / vel / frc, e_potential and e_kinetic
+    sensors written (``energy.py``: one more launch; ``qvel`` serves the limit velocities and the kinetic energy too)."""
     name = "sensor_postconstraint"
     _refuse_tracing(name, d.qpos, qvel)
     _refuse_zones(name, m)
+    if not all_sensors:
+        return _sensor_postconstraint(name, m, d, qvel)
+    from .energy import plan_sensors, write_sensors
+
+    p = plan_sensors(name, m, d, qvel)  # (checked before the first launch: a refused call launches nothing)
+    out = _sensor_postconstraint(name, m, d, qvel)
+    if p is not None:
+        write_sensors(name, m, p, out.sensordata)  # (fwd_postconstraint's own fresh sensordata)
+    return out
+
+
+def _sensor_postconstraint(name, m, d, qvel):
+    from .postconstraint import RNE, SENSORS as PC_SENSORS, SUBTREE, _run
+
     rows = m.tables.contact_sensors["rows"]
     nsd = int(getattr(m, "nsensordata", 0) or 0)
     extra, tails = {}, {}

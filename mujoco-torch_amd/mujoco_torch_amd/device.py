@@ -254,6 +254,46 @@ def _contact_sensor_tables(m) -> dict:
     return out
 
 
+ENERGY_SENSOR_COLUMNS = ("type", "adr", "objid", "efcrow", "datatype", "jnttype")
+_LIMIT_SENSORS = {int(_ST.JOINTLIMITPOS): "jnt", int(_ST.JOINTLIMITVEL): "jnt", int(_ST.JOINTLIMITFRC): "jnt",
+                  int(_ST.TENDONLIMITPOS): "tendon", int(_ST.TENDONLIMITVEL): "tendon", int(_ST.TENDONLIMITFRC): "tendon"}
+
+
+def _energy_sensor_tables(m, T) -> dict:
+    """The joint / tendon limit sensors and the energy sensors (energy.py, csrc/mjh_energy.h), one row per sensor in sensor order: type, adr, object id, the row of
+    the object's limit in efc_J / efc_force (-1: the object has no row -- not limited, or limits / constraints disabled), datatype, the joint's type (-1 elsewhere);
+    ``index`` is each row's sensor (its cutoff is read from the caller's Model at each call).  The rows of a pass: equality, frictionloss, ball limits, slide / hinge
+    limits, tendon limits, contacts (the constraint stage of csrc/mjh_kernels.h).  No pass evaluates these sensors (``tables.sensors`` does not list them):
+    ``sensor_postconstraint(all_sensors=True)`` does."""
+    ns = int(getattr(m, "nsensor", 0) or 0)
+    out = dict(rows=np.zeros((0, len(ENERGY_SENSOR_COLUMNS)), dtype=np.int32), index=np.zeros(0, dtype=np.int64))
+    if ns == 0 or (int(m.opt.disableflags) & DisableBit.SENSOR):
+        return out
+    A = lambda name: np.asarray(getattr(m, name))
+    ne, nf, _, _, _ = T.constraint_sizes
+    first = {"ball": ne + nf, "jnt": ne + nf + len(T.lim_ball_jnt), "tendon": ne + nf + len(T.lim_ball_jnt) + len(T.lim_jnt)}
+    where = {"ball": T.lim_ball_jnt.tolist(), "jnt": T.lim_jnt.tolist(), "tendon": list(T.tendon["lim"])}
+    rows, index = [], []
+    for i in range(ns):
+        t, oid = int(A("sensor_type")[i]), int(A("sensor_objid")[i])
+        efcrow, jt = -1, -1
+        if t in _LIMIT_SENSORS:
+            kind = _LIMIT_SENSORS[t]
+            if kind == "jnt":
+                jt = int(A("jnt_type")[oid])
+                if jt == int(JointType.BALL):
+                    kind = "ball"
+            if oid in where[kind]:
+                efcrow = first[kind] + where[kind].index(oid)
+        elif t not in (int(_ST.E_POTENTIAL), int(_ST.E_KINETIC)):
+            continue
+        rows.append([t, int(A("sensor_adr")[i]), oid, efcrow, int(A("sensor_datatype")[i]), jt])
+        index.append(i)
+    if rows:
+        out = dict(rows=np.array(rows, dtype=np.int32), index=np.array(index, dtype=np.int64))
+    return out
+
+
 class StaticTables:
     """Everything about a model that is constant across steps and environments.
 
@@ -371,6 +411,7 @@ def _build_tables(m, dtype) -> StaticTables:
     T.tendon = _tendon_tables(m, flags)
     T.nlt = len(T.tendon["lim"])  # tendon limit rows
     assert len(lim) + len(lim_ball) + T.nlt == nl, (len(lim), len(lim_ball), nl)
+    T.energy_sensors = _energy_sensor_tables(m, T)  # joint / tendon limit and energy sensors: evaluated by sensor_postconstraint(all_sensors=True), never by a pass
     T.ray = ray_tables(m)  # ray casting (ray.py): what its candidate tables are built from
     T.render = render_tables(m)  # rendering (render.py): materials, cameras, lights
     return T

@@ -1614,7 +1614,7 @@ class _Compiler:
                 jt = int(m.jnt_type[oi])
                 if sn.tag in ("ballquat", "ballangvel") and jt != int(JointType.BALL):
                     raise ValueError(f"sensor <{sn.tag}>: joint {self._t(sn).get('joint')!r} must be a ball joint")
-                if sn.tag in ("jointpos", "jointvel", "jointlimitpos", "jointlimitvel", "jointlimitfrc") and jt not in (int(JointType.SLIDE), int(JointType.HINGE)):
+                if sn.tag in ("jointpos", "jointvel") and jt not in (int(JointType.SLIDE), int(JointType.HINGE)):
                     raise ValueError(f"sensor <{sn.tag}>: joint {self._t(sn).get('joint')!r} must be a slide or hinge joint")
             elif attach == "tendon":
                 ot, oi = int(ObjType.TENDON), lookup(sn, "tendon", getattr(m, "names_tendon", []), "tendon")

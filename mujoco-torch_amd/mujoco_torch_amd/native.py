@@ -259,6 +259,14 @@ class ContactSensorArgs(ctypes.Structure):
         "subtree_com", "xipos", "xpos", "geom_xpos", "cam_xpos", "site_size", "sns", "sns_cutoff", "force", "sensordata")]
 
 
+class EnergyArgs(ctypes.Structure):
+    """include/mjhip.h mjhEnergyArgs: one mjh_energy call (device pointers)."""
+
+    _fields_ = [("flags", ctypes.c_int32), ("nsens", ctypes.c_int32), ("B", ctypes.c_int64)] + [(n, ctypes.c_void_p) for n in (
+        "qpos", "qvel", "xipos", "ten_length", "qM", "efc_J", "efc_force", "gravity", "body_mass", "jnt_stiffness", "qpos_spring", "jnt_range", "jnt_margin",
+        "tendon_stiffness", "tendon_lengthspring", "tendon_range", "tendon_margin", "sns", "sns_cutoff", "energy", "sensordata")]
+
+
 def load_library(path: str | None = None):
     """Loads libmjhip.so (once). Raises if it has not been built: no fallback path exists."""
     global _lib
@@ -299,6 +307,9 @@ def load_library(path: str | None = None):
     if hasattr(lib, "mjh_contact_sensors"):  # (likewise a build from before contact_force / sensor_postconstraint)
         lib.mjh_contact_sensors.argtypes = [ctypes.c_void_p, ctypes.POINTER(ContactSensorArgs), ctypes.c_void_p]
         lib.mjh_contact_sensors.restype = ctypes.c_int
+    if hasattr(lib, "mjh_energy"):  # (likewise a build from before energy / the limit and energy sensors)
+        lib.mjh_energy.argtypes = [ctypes.c_void_p, ctypes.POINTER(EnergyArgs), ctypes.c_void_p]
+        lib.mjh_energy.restype = ctypes.c_int
     lib.mjh_reset_where.argtypes = [ctypes.c_void_p, ctypes.POINTER(DataPtrs), ctypes.POINTER(DataPtrs), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
     lib.mjh_reset_where.restype = ctypes.c_int
     lib.mjh_debug_phase_timing.argtypes = [ctypes.c_int]
