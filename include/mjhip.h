@@ -17,6 +17,7 @@
  *   mjh_postconstraint <- MuJoCo's mj_rnePostConstraint / mj_subtreeVel (MJX smooth.rne_postconstraint / subtree_vel; the reference has no counterpart)
  *   mjh_contact_sensors <- MuJoCo's mj_contactForce (MJX support.contact_force) and its touch / framelinacc / frameangacc sensors (the reference evaluates none of them)
  *   mjh_energy         <- MuJoCo's mj_energyPos / mj_energyVel and its joint / tendon limit and energy sensors (the reference evaluates none of them)
+ *   mjh_integrate      <- derivative.deriv_smooth_vel, forward._implicit (implicitfast), forward._euler and their _advance, on a finished pass (_src/derivative.py:22-68, forward.py:255-328, 404-416)
  *
  * Conventions
  *  - every Data leaf is batch-major contiguous: shape [B, ...] exactly as
@@ -42,7 +43,7 @@
 extern "C" {
 #endif
 
-#define MJH_ABI_VERSION 18
+#define MJH_ABI_VERSION 19
 
 /* ---- dtype / flags ------------------------------------------------------------------- */
 #define MJH_F64 0
@@ -97,6 +98,7 @@ extern "C" {
 #define MJH_KERNEL_POSTCON 32    /* mjh_postconstraint: cacc, cfrc_int, cfrc_ext, subtree_linvel, subtree_angmom       */
 #define MJH_KERNEL_CONSENS 33    /* mjh_contact_sensors: contact forces, touch / framelinacc / frameangacc sensors     */
 #define MJH_KERNEL_ENERGY 34     /* mjh_energy: potential / kinetic energy, joint / tendon limit and energy sensors     */
+#define MJH_KERNEL_INTEGRATE 35  /* mjh_integrate: deriv_smooth_vel, the implicit (implicitfast) and Euler integrators   */
 
 /* pair-function ids of the static collision table (collision_driver.py:106-125) */
 #define MJH_FN_PLANE_SPHERE 0
@@ -638,6 +640,40 @@ typedef struct mjhEnergyArgs {
  * synchronisation.  Returns 0 or a negative code; B == 0 is a no-op. */
 int mjh_energy(const mjhModel* m, const mjhEnergyArgs* args, void* hip_stream);
 
+/* mjh_integrate flags: what one launch computes */
+#define MJH_INTEGRATE_QDERIV 1        /* build qDeriv = d(qfrc_smooth) / d(qvel): actuators, dof damping, tendon damping (derivative.py:22-68)        */
+#define MJH_INTEGRATE_IMPLICIT 2      /* with QDERIV: qacc = chol_solve(qM - h qDeriv, qfrc_smooth + qfrc_constraint) (forward.py:404-416)            */
+#define MJH_INTEGRATE_EULER 4         /* qacc = chol_solve(qM + h diag(dof_damping), qfrc_smooth + qfrc_constraint) (forward.py:313-328)              */
+#define MJH_INTEGRATE_STATE 8         /* advance: qpos_out, qvel_out, act_out, time_out (forward.py:255-310), with the qacc above or else the qacc leaf */
+#define MJH_INTEGRATE_WRITE_QDERIV 16 /* with QDERIV: qderiv_out [B, nv, nv], the full symmetric matrix                                               */
+#define MJH_INTEGRATE_WRITE_QACC 32   /* qacc_out [B, nv]: the acceleration the state is advanced with                                                */
+
+/* one mjh_integrate call.  Every pointer is device memory; the leaves are batch-major over B environments, reals are of the model's dtype.  The MODEL VALUES are
+ * arguments of the call (the caller's Model, not the blob): dof_damping [nv], tendon_damping [ntendon], gainprm [nu, gain_stride], biasprm [nu, bias_stride] (entry 2 of a
+ * row is read), dynprm [nu, dyn_stride] (entry 0), actrange [nu, 2], the step h and the disable flags (ACTUATION 1 << 11, DAMPER 1 << 6 are read).  The structure (gain /
+ * bias / dyn types, actadr, actlimited, jnt_type / qposadr / dofadr) is the compiled model's.  QDERIV reads ctrl [B, nu], act [B, na], actuator_moment [B, nu, nv], ten_J
+ * [B, ntendon, nv]; IMPLICIT / EULER read qM [B, nv, nv] (its lower triangle), qfrc_smooth and qfrc_constraint [B, nv]; a call with neither reads qacc [B, nv]; STATE reads
+ * qpos [B, nq], qvel [B, nv], act, act_dot [B, na], time [B].  The definitions, the factorisation rule (the reference's math.small_cholesky) and the order of every sum
+ * are in csrc/mjh_integrate.h.  No output may alias an input. */
+typedef struct mjhIntegrateArgs {
+  int32_t flags, disableflags;
+  int64_t B;
+  double h;
+  int32_t gain_stride, bias_stride, dyn_stride, reserved;
+  const void *qpos, *qvel, *act, *act_dot, *time, *ctrl, *qacc, *qM, *qfrc_smooth, *qfrc_constraint, *actuator_moment, *ten_J;
+  const void *dof_damping, *tendon_damping, *gainprm, *biasprm, *dynprm, *actrange;
+  void *qpos_out, *qvel_out, *act_out, *time_out, *qderiv_out, *qacc_out;
+} mjhIntegrateArgs;
+
+/* deriv_smooth_vel and / or one implicit or Euler integration step on a finished forward pass (see mjhIntegrateArgs) as ONE launch.  Runs on hip_stream without host
+ * synchronisation.  Returns 0 or a negative code (a model whose matrix does not fit the LDS of a workgroup is refused); B == 0 is a no-op. */
+int mjh_integrate(const mjhModel* m, const mjhIntegrateArgs* args, void* hip_stream);
+
+/* the launch plan mjh_integrate uses for a model of nv dofs, nu actuators and ntendon tendons in reals of real_bytes (4 / 8) bytes, a host computation (no device is
+ * touched): out = {lanes per environment, environments per workgroup, rows per LDS chunk, reals of LDS per environment}.  Returns 0, -12 when one environment does not
+ * fit a workgroup's LDS (mjh_integrate refuses such a model), -22 for a bad argument. */
+int mjh_integrate_plan(int nv, int nu, int ntendon, int real_bytes, int* lanes_envs_chunk_lds);
+
 /* Finite-difference transition Jacobians (MuJoCo's mjd_transitionFD), as two launches around an mjh_step of the caller's own.  State x = (qpos in
  * tangent space: nv, qvel: nv, act: na), ns = 2 nv + na; column c in [0, ns) nudges entry c of x, column ns + i nudges ctrl[i].  A call serves the
  * columns [col0, col0 + ncol) of all B environments.  Each column of an environment owns nside = (centered ? 2 : 1) environments ("slots") of a
@@ -698,7 +734,7 @@ int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsi
 int mjh_model_lds_bytes(const mjhModel* m, int arena);
 
 /* measurement aid used by bench.py for the per-kernel roofline: while enabled, every kernel launch of mjh_step / mjh_forward is
- * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_postconstraint, mjh_contact_sensors and mjh_energy too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
+ * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_postconstraint, mjh_contact_sensors, mjh_energy and mjh_integrate too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
  * the elapsed milliseconds and the kernel id (MJH_KERNEL_*).  Returns the number of launches (<= max) or a negative code. */
 int mjh_debug_phase_timing(int enable);
 int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
@@ -719,7 +755,8 @@ void mjh_debug_set_stamps(void* dev_ptr);
  * qpos, qvel, act and sensordata (an upper bound: a one-sided column reads the nominal, a centered state column its two slots) and the cotangent, with
  * [1] = one entry of gx / gu; MJH_KERNEL_FD_TANGENT: per environment, qpos and a cotangent of at most nq entries read, one written.  MJH_KERNEL_POSTCON (an
  * mjh_postconstraint call with all three flags): per environment, every input leaf of mjhPostconArgs once, from the leaf extents, and the six outputs.  MJH_KERNEL_ENERGY
- * (an mjh_energy call with MJH_ENERGY_POS | MJH_ENERGY_VEL): per environment, qpos, qvel, xipos, ten_length and qM once, the two energies written.  Returns 0, or -2 when this model's step does not launch that kernel. */
+ * (an mjh_energy call with MJH_ENERGY_POS | MJH_ENERGY_VEL): per environment, qpos, qvel, xipos, ten_length and qM once, the two energies written.  MJH_KERNEL_INTEGRATE
+ * (an mjh_integrate call for implicit: QDERIV | IMPLICIT | STATE): per environment, the leaves that call reads once (qM in full), qpos, qvel, act and time written.  Returns 0, or -2 when this model's step does not launch that kernel. */
 int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes);
 
 /* last error message of the calling thread ("" if none) */

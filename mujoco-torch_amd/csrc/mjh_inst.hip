@@ -13,6 +13,7 @@
 #include "mjh_postcon.h"
 #include "mjh_contact_sensors.h"
 #include "mjh_energy.h"
+#include "mjh_integrate.h"
 #include "mjh_instances.h"
 
 #define MJH_CAT_(a, b) a##b
@@ -52,4 +53,7 @@ template __global__ void mjh_consens_kernel<MJH_INST_REAL>(ConSensArgs<MJH_INST_
 #endif
 #if MJH_INST_GROUP == 26
 template __global__ void mjh_energy_kernel<MJH_INST_REAL>(EnergyArgs<MJH_INST_REAL>);
+#endif
+#if MJH_INST_GROUP == 27
+template __global__ void mjh_integrate_kernel<MJH_INST_REAL>(IntegrateArgs<MJH_INST_REAL>);
 #endif

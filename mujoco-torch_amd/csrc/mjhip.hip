@@ -25,6 +25,7 @@
 #include "mjh_postcon.h"
 #include "mjh_contact_sensors.h"
 #include "mjh_energy.h"
+#include "mjh_integrate.h"
 #include "mjh_instances.h"
 
 // the kernels are compiled in their own translation units (mjh_inst.hip, one per build group): this file is the host side only
@@ -63,6 +64,8 @@ extern template __global__ void mjh_consens_kernel<double>(ConSensArgs<double>);
 extern template __global__ void mjh_consens_kernel<float>(ConSensArgs<float>);
 extern template __global__ void mjh_energy_kernel<double>(EnergyArgs<double>);  // (build group 26)
 extern template __global__ void mjh_energy_kernel<float>(EnergyArgs<float>);
+extern template __global__ void mjh_integrate_kernel<double>(IntegrateArgs<double>);  // (build group 27)
+extern template __global__ void mjh_integrate_kernel<float>(IntegrateArgs<float>);
 #undef X_
 #undef S_
 #undef C_
@@ -889,6 +892,7 @@ int grant_lds(const mjhModel* m) {
   if (m->pc_envs > 0) HIP_TRY(allow_lds(&mjh_postcon_kernel<REAL>, std::max(kLdsWg, m->pc_envs * m->pc_lds_env * (int)sizeof(REAL))));
   if (m->cs_ok) HIP_TRY(allow_lds(&mjh_consens_kernel<REAL>, std::max(kLdsWg, m->cs_lds_env * (int)sizeof(REAL))));
   HIP_TRY(allow_lds(&mjh_energy_kernel<REAL>, kLdsWg));  // (run_energy's LDS_BUDGET plus the rounding of lds_env)
+  HIP_TRY(allow_lds(&mjh_integrate_kernel<REAL>, kLdsWg));  // (run_integrate never asks for more)
   return 0;
 }
 
@@ -1621,6 +1625,88 @@ int run_energy(const mjhModel* m, const DevModel<REAL>& M, const mjhEnergyArgs* 
   return 0;
 }
 
+// mjh_integrate's launch plan, from the model alone: lanes per environment, environments per workgroup, rows of nv reals per LDS chunk, reals of LDS per
+// environment.  An environment's LDS: the packed triangle, the right-hand side, the new qvel, vel_i (`fixed`) and chunk rows.  LDS_BUDGET bytes per workgroup are
+// shared by 256 / lanes environments, halved until one environment's share holds the fixed part, one row and the rounding of lds_env to a multiple of 4; a single
+// environment may take all of kLdsWg.  Returns 0, or -12 when one environment does not fit kLdsWg.
+static int integrate_plan(int nv, int nu, int nt, int real_bytes, int* out) {
+  constexpr int LDS_BUDGET = 52 * 1024;  // three workgroups per CU (160 KB)
+  const int lanes = nv <= 16 ? 16 : (nv <= 32 ? 32 : 64);
+  const int fixed = (((nv * (nv + 1)) / 2 + 3) & ~3) + 2 * ((nv + 3) & ~3) + ((nu + 3) & ~3), row = std::max(nv, 1);
+  const int most = std::max(std::max(nv, nu), std::max(nt, 1));  // rows worth holding at once
+  int envs = MJH_INTEGRATE_WG / lanes;
+  while (envs > 1 && LDS_BUDGET / envs / real_bytes - 4 < fixed + row) envs >>= 1;
+  const int reals = (envs > 1 ? LDS_BUDGET / envs : kLdsWg) / real_bytes - 4;
+  int chunk = (reals - fixed) / row;
+  if (chunk > most) chunk = most;
+  if (chunk < 1) return -12;
+  const int lds_env = (fixed + chunk * row + 3) & ~3;
+  if ((int64_t)envs * lds_env * real_bytes > (int64_t)kLdsWg) return -12;
+  out[0] = lanes; out[1] = envs; out[2] = chunk; out[3] = lds_env;
+  return 0;
+}
+
+// deriv_smooth_vel and the implicit / Euler integrators on a finished forward pass (mjh_integrate.h), one launch
+template <typename REAL>
+int run_integrate(const mjhModel* m, const DevModel<REAL>& M, const mjhIntegrateArgs* x, void* stream) {
+  const int f = x->flags;
+  constexpr int ALL = MJH_INTEGRATE_QDERIV | MJH_INTEGRATE_IMPLICIT | MJH_INTEGRATE_EULER | MJH_INTEGRATE_STATE | MJH_INTEGRATE_WRITE_QDERIV | MJH_INTEGRATE_WRITE_QACC;
+  if (f <= 0 || f > ALL) return fail(-22, "integrate: unknown flags");
+  const bool build = f & MJH_INTEGRATE_QDERIV, implicit = f & MJH_INTEGRATE_IMPLICIT, euler = f & MJH_INTEGRATE_EULER, state = f & MJH_INTEGRATE_STATE;
+  const bool wqd = f & MJH_INTEGRATE_WRITE_QDERIV, wqa = f & MJH_INTEGRATE_WRITE_QACC;
+  if ((implicit && !build) || (implicit && euler) || (wqd && !build)) return fail(-22, "integrate: IMPLICIT and WRITE_QDERIV need QDERIV, IMPLICIT excludes EULER");
+  if (!state && !wqd && !wqa) return fail(-22, "integrate: the flags ask for no output");
+  if (x->B < 0) return fail(-22, "integrate: B must be >= 0");
+  if (x->B == 0) return 0;
+  if (!(x->h == x->h)) return fail(-22, "integrate: h is not a number");
+  const int nv = M.nv, nu = M.nu, na = M.na, nt = M.ntendon;
+  const bool actuation = !(x->disableflags & DSBL_ACTUATION) && nu > 0, damper = !(x->disableflags & DSBL_DAMPER);
+  const bool solve = (implicit || euler) && nv > 0;
+  if (build && nv > 0) {
+    if (actuation && (!x->actuator_moment || !x->ctrl || !x->gainprm || !x->biasprm || (na > 0 && !x->act))) return fail(-22, "integrate: null pointer (actuator leaves)");
+    if (actuation && (x->gain_stride < 3 || x->bias_stride < 3)) return fail(-22, "integrate: gainprm / biasprm rows need at least 3 entries");
+    if (damper && !x->dof_damping) return fail(-22, "integrate: null pointer (dof_damping)");
+    if (nt > 0 && (!x->ten_J || !x->tendon_damping)) return fail(-22, "integrate: null pointer (tendon leaves)");
+    if (wqd && !x->qderiv_out) return fail(-22, "integrate: null pointer (qderiv_out)");
+  }
+  if (solve && (!x->qM || !x->qfrc_smooth || !x->qfrc_constraint || (euler && !implicit && !x->dof_damping))) return fail(-22, "integrate: null pointer (qM, qfrc_smooth, qfrc_constraint, dof_damping)");
+  if (!solve && (state || wqa) && nv > 0 && !x->qacc) return fail(-22, "integrate: null pointer (qacc)");
+  if (wqa && nv > 0 && !x->qacc_out) return fail(-22, "integrate: null pointer (qacc_out)");
+  if (state) {
+    if ((M.nq > 0 && (!x->qpos || !x->qpos_out)) || (nv > 0 && (!x->qvel || !x->qvel_out)) || !x->time || !x->time_out) return fail(-22, "integrate: null pointer (state leaves)");
+    if (na > 0 && (!x->act || !x->act_dot || !x->act_out || !x->dynprm || !x->actrange || x->dyn_stride < 1)) return fail(-22, "integrate: null pointer (activation leaves)");
+  }
+  IntegrateArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+#define P_(n) a.n = reinterpret_cast<const REAL*>(x->n);
+  P_(qpos) P_(qvel) P_(act) P_(act_dot) P_(time) P_(ctrl) P_(qacc) P_(qM) P_(qfrc_smooth) P_(qfrc_constraint) P_(actuator_moment) P_(ten_J)
+  P_(dof_damping) P_(tendon_damping) P_(gainprm) P_(biasprm) P_(dynprm) P_(actrange)
+#undef P_
+#define O_(n) a.n = reinterpret_cast<REAL*>(x->n);
+  O_(qpos_out) O_(qvel_out) O_(act_out) O_(time_out) O_(qderiv_out) O_(qacc_out)
+#undef O_
+  a.act_gaintype = M.act_gaintype; a.act_biastype = M.act_biastype; a.act_dyntype = M.act_dyntype; a.act_actadr = M.act_actadr; a.act_actlimited = M.act_actlimited;
+  a.jnt_type = M.jnt_type; a.jnt_qposadr = M.jnt_qposadr; a.jnt_dofadr = M.jnt_dofadr;
+  a.h = (REAL)x->h;
+  a.nq = M.nq; a.nv = nv; a.nu = nu; a.na = na; a.njnt = M.njnt; a.ntendon = nt;
+  a.gain_stride = x->gain_stride; a.bias_stride = x->bias_stride; a.dyn_stride = x->dyn_stride;
+  a.flags = f;
+  a.actuation_on = actuation; a.damper_on = damper;
+  int plan[4];
+  if (integrate_plan(nv, nu, nt, (int)sizeof(REAL), plan)) return fail(-12, "integrate: nv too large for the LDS of one workgroup");
+  a.lanes = plan[0]; a.envs = plan[1]; a.chunk = plan[2]; a.lds_env = plan[3];
+  const size_t lds = (size_t)a.envs * a.lds_env * sizeof(REAL);
+  hipStream_t s = (hipStream_t)stream;
+  timing_begin(s);  // (behind the last refusal)
+  if (const int rc = launch_cut(x->B, a.envs, [&](int64_t first, int64_t n, unsigned grid) {
+        a.env_begin = first; a.env_count = n;
+        hipLaunchKernelGGL((mjh_integrate_kernel<REAL>), dim3(grid), dim3(a.envs * a.lanes), lds, s, a);
+      }))
+    return rc;
+  timing_mark(s, MJH_KERNEL_INTEGRATE);
+  return 0;
+}
+
 // ---- finite-difference transition Jacobians (mjh_fd.h): the launches on either side of the caller's mjh_step over the perturbed environments ----
 
 // 4-byte words per environment of every mjhData slot, in struct order: reals, int32, int64, then the trailing input-only leaves
@@ -1848,6 +1934,16 @@ int mjh_energy(const mjhModel* m, const mjhEnergyArgs* args, void* stream) {
   return m->dtype == MJH_F64 ? run_energy<double>(m, m->m64, args, stream) : run_energy<float>(m, m->m32, args, stream);
 }
 
+int mjh_integrate(const mjhModel* m, const mjhIntegrateArgs* args, void* stream) {
+  if (!m || !args) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_integrate<double>(m, m->m64, args, stream) : run_integrate<float>(m, m->m32, args, stream);
+}
+
+int mjh_integrate_plan(int nv, int nu, int ntendon, int real_bytes, int* lanes_envs_chunk_lds) {
+  if (nv < 0 || nu < 0 || ntendon < 0 || (real_bytes != 4 && real_bytes != 8) || !lanes_envs_chunk_lds) return fail(-22, "integrate_plan: bad argument");
+  return integrate_plan(nv, nu, ntendon, real_bytes, lanes_envs_chunk_lds);
+}
+
 int mjh_fd_perturb(const mjhModel* m, const mjhData* in, mjhData* scratch, int64_t B, int col0, int ncol, double eps, int centered, void* stream) {
   if (!m || !in || !scratch) return fail(-22, "null argument");
   return m->dtype == MJH_F64 ? run_fd_perturb<double>(m, m->m64, in, scratch, B, col0, ncol, eps, centered, stream)
@@ -2017,6 +2113,13 @@ static int kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes, b
     const int64_t R = f64 ? 8 : 4, nq = f64 ? m->m64.nq : m->m32.nq, nv = f64 ? m->m64.nv : m->m32.nv, nb = f64 ? m->m64.nbody : m->m32.nbody, nt = f64 ? m->m64.ntendon : m->m32.ntendon;
     read_write_bytes[0] = (nq + nv + 3 * nb + nt + nv * nv) * R;
     read_write_bytes[1] = 2 * R;
+    return 0;
+  }
+  if (kernel == MJH_KERNEL_INTEGRATE) {  // an implicit step (mjh_integrate, QDERIV | IMPLICIT | STATE): the leaves it reads once (qM in full), the four state leaves out
+    const int64_t R = f64 ? 8 : 4, nq = f64 ? m->m64.nq : m->m32.nq, nv = f64 ? m->m64.nv : m->m32.nv, nu = f64 ? m->m64.nu : m->m32.nu, na = f64 ? m->m64.na : m->m32.na,
+                  nt = f64 ? m->m64.ntendon : m->m32.ntendon;
+    read_write_bytes[0] = (nq + 3 * nv + 2 * na + 1 + nu + nv * nv + nu * nv + nt * nv) * R;
+    read_write_bytes[1] = (nq + nv + na + 1) * R;
     return 0;
   }
   if (kernel == MJH_KERNEL_INVERSE) {  // the inverse-dynamics tail (mjh_inverse): efc_J and qM once, efc_D / efc_aref, qacc, qfrc_bias / passive in; efc_force, qfrc_constraint, qfrc_inverse out.

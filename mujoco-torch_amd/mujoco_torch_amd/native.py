@@ -267,6 +267,15 @@ class EnergyArgs(ctypes.Structure):
         "tendon_stiffness", "tendon_lengthspring", "tendon_range", "tendon_margin", "sns", "sns_cutoff", "energy", "sensordata")]
 
 
+class IntegrateArgs(ctypes.Structure):
+    """include/mjhip.h mjhIntegrateArgs: one mjh_integrate call (device pointers)."""
+
+    _fields_ = [("flags", ctypes.c_int32), ("disableflags", ctypes.c_int32), ("B", ctypes.c_int64), ("h", ctypes.c_double), ("gain_stride", ctypes.c_int32),
+                ("bias_stride", ctypes.c_int32), ("dyn_stride", ctypes.c_int32), ("reserved", ctypes.c_int32)] + [(n, ctypes.c_void_p) for n in (
+        "qpos", "qvel", "act", "act_dot", "time", "ctrl", "qacc", "qM", "qfrc_smooth", "qfrc_constraint", "actuator_moment", "ten_J", "dof_damping", "tendon_damping",
+        "gainprm", "biasprm", "dynprm", "actrange", "qpos_out", "qvel_out", "act_out", "time_out", "qderiv_out", "qacc_out")]
+
+
 def load_library(path: str | None = None):
     """Loads libmjhip.so (once). Raises if it has not been built: no fallback path exists."""
     global _lib
@@ -310,6 +319,12 @@ def load_library(path: str | None = None):
     if hasattr(lib, "mjh_energy"):  # (likewise a build from before energy / the limit and energy sensors)
         lib.mjh_energy.argtypes = [ctypes.c_void_p, ctypes.POINTER(EnergyArgs), ctypes.c_void_p]
         lib.mjh_energy.restype = ctypes.c_int
+    if hasattr(lib, "mjh_integrate"):  # (likewise a build from before deriv_smooth_vel / implicit / euler)
+        lib.mjh_integrate.argtypes = [ctypes.c_void_p, ctypes.POINTER(IntegrateArgs), ctypes.c_void_p]
+        lib.mjh_integrate.restype = ctypes.c_int
+    if hasattr(lib, "mjh_integrate_plan"):
+        lib.mjh_integrate_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        lib.mjh_integrate_plan.restype = ctypes.c_int
     lib.mjh_reset_where.argtypes = [ctypes.c_void_p, ctypes.POINTER(DataPtrs), ctypes.POINTER(DataPtrs), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
     lib.mjh_reset_where.restype = ctypes.c_int
     lib.mjh_debug_phase_timing.argtypes = [ctypes.c_int]
