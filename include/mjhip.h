@@ -17,6 +17,7 @@
  *   mjh_postconstraint <- MuJoCo's mj_rnePostConstraint / mj_subtreeVel (MJX smooth.rne_postconstraint / subtree_vel; the reference has no counterpart)
  *   mjh_contact_sensors <- MuJoCo's mj_contactForce (MJX support.contact_force) and its touch / framelinacc / frameangacc sensors (the reference evaluates none of them)
  *   mjh_energy         <- MuJoCo's mj_energyPos / mj_energyVel and its joint / tendon limit and energy sensors (the reference evaluates none of them)
+ *   mjh_jacobian       <- MuJoCo's mj_jacBody .. mj_jacGeom (as products), mj_jacDot, mj_jacSubtreeCom, mj_angmomMat (the reference has support.jac alone)
  *   mjh_integrate      <- derivative.deriv_smooth_vel, forward._implicit (implicitfast), forward._euler and their _advance, on a finished pass (_src/derivative.py:22-68, forward.py:255-328, 404-416)
  *
  * Conventions
@@ -43,7 +44,7 @@
 extern "C" {
 #endif
 
-#define MJH_ABI_VERSION 19
+#define MJH_ABI_VERSION 20
 
 /* ---- dtype / flags ------------------------------------------------------------------- */
 #define MJH_F64 0
@@ -99,6 +100,14 @@ extern "C" {
 #define MJH_KERNEL_CONSENS 33    /* mjh_contact_sensors: contact forces, touch / framelinacc / frameangacc sensors     */
 #define MJH_KERNEL_ENERGY 34     /* mjh_energy: potential / kinetic energy, joint / tendon limit and energy sensors     */
 #define MJH_KERNEL_INTEGRATE 35  /* mjh_integrate: deriv_smooth_vel, the implicit (implicitfast) and Euler integrators   */
+#define MJH_KERNEL_JACOBIAN_POINT 36       /* mjh_jacobian, matrix form (36 + op): MJH_JACOBIAN_POINT                   */
+#define MJH_KERNEL_JACOBIAN_DOT 37         /* ... MJH_JACOBIAN_DOT: the time derivative of a point Jacobian              */
+#define MJH_KERNEL_JACOBIAN_SUBTREE_COM 38 /* ... MJH_JACOBIAN_SUBTREE_COM: the Jacobian of a subtree's centre of mass  */
+#define MJH_KERNEL_JACOBIAN_ANGMOM 39      /* ... MJH_JACOBIAN_ANGMOM: the angular-momentum matrix of a subtree         */
+#define MJH_KERNEL_JACOBIAN_POINT_VEC 40   /* mjh_jacobian, product form (40 + op): the same four times a vector          */
+#define MJH_KERNEL_JACOBIAN_DOT_VEC 41
+#define MJH_KERNEL_JACOBIAN_SUBTREE_COM_VEC 42
+#define MJH_KERNEL_JACOBIAN_ANGMOM_VEC 43
 
 /* pair-function ids of the static collision table (collision_driver.py:106-125) */
 #define MJH_FN_PLANE_SPHERE 0
@@ -674,6 +683,41 @@ int mjh_integrate(const mjhModel* m, const mjhIntegrateArgs* args, void* hip_str
  * fit a workgroup's LDS (mjh_integrate refuses such a model), -22 for a bad argument. */
 int mjh_integrate_plan(int nv, int nu, int ntendon, int real_bytes, int* lanes_envs_chunk_lds);
 
+/* mjh_jacobian operations (mjhJacobianArgs.op); MJH_KERNEL_JACOBIAN_POINT + op (matrix form) or MJH_KERNEL_JACOBIAN_POINT_VEC + op (product form) is the kernel id
+ * the timing aid reports */
+#define MJH_JACOBIAN_POINT 0
+#define MJH_JACOBIAN_DOT 1
+#define MJH_JACOBIAN_SUBTREE_COM 2
+#define MJH_JACOBIAN_ANGMOM 3
+
+/* one mjh_jacobian call.  Every pointer is device memory holding reals of the model's dtype, batch-major over B environments; the leaves are a finished forward
+ * pass's: cdof / cdof_dot [B, nv, 6], cvel [B, nbody, 6], subtree_com / xipos [B, nbody, 3], ximat [B, nbody, 9].  The MODEL VALUES body_mass [nbody],
+ * body_subtreemass [nbody] and body_inertia [nbody, 3] are arguments of the call (the caller's Model, not the blob).  body_id: P body ids in [0, nbody)
+ * (body_stride 1) or one id for every query (0); the library does not validate them, nor that body_subtreemass[body] != 0.  point is addressed as in mjhSupportArgs.
+ * Per op, what is read and written (outputs environment-major, contiguous; the definitions and the order of every sum are in csrc/mjh_jacobian.h):
+ *   POINT        cdof, subtree_com, point                   -> out0 = jacp, out1 = jacr [B, P, nv, 3] (mjh_support's JAC)
+ *   DOT          the same, cdof_dot, cvel                   -> out0 = jacp_dot, out1 = jacr_dot [B, P, nv, 3]
+ *   SUBTREE_COM  cdof, subtree_com, xipos, body_mass, body_subtreemass            -> out0 [B, P, nv, 3]
+ *   ANGMOM       the same, ximat, body_inertia                                    -> out0 [B, P, nv, 3]
+ * vec != NULL ([B, nv]) selects the product form: out0 (and out1) are [B, P, 3] = sum_i matrix[i, :] vec[i] in ascending dof order, the matrix is not written.
+ * P >= 1 and P * nv * 3 must stay below 2^30.  No output may alias an input. */
+typedef struct mjhJacobianArgs {
+  int32_t op, P;
+  int64_t B;
+  const void *cdof, *cdof_dot, *cvel, *subtree_com, *xipos, *ximat;
+  const void *body_mass, *body_subtreemass, *body_inertia;
+  const int32_t* body_id;
+  int64_t body_stride;
+  const void* point;
+  int64_t point_env, point_q;
+  const void* vec;
+  void *out0, *out1;
+} mjhJacobianArgs;
+
+/* the Jacobian block on a finished forward pass (see mjhJacobianArgs).  Runs on hip_stream without host synchronisation.  Returns 0 or a negative code (-12: one
+ * environment's rows do not fit a workgroup's LDS in the product form); B == 0 is a no-op. */
+int mjh_jacobian(const mjhModel* m, const mjhJacobianArgs* args, void* hip_stream);
+
 /* Finite-difference transition Jacobians (MuJoCo's mjd_transitionFD), as two launches around an mjh_step of the caller's own.  State x = (qpos in
  * tangent space: nv, qvel: nv, act: na), ns = 2 nv + na; column c in [0, ns) nudges entry c of x, column ns + i nudges ctrl[i].  A call serves the
  * columns [col0, col0 + ncol) of all B environments.  Each column of an environment owns nside = (centered ? 2 : 1) environments ("slots") of a
@@ -734,7 +778,7 @@ int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsi
 int mjh_model_lds_bytes(const mjhModel* m, int arena);
 
 /* measurement aid used by bench.py for the per-kernel roofline: while enabled, every kernel launch of mjh_step / mjh_forward is
- * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_postconstraint, mjh_contact_sensors, mjh_energy and mjh_integrate too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
+ * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_postconstraint, mjh_contact_sensors, mjh_energy, mjh_integrate and mjh_jacobian too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
  * the elapsed milliseconds and the kernel id (MJH_KERNEL_*).  Returns the number of launches (<= max) or a negative code. */
 int mjh_debug_phase_timing(int enable);
 int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
@@ -756,7 +800,9 @@ void mjh_debug_set_stamps(void* dev_ptr);
  * [1] = one entry of gx / gu; MJH_KERNEL_FD_TANGENT: per environment, qpos and a cotangent of at most nq entries read, one written.  MJH_KERNEL_POSTCON (an
  * mjh_postconstraint call with all three flags): per environment, every input leaf of mjhPostconArgs once, from the leaf extents, and the six outputs.  MJH_KERNEL_ENERGY
  * (an mjh_energy call with MJH_ENERGY_POS | MJH_ENERGY_VEL): per environment, qpos, qvel, xipos, ten_length and qM once, the two energies written.  MJH_KERNEL_INTEGRATE
- * (an mjh_integrate call for implicit: QDERIV | IMPLICIT | STATE): per environment, the leaves that call reads once (qM in full), qpos, qvel, act and time written.  Returns 0, or -2 when this model's step does not launch that kernel. */
+ * (an mjh_integrate call for implicit: QDERIV | IMPLICIT | STATE): per environment, the leaves that call reads once (qM in full), qpos, qvel, act and time written.  MJH_KERNEL_JACOBIAN_* (an mjh_jacobian call): per environment
+ * for one query, the dof rows and the body rows the operation reads (DOT: cvel and cdof_dot too; the subtree operations: xipos, ximat for ANGMOM) and the matrices,
+ * or, for the *_VEC ids, vec and the 3-vectors.  Returns 0, or -2 when this model's step does not launch that kernel. */
 int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes);
 
 /* last error message of the calling thread ("" if none) */

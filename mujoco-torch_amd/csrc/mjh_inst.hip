@@ -14,6 +14,7 @@
 #include "mjh_contact_sensors.h"
 #include "mjh_energy.h"
 #include "mjh_integrate.h"
+#include "mjh_jacobian.h"
 #include "mjh_instances.h"
 
 #define MJH_CAT_(a, b) a##b
@@ -56,4 +57,8 @@ template __global__ void mjh_energy_kernel<MJH_INST_REAL>(EnergyArgs<MJH_INST_RE
 #endif
 #if MJH_INST_GROUP == 27
 template __global__ void mjh_integrate_kernel<MJH_INST_REAL>(IntegrateArgs<MJH_INST_REAL>);
+#endif
+#if MJH_INST_GROUP == 28
+template __global__ void mjh_jac_matrix_kernel<MJH_INST_REAL>(JacArgs<MJH_INST_REAL>);
+template __global__ void mjh_jac_product_kernel<MJH_INST_REAL>(JacArgs<MJH_INST_REAL>);
 #endif

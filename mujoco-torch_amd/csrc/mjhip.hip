@@ -25,6 +25,7 @@
 #include "mjh_postcon.h"
 #include "mjh_contact_sensors.h"
 #include "mjh_energy.h"
+#include "mjh_jacobian.h"
 #include "mjh_integrate.h"
 #include "mjh_instances.h"
 
@@ -64,6 +65,10 @@ extern template __global__ void mjh_consens_kernel<double>(ConSensArgs<double>);
 extern template __global__ void mjh_consens_kernel<float>(ConSensArgs<float>);
 extern template __global__ void mjh_energy_kernel<double>(EnergyArgs<double>);  // (build group 26)
 extern template __global__ void mjh_energy_kernel<float>(EnergyArgs<float>);
+extern template __global__ void mjh_jac_matrix_kernel<double>(JacArgs<double>);  // (build group 28)
+extern template __global__ void mjh_jac_matrix_kernel<float>(JacArgs<float>);
+extern template __global__ void mjh_jac_product_kernel<double>(JacArgs<double>);
+extern template __global__ void mjh_jac_product_kernel<float>(JacArgs<float>);
 extern template __global__ void mjh_integrate_kernel<double>(IntegrateArgs<double>);  // (build group 27)
 extern template __global__ void mjh_integrate_kernel<float>(IntegrateArgs<float>);
 #undef X_
@@ -1625,6 +1630,61 @@ int run_energy(const mjhModel* m, const DevModel<REAL>& M, const mjhEnergyArgs* 
   return 0;
 }
 
+// the Jacobian block on a finished forward pass (mjh_jacobian.h): matrices by one lane per element, products (vec given) by 16 lanes per environment
+template <typename REAL>
+int run_jacobian(const mjhModel* m, const DevModel<REAL>& M, const mjhJacobianArgs* x, void* stream) {
+  (void)m;
+  const int op = x->op, nv = M.nv;
+  if (op < MJH_JACOBIAN_POINT || op > MJH_JACOBIAN_ANGMOM) return fail(-22, "jacobian: unknown op");
+  if (x->B < 0) return fail(-22, "jacobian: B must be >= 0");
+  if (x->P < 1 || (int64_t)x->P * nv * 3 >= (1 << 30)) return fail(-22, "jacobian: bad query count P");
+  if (x->body_stride != 0 && x->body_stride != 1) return fail(-22, "jacobian: body_stride must be 0 or 1");
+  if (x->B == 0 || nv == 0) return 0;
+  const bool pt = op == MJH_JACOBIAN_POINT || op == MJH_JACOBIAN_DOT, product = x->vec != nullptr;
+  if (!x->out0 || (pt && !x->out1) || !x->cdof || !x->subtree_com || !x->body_id || (pt && !x->point) || (op == MJH_JACOBIAN_DOT && (!x->cdof_dot || !x->cvel)) ||
+      (!pt && (!x->xipos || !x->body_mass || !x->body_subtreemass)) || (op == MJH_JACOBIAN_ANGMOM && (!x->ximat || !x->body_inertia)))
+    return fail(-22, "jacobian: null pointer");
+  JacArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+#define P_(n) a.n = reinterpret_cast<const REAL*>(x->n);
+  P_(cdof) P_(cdof_dot) P_(cvel) P_(subtree_com) P_(xipos) P_(ximat) P_(body_mass) P_(body_subtreemass) P_(body_inertia) P_(point) P_(vec)
+#undef P_
+  a.body = x->body_id; a.body_stride = (int)x->body_stride;
+  a.body_dofmask = M.body_dofmask; a.body_rootid = M.body_rootid; a.body_subtree_end = M.body_subtree_end;
+  a.dof_bodyid = M.dof_bodyid; a.dof_jntid = M.dof_jntid; a.jnt_type = M.jnt_type; a.jnt_dofadr = M.jnt_dofadr;
+  a.out0 = reinterpret_cast<REAL*>(x->out0); a.out1 = reinterpret_cast<REAL*>(x->out1);
+  a.point_env = x->point_env; a.point_q = x->point_q;
+  a.op = op; a.nv = nv; a.nbody = M.nbody; a.mask_words = M.mask_words; a.P = x->P;
+  hipStream_t s = (hipStream_t)stream;
+  if (!product) {  // one lane per output element; a launch starts at (env_base, r_base) so that the lanes index in 32 bits
+    timing_begin(s);
+    const int64_t per_env = (int64_t)x->P * nv * 3;
+    if (const int rc = launch_cut(x->B * per_env, MJH_JAC_WG, [&](int64_t first, int64_t n, unsigned grid) {
+          a.env_base = first / per_env; a.r_base = (int)(first % per_env); a.count = (int)n;
+          hipLaunchKernelGGL((mjh_jac_matrix_kernel<REAL>), dim3(grid), dim3(MJH_JAC_WG), 0, s, a);
+        }))
+      return rc;
+    timing_mark(s, MJH_KERNEL_JACOBIAN_POINT + op);
+    return 0;
+  }
+  // the product form: an environment's LDS holds cdof, vec, the terms of one query and (DOT) cdof_dot; LDS_BUDGET bytes per workgroup are shared by at most 256 / 16 environments, halved
+  // until they fit; a single environment may take up to 64 KB (the limit a kernel has without a grant)
+  constexpr int LDS_BUDGET = 48 * 1024, LDS_MAX = 64 * 1024;
+  a.lds_env = 2 * ((6 * nv + 3) & ~3) + ((nv + 3) & ~3) + (op == MJH_JACOBIAN_DOT ? ((6 * nv + 3) & ~3) : 0);
+  a.envs = MJH_JAC_WG / MJH_JAC_LANES;
+  while (a.envs > 1 && (int64_t)a.envs * a.lds_env * (int64_t)sizeof(REAL) > LDS_BUDGET) a.envs >>= 1;
+  const size_t lds = (size_t)a.envs * a.lds_env * sizeof(REAL);
+  if (lds > (size_t)LDS_MAX) return fail(-12, "jacobian: nv too large for the LDS rows of one environment");
+  timing_begin(s);  // (behind the last refusal)
+  if (const int rc = launch_cut(x->B, a.envs, [&](int64_t first, int64_t n, unsigned grid) {
+        a.env_base = first; a.env_count = n;
+        hipLaunchKernelGGL((mjh_jac_product_kernel<REAL>), dim3(grid), dim3(a.envs * MJH_JAC_LANES), lds, s, a);
+      }))
+    return rc;
+  timing_mark(s, MJH_KERNEL_JACOBIAN_POINT_VEC + op);
+  return 0;
+}
+
 // mjh_integrate's launch plan, from the model alone: lanes per environment, environments per workgroup, rows of nv reals per LDS chunk, reals of LDS per
 // environment.  An environment's LDS: the packed triangle, the right-hand side, the new qvel, vel_i (`fixed`) and chunk rows.  LDS_BUDGET bytes per workgroup are
 // shared by 256 / lanes environments, halved until one environment's share holds the fixed part, one row and the rounding of lds_env to a multiple of 4; a single
@@ -1934,6 +1994,11 @@ int mjh_energy(const mjhModel* m, const mjhEnergyArgs* args, void* stream) {
   return m->dtype == MJH_F64 ? run_energy<double>(m, m->m64, args, stream) : run_energy<float>(m, m->m32, args, stream);
 }
 
+int mjh_jacobian(const mjhModel* m, const mjhJacobianArgs* args, void* stream) {
+  if (!m || !args) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_jacobian<double>(m, m->m64, args, stream) : run_jacobian<float>(m, m->m32, args, stream);
+}
+
 int mjh_integrate(const mjhModel* m, const mjhIntegrateArgs* args, void* stream) {
   if (!m || !args) return fail(-22, "null argument");
   return m->dtype == MJH_F64 ? run_integrate<double>(m, m->m64, args, stream) : run_integrate<float>(m, m->m32, args, stream);
@@ -2113,6 +2178,17 @@ static int kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes, b
     const int64_t R = f64 ? 8 : 4, nq = f64 ? m->m64.nq : m->m32.nq, nv = f64 ? m->m64.nv : m->m32.nv, nb = f64 ? m->m64.nbody : m->m32.nbody, nt = f64 ? m->m64.ntendon : m->m32.ntendon;
     read_write_bytes[0] = (nq + nv + 3 * nb + nt + nv * nv) * R;
     read_write_bytes[1] = 2 * R;
+    return 0;
+  }
+  if (kernel >= MJH_KERNEL_JACOBIAN_POINT && kernel <= MJH_KERNEL_JACOBIAN_ANGMOM_VEC) {  // mjh_jacobian, per environment for one query: see include/mjhip.h
+    const int64_t R = f64 ? 8 : 4, nv = f64 ? m->m64.nv : m->m32.nv, nb = f64 ? m->m64.nbody : m->m32.nbody;
+    if (nv == 0) return -2;
+    const bool vec = kernel >= MJH_KERNEL_JACOBIAN_POINT_VEC;
+    const int op = kernel - (vec ? MJH_KERNEL_JACOBIAN_POINT_VEC : MJH_KERNEL_JACOBIAN_POINT);
+    // POINT: cdof, the root's subtree_com, the point; DOT: cdof_dot and cvel too; SUBTREE_COM: cdof, subtree_com, xipos; ANGMOM: ximat too
+    const int64_t rd[4] = {6 * nv + 3 + 3, 12 * nv + 3 + 3 + 6 * nb, 6 * nv + 6 * nb, 6 * nv + 15 * nb}, wr[4] = {6 * nv, 6 * nv, 3 * nv, 3 * nv};
+    read_write_bytes[0] = (rd[op] + (vec ? nv : 0)) * R;
+    read_write_bytes[1] = (vec ? wr[op] / nv : wr[op]) * R;
     return 0;
   }
   if (kernel == MJH_KERNEL_INTEGRATE) {  // an implicit step (mjh_integrate, QDERIV | IMPLICIT | STATE): the leaves it reads once (qM in full), the four state leaves out

@@ -276,6 +276,15 @@ class IntegrateArgs(ctypes.Structure):
         "gainprm", "biasprm", "dynprm", "actrange", "qpos_out", "qvel_out", "act_out", "time_out", "qderiv_out", "qacc_out")]
 
 
+class JacobianArgs(ctypes.Structure):
+    """include/mjhip.h mjhJacobianArgs: one mjh_jacobian call (device pointers, element strides)."""
+
+    _fields_ = [("op", ctypes.c_int32), ("P", ctypes.c_int32), ("B", ctypes.c_int64)] + [(n, ctypes.c_void_p) for n in (
+        "cdof", "cdof_dot", "cvel", "subtree_com", "xipos", "ximat", "body_mass", "body_subtreemass", "body_inertia", "body_id")] + [
+        ("body_stride", ctypes.c_int64), ("point", ctypes.c_void_p), ("point_env", ctypes.c_int64), ("point_q", ctypes.c_int64), ("vec", ctypes.c_void_p),
+        ("out0", ctypes.c_void_p), ("out1", ctypes.c_void_p)]
+
+
 def load_library(path: str | None = None):
     """Loads libmjhip.so (once). Raises if it has not been built: no fallback path exists."""
     global _lib
@@ -322,6 +331,9 @@ def load_library(path: str | None = None):
     if hasattr(lib, "mjh_integrate"):  # (likewise a build from before deriv_smooth_vel / implicit / euler)
         lib.mjh_integrate.argtypes = [ctypes.c_void_p, ctypes.POINTER(IntegrateArgs), ctypes.c_void_p]
         lib.mjh_integrate.restype = ctypes.c_int
+    if hasattr(lib, "mjh_jacobian"):  # (likewise a build from before the Jacobian block)
+        lib.mjh_jacobian.argtypes = [ctypes.c_void_p, ctypes.POINTER(JacobianArgs), ctypes.c_void_p]
+        lib.mjh_jacobian.restype = ctypes.c_int
     if hasattr(lib, "mjh_integrate_plan"):
         lib.mjh_integrate_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         lib.mjh_integrate_plan.restype = ctypes.c_int
