@@ -1473,6 +1473,25 @@ int run_support(const mjhModel* m, const DevModel<REAL>& M, const mjhSupportArgs
   return 0;
 }
 
+// The tail of the kernels that give every workgroup a.envs environments of a.lanes lanes and a.lds_env reals of LDS each (postcon, consens, energy, integrate): the
+// batch goes out in cuts of environments [env_begin, env_begin + env_count), timed as kernel `id`.  The caller has made its last refusal.
+template <typename REAL, template <typename> class Args>
+int launch_envs(void (*kernel)(Args<REAL>), Args<REAL>& a, int64_t B, hipStream_t s, int id) {
+  const size_t lds = (size_t)a.envs * a.lds_env * sizeof(REAL);
+  timing_begin(s);
+  if (const int rc = launch_cut(B, a.envs, [&](int64_t first, int64_t n, unsigned grid) {
+        a.env_begin = first; a.env_count = n;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(a.envs * a.lanes), lds, s, a);
+      }))
+    return rc;
+  timing_mark(s, id);
+  return 0;
+}
+
+// a.n = x->n as a pointer to (const) REAL: how the run_* functions from here to run_integrate copy the leaves of an ABI args struct into a kernel's
+#define P_(n) a.n = reinterpret_cast<const REAL*>(x->n);
+#define O_(n) a.n = reinterpret_cast<REAL*>(x->n);
+
 // body accelerations and forces of a finished forward pass (mjh_postcon.h): MuJoCo's mj_rnePostConstraint / mj_subtreeVel and the sensors that read them, one launch
 template <typename REAL>
 int run_postcon(const mjhModel* m, const DevModel<REAL>& M, const mjhPostconArgs* x, void* stream) {
@@ -1490,23 +1509,17 @@ int run_postcon(const mjhModel* m, const DevModel<REAL>& M, const mjhPostconArgs
     return fail(-22, "postconstraint: null pointer (rne leaves)");
   if (sub && (!x->ximat || !x->body_subtreemass || !x->subtree_linvel || !x->subtree_angmom)) return fail(-22, "postconstraint: null pointer (subtree leaves)");
   if (sns && (!x->sensordata_in || !x->sensordata || (M.nsite > 0 && (!x->site_xpos || !x->site_xmat)))) return fail(-22, "postconstraint: null pointer (sensor leaves)");
-  hipStream_t s = (hipStream_t)stream;
-  timing_begin(s);
   PostconArgs<REAL> a;
   memset(&a, 0, sizeof(a));
-#define P_(n) a.n = reinterpret_cast<const REAL*>(x->n);
   P_(qvel) P_(qacc) P_(cdof) P_(cdof_dot) P_(cvel) P_(cinert) P_(xipos) P_(ximat) P_(subtree_com) P_(efc_force) P_(contact_pos) P_(contact_frame) P_(contact_friction)
   P_(site_xpos) P_(site_xmat) P_(sensordata_in) P_(body_subtreemass)
-#undef P_
   a.xfrc = reinterpret_cast<const REAL*>(x->xfrc_applied);
   a.contact_dim = x->contact_dim; a.contact_geom = x->contact_geom; a.contact_efc_address = x->contact_efc_address;
   a.body_parentid = M.body_parentid; a.body_rootid = M.body_rootid; a.body_dofadr = M.body_dofadr; a.body_dofnum = M.body_dofnum; a.body_depth = M.body_depth;
   a.body_chain = M.body_chain; a.body_subtree_end = M.body_subtree_end; a.geom_bodyid = M.geom_bodyid;
   a.sns_type = M.sns_type; a.sns_adr = M.sns_adr; a.sns_objid = M.sns_objid; a.sns_bodyid = M.sns_bodyid; a.sns_rootid = M.sns_rootid; a.sns_datatype = M.sns_datatype;
   a.slot_sensor = M.slot_sensor; a.body_mass = M.body_mass; a.body_inertia = M.body_inertia; a.sns_cutoff = M.sns_cutoff;
-#define O_(n) a.n = reinterpret_cast<REAL*>(x->n);
   O_(cacc) O_(cfrc_int) O_(cfrc_ext) O_(subtree_linvel) O_(subtree_angmom) O_(sensordata)
-#undef O_
   const bool nograv = M.disableflags & DSBL_GRAVITY;
   for (int k = 0; k < 3; k++) a.cacc0[k] = nograv ? (REAL)0 : -M.gravity[k];
   a.nbody = M.nbody; a.nv = M.nv; a.nefc = M.nefc; a.ngeom = M.ngeom; a.nsite = M.nsite; a.nsensordata = M.nsensordata; a.max_depth = M.max_depth;
@@ -1514,14 +1527,7 @@ int run_postcon(const mjhModel* m, const DevModel<REAL>& M, const mjhPostconArgs
   a.pyramidal = M.cone != CONE_ELLIPTIC;
   a.flags = (rne ? MJH_POSTCON_RNE : 0) | (sub ? MJH_POSTCON_SUBTREE : 0) | (sns ? MJH_POSTCON_SENSORS : 0);
   a.lanes = m->pc_lanes; a.envs = m->pc_envs; a.lds_env = m->pc_lds_env;
-  const size_t lds = (size_t)a.envs * a.lds_env * sizeof(REAL);
-  if (const int rc = launch_cut(x->B, a.envs, [&](int64_t first, int64_t n, unsigned grid) {
-        a.env_begin = first; a.env_count = n;
-        hipLaunchKernelGGL((mjh_postcon_kernel<REAL>), dim3(grid), dim3(a.envs * a.lanes), lds, s, a);
-      }))
-    return rc;
-  timing_mark(s, MJH_KERNEL_POSTCON);
-  return 0;
+  return launch_envs(mjh_postcon_kernel<REAL>, a, x->B, (hipStream_t)stream, MJH_KERNEL_POSTCON);
 }
 
 // contact forces and the touch / framelinacc / frameangacc sensors of a finished forward pass (mjh_contact_sensors.h), one launch
@@ -1543,14 +1549,10 @@ int run_consens(const mjhModel* m, const DevModel<REAL>& M, const mjhContactSens
   if (sns && (!x->sns || !x->sns_cutoff || !x->sensordata || !x->cvel || !x->cacc || !x->subtree_com || !x->xipos || !x->xpos || (M.ngeom > 0 && !x->geom_xpos) ||
               (M.nsite > 0 && (!x->site_xpos || !x->site_xmat || !x->site_size)) || (M.ncam > 0 && !x->cam_xpos)))
     return fail(-22, "contact_sensors: null pointer (sensor leaves)");
-  hipStream_t s = (hipStream_t)stream;
-  timing_begin(s);
   ConSensArgs<REAL> a;
   memset(&a, 0, sizeof(a));
-#define P_(n) a.n = reinterpret_cast<const REAL*>(x->n);
   P_(efc_force) P_(contact_pos) P_(contact_frame) P_(contact_friction) P_(site_xpos) P_(site_xmat) P_(cvel) P_(cacc) P_(subtree_com) P_(xipos) P_(xpos) P_(geom_xpos)
   P_(cam_xpos) P_(site_size) P_(sns_cutoff)
-#undef P_
   a.contact_dim = x->contact_dim; a.contact_geom = x->contact_geom; a.contact_efc_address = x->contact_efc_address;
   a.geom_bodyid = M.geom_bodyid; a.sns = x->sns;
   a.force = reinterpret_cast<REAL*>(x->force); a.sensordata = reinterpret_cast<REAL*>(x->sensordata);
@@ -1564,14 +1566,7 @@ int run_consens(const mjhModel* m, const DevModel<REAL>& M, const mjhContactSens
   a.lds_env = m->cs_lds_env;
   const int64_t env_bytes = (int64_t)a.lds_env * (int64_t)sizeof(REAL);
   a.envs = (int)std::max<int64_t>(1, std::min<int64_t>(MJH_CONSENS_WG / a.lanes, kLdsWg / env_bytes));
-  const size_t lds = (size_t)a.envs * a.lds_env * sizeof(REAL);
-  if (const int rc = launch_cut(x->B, a.envs, [&](int64_t first, int64_t n, unsigned grid) {
-        a.env_begin = first; a.env_count = n;
-        hipLaunchKernelGGL((mjh_consens_kernel<REAL>), dim3(grid), dim3(a.envs * a.lanes), lds, s, a);
-      }))
-    return rc;
-  timing_mark(s, MJH_KERNEL_CONSENS);
-  return 0;
+  return launch_envs(mjh_consens_kernel<REAL>, a, x->B, (hipStream_t)stream, MJH_KERNEL_CONSENS);
 }
 
 // the energies and the joint / tendon limit and energy sensors of a finished forward pass (mjh_energy.h), one launch
@@ -1594,10 +1589,8 @@ int run_energy(const mjhModel* m, const DevModel<REAL>& M, const mjhEnergyArgs* 
     return fail(-22, "energy: null pointer (sensor leaves)");
   EnergyArgs<REAL> a;
   memset(&a, 0, sizeof(a));
-#define P_(n) a.n = reinterpret_cast<const REAL*>(x->n);
   P_(qpos) P_(qvel) P_(xipos) P_(ten_length) P_(qM) P_(efc_J) P_(efc_force) P_(gravity) P_(body_mass) P_(jnt_stiffness) P_(qpos_spring) P_(jnt_range) P_(jnt_margin)
   P_(tendon_stiffness) P_(tendon_lengthspring) P_(tendon_range) P_(tendon_margin) P_(sns_cutoff)
-#undef P_
   a.jnt_type = M.jnt_type; a.jnt_qposadr = M.jnt_qposadr; a.sns = x->sns;
   a.energy = reinterpret_cast<REAL*>(x->energy); a.sensordata = reinterpret_cast<REAL*>(x->sensordata);
   a.nq = M.nq; a.nv = M.nv; a.nbody = M.nbody; a.njnt = M.njnt; a.ntendon = M.ntendon; a.nefc = M.nefc; a.nsensordata = M.nsensordata;
@@ -1618,16 +1611,7 @@ int run_energy(const mjhModel* m, const DevModel<REAL>& M, const mjhEnergyArgs* 
   if (chunk < 1) return fail(-12, "energy: nv too large for the LDS chunk of one environment");
   a.chunk = chunk;
   a.lds_env = (fixed + chunk * nv + 3) & ~3;
-  const size_t lds = (size_t)a.envs * a.lds_env * sizeof(REAL);
-  hipStream_t s = (hipStream_t)stream;
-  timing_begin(s);  // (behind the last refusal)
-  if (const int rc = launch_cut(x->B, a.envs, [&](int64_t first, int64_t n, unsigned grid) {
-        a.env_begin = first; a.env_count = n;
-        hipLaunchKernelGGL((mjh_energy_kernel<REAL>), dim3(grid), dim3(a.envs * a.lanes), lds, s, a);
-      }))
-    return rc;
-  timing_mark(s, MJH_KERNEL_ENERGY);
-  return 0;
+  return launch_envs(mjh_energy_kernel<REAL>, a, x->B, (hipStream_t)stream, MJH_KERNEL_ENERGY);
 }
 
 // the Jacobian block on a finished forward pass (mjh_jacobian.h): matrices by one lane per element, products (vec given) by 16 lanes per environment
@@ -1646,9 +1630,7 @@ int run_jacobian(const mjhModel* m, const DevModel<REAL>& M, const mjhJacobianAr
     return fail(-22, "jacobian: null pointer");
   JacArgs<REAL> a;
   memset(&a, 0, sizeof(a));
-#define P_(n) a.n = reinterpret_cast<const REAL*>(x->n);
   P_(cdof) P_(cdof_dot) P_(cvel) P_(subtree_com) P_(xipos) P_(ximat) P_(body_mass) P_(body_subtreemass) P_(body_inertia) P_(point) P_(vec)
-#undef P_
   a.body = x->body_id; a.body_stride = (int)x->body_stride;
   a.body_dofmask = M.body_dofmask; a.body_rootid = M.body_rootid; a.body_subtree_end = M.body_subtree_end;
   a.dof_bodyid = M.dof_bodyid; a.dof_jntid = M.dof_jntid; a.jnt_type = M.jnt_type; a.jnt_dofadr = M.jnt_dofadr;
@@ -1738,13 +1720,9 @@ int run_integrate(const mjhModel* m, const DevModel<REAL>& M, const mjhIntegrate
   }
   IntegrateArgs<REAL> a;
   memset(&a, 0, sizeof(a));
-#define P_(n) a.n = reinterpret_cast<const REAL*>(x->n);
   P_(qpos) P_(qvel) P_(act) P_(act_dot) P_(time) P_(ctrl) P_(qacc) P_(qM) P_(qfrc_smooth) P_(qfrc_constraint) P_(actuator_moment) P_(ten_J)
   P_(dof_damping) P_(tendon_damping) P_(gainprm) P_(biasprm) P_(dynprm) P_(actrange)
-#undef P_
-#define O_(n) a.n = reinterpret_cast<REAL*>(x->n);
   O_(qpos_out) O_(qvel_out) O_(act_out) O_(time_out) O_(qderiv_out) O_(qacc_out)
-#undef O_
   a.act_gaintype = M.act_gaintype; a.act_biastype = M.act_biastype; a.act_dyntype = M.act_dyntype; a.act_actadr = M.act_actadr; a.act_actlimited = M.act_actlimited;
   a.jnt_type = M.jnt_type; a.jnt_qposadr = M.jnt_qposadr; a.jnt_dofadr = M.jnt_dofadr;
   a.h = (REAL)x->h;
@@ -1755,17 +1733,11 @@ int run_integrate(const mjhModel* m, const DevModel<REAL>& M, const mjhIntegrate
   int plan[4];
   if (integrate_plan(nv, nu, nt, (int)sizeof(REAL), plan)) return fail(-12, "integrate: nv too large for the LDS of one workgroup");
   a.lanes = plan[0]; a.envs = plan[1]; a.chunk = plan[2]; a.lds_env = plan[3];
-  const size_t lds = (size_t)a.envs * a.lds_env * sizeof(REAL);
-  hipStream_t s = (hipStream_t)stream;
-  timing_begin(s);  // (behind the last refusal)
-  if (const int rc = launch_cut(x->B, a.envs, [&](int64_t first, int64_t n, unsigned grid) {
-        a.env_begin = first; a.env_count = n;
-        hipLaunchKernelGGL((mjh_integrate_kernel<REAL>), dim3(grid), dim3(a.envs * a.lanes), lds, s, a);
-      }))
-    return rc;
-  timing_mark(s, MJH_KERNEL_INTEGRATE);
-  return 0;
+  return launch_envs(mjh_integrate_kernel<REAL>, a, x->B, (hipStream_t)stream, MJH_KERNEL_INTEGRATE);
 }
+
+#undef P_
+#undef O_
 
 // ---- finite-difference transition Jacobians (mjh_fd.h): the launches on either side of the caller's mjh_step over the perturbed environments ----
 

@@ -23,76 +23,32 @@ current stream.  ``torch.vmap`` / ``torch.compile``: there is no operator for th
 
 from __future__ import annotations
 
-import ctypes
 import math
 
 import numpy as np
 import torch
 
+from . import native
+from ._postpass import bind, cached, call, check_leaves, probe, refuse_tracing, require_device, upload
+from .postconstraint import CONTACT_INTS
+
 FORCES, SENSORS, WORLD = 1, 2, 4  # include/mjhip.h MJH_CONSENS_*
 TOUCH = 0
 _ZONES = {2: "sphere", 3: "capsule", 4: "ellipsoid", 5: "cylinder", 6: "box"}  # the site shapes a touch zone can have (GeomType)
-_INTS = dict(contact_dim=torch.int32, contact_geom=torch.int64, contact_efc_address=torch.int64)
 _DEV = {}  # (tables uid, dtype, device) -> the sensor rows and cutoffs on the device
-_SIZES = {}  # (tables uid, dtype, device) -> (the bytes of Model.site_size, its device copy)
 
 
 def _tables(m, dtype, device):
-    T = m.tables
-    k = (T.uid, dtype, device)
-    hit = _DEV.get(k)
-    if hit is None:
-        cs = T.contact_sensors
+    def make():
+        cs = m.tables.contact_sensors
         counts = (int(m.nbody), int(m.nbody), int(m.ngeom), int(m.nsite), int(m.ncam))
         for r in cs["rows"]:  # (the kernel indexes with these unchecked)
             if not (0 <= r[1] and r[1] + (1 if r[0] == TOUCH else 3) <= int(m.nsensordata) and 0 <= r[3] < 5 and 0 <= r[2] < counts[r[3]] and 0 <= r[4] < counts[0]
                     and 0 <= r[5] < counts[0]):
                 raise RuntimeError(f"contact-sensor table row {r.tolist()} does not address this Model")
-        hit = dict(rows=torch.tensor(cs["rows"], dtype=torch.int32, device=device).contiguous(), cutoff=torch.tensor(cs["cutoff"], dtype=dtype, device=device).contiguous())
-        if len(_DEV) > 256:
-            _DEV.clear()
-        _DEV[k] = hit
-    return hit
+        return dict(rows=torch.tensor(cs["rows"], dtype=torch.int32, device=device).contiguous(), cutoff=torch.tensor(cs["cutoff"], dtype=dtype, device=device).contiguous())
 
-
-def _sizes(m, size, dtype, device):
-    """Model.site_size (a host array of the Model, read at each call) on the device: uploaded again only when its values changed."""
-    k = (m.tables.uid, dtype, device)
-    key = size.tobytes()
-    hit = _SIZES.get(k)
-    if hit is None or hit[0] != key:
-        if len(_SIZES) > 256:
-            _SIZES.clear()
-        hit = _SIZES[k] = (key, torch.tensor(size, dtype=dtype, device=device).contiguous())
-    return hit[1]
-
-
-def _refuse_tracing(name, *tensors):
-    from .forward import _plain
-
-    if torch.compiler.is_compiling() or not all(_plain(t) for t in tensors if isinstance(t, torch.Tensor)):
-        raise NotImplementedError(f"{name} cannot be used under torch.vmap / torch.compile: there is no operator for it.  Call it on a "
-                                  "batched Data directly (every leading dimension of a leaf is the batch).")
-
-
-def _batch(name, m, d):
-    q, nq = d.qpos, int(m.nq)
-    if q.dim() < 1 or q.shape[-1] != nq:
-        raise ValueError(f"{name}: qpos has shape {tuple(q.shape)}, expected (..., {nq}) for this Model")
-    if q.dtype not in (torch.float64, torch.float32):
-        raise ValueError(f"{name}: unsupported Data dtype {q.dtype}")
-    if q.dtype != m.qpos0.dtype:
-        raise ValueError(f"{name}: the Data is {q.dtype}, the Model {m.qpos0.dtype}: it runs in the model's dtype")
-    return tuple(q.shape[:-1]), q.dtype, q.device
-
-
-def _check(name, leaves, tails, batch, dtype, device):
-    for n, t in leaves.items():
-        want = batch + tails[n]
-        if tuple(t.shape) != want and not (len(tails[n]) == 3 and tuple(t.shape) == batch + (tails[n][0], 9)):
-            raise ValueError(f"{name}: {n} has shape {tuple(t.shape)}, expected {want} for a Data of batch shape {batch}")
-        if t.dtype != _INTS.get(n, dtype) or t.device != device:
-            raise ValueError(f"{name}: {n} is {t.dtype} on {t.device}, expected {_INTS.get(n, dtype)} on {device}")
+    return cached(_DEV, (m.tables.uid, dtype, device), make)
 
 
 def _contact_leaves(m, d):
@@ -107,33 +63,10 @@ def _contact_leaves(m, d):
     return leaves, tails
 
 
-def _launch(name, m, device, dtype, B, flags, leaves, outputs, nsens=0):
-    from . import native
-    from .forward import _stream_and_guard
-    from .ray import _handle
-
-    nm = _handle(m, device, dtype)
-    if not hasattr(nm.lib, "mjh_contact_sensors"):
-        raise RuntimeError(f"{native.LIB_PATH} predates {name} (no mjh_contact_sensors): rebuild the library")
-    a = native.ContactSensorArgs()
-    a.flags, a.nsens, a.B = flags, nsens, B
-    keep = []
-    for n, t in leaves.items():
-        if t.numel() == 0:
-            continue
-        t = t.contiguous()
-        keep.append(t)
-        setattr(a, n, t.data_ptr())
-    for n, t in outputs.items():
-        setattr(a, n, t.data_ptr())
-    stream, prev = _stream_and_guard(device)
-    try:
-        rc = nm.lib.mjh_contact_sensors(nm.handle, ctypes.byref(a), ctypes.c_void_p(stream))
-    finally:
-        if prev is not None:
-            torch.cuda.set_device(prev)
-    if rc != 0:
-        raise RuntimeError(f"native {name} failed ({rc}): {nm.lib.mjh_last_error().decode()}")
+def _launch(name, m, device, dtype, B, flags, tensors, nsens=0):
+    a = native.ARGS["mjh_contact_sensors"](flags=flags, nsens=nsens, B=B)
+    bind(a, tensors)
+    call(name, m, "mjh_contact_sensors", a, device, dtype)
 
 
 def _slots(name, contact_id, ncon):
@@ -157,22 +90,20 @@ def contact_force(m, d, contact_id=None, to_world_frame: bool = False):
     """The force of every contact slot of the finished pass ``d`` holds (MuJoCo's ``mj_contactForce``): ``S + (ncon, 6)``, each row ``[force(3), torque(3)]`` in
     the contact frame (``[..., 0]`` is the normal force), or in the world frame with ``to_world_frame=True``.  ``contact_id``: an int (``S + (6,)``) or a flat
     sequence of slots shared by all environments (``S + (P, 6)``).  An unused slot gives zeros; a model without contacts or constraint rows an empty / zero result."""
-    from .forward import _require_device
-
     name = "contact_force"
-    _refuse_tracing(name, d.qpos, d.efc_force)
+    refuse_tracing(name, d.qpos, d.efc_force)
     _, _, _, ncon, nefc = m.constraint_sizes_py
-    batch, dtype, device = _batch(name, m, d)
+    batch, dtype, device = probe(name, m, "qpos", d.qpos, (int(m.nq),))
     leaves, tails = _contact_leaves(m, d)
-    _check(name, leaves, tails, batch, dtype, device)
+    check_leaves(name, leaves, tails, batch, dtype, device, 3, CONTACT_INTS)
     ids, one = (None, False) if contact_id is None else _slots(name, contact_id, ncon)
-    _require_device(device)
+    require_device(device)
     B = int(math.prod(batch)) if batch else 1
     if B == 0 or not leaves:
         out = torch.zeros(batch + (ncon, 6), dtype=dtype, device=device)
     else:
         out = torch.empty(batch + (ncon, 6), dtype=dtype, device=device)
-        _launch(name, m, device, dtype, B, FORCES | (WORLD if to_world_frame else 0), leaves, dict(force=out))
+        _launch(name, m, device, dtype, B, FORCES | (WORLD if to_world_frame else 0), dict(leaves, force=out))
     if ids is None:
         return out
     return out[..., ids[0], :] if one else out[..., torch.tensor(ids, dtype=torch.int64, device=device), :]
@@ -194,7 +125,7 @@ def sensor_postconstraint(m, d, qvel=None, *, all_sensors: bool = False):
     ``all_sensors=True``: the same ``Data`` with, in addition, the slots of the jointlimitpos / vel / frc, tendonlimitpos / vel / frc, e_potential and e_kinetic
     sensors written (``energy.py``: one more launch; ``qvel`` serves the limit velocities and the kinetic energy too)."""
     name = "sensor_postconstraint"
-    _refuse_tracing(name, d.qpos, qvel)
+    refuse_tracing(name, d.qpos, qvel)
     _refuse_zones(name, m)
     if not all_sensors:
         return _sensor_postconstraint(name, m, d, qvel)
@@ -214,12 +145,12 @@ def _sensor_postconstraint(name, m, d, qvel):
     nsd = int(getattr(m, "nsensordata", 0) or 0)
     extra, tails = {}, {}
     if len(rows) and nsd > 0:  # (checked before the first launch: a refused call launches nothing)
-        batch, dtype, device = _batch(name, m, d)
+        batch, dtype, device = probe(name, m, "qpos", d.qpos, (int(m.nq),))
         nb, ng, ns, nc = int(m.nbody), int(m.ngeom), int(m.nsite), int(m.ncam)
         extra, tails = _contact_leaves(m, d)
         extra.update(xpos=d.xpos, geom_xpos=d.geom_xpos, cam_xpos=d.cam_xpos)
         tails.update(xpos=(nb, 3), geom_xpos=(ng, 3), cam_xpos=(nc, 3))
-        _check(name, extra, tails, batch, dtype, device)
+        check_leaves(name, extra, tails, batch, dtype, device, 3, CONTACT_INTS)
         size = np.asarray(m.site_size.detach().cpu().numpy() if isinstance(m.site_size, torch.Tensor) else m.site_size, dtype=np.float64)
         if size.shape != (ns, 3):
             raise ValueError(f"{name}: Model.site_size has shape {size.shape}, expected ({ns}, 3)")
@@ -230,7 +161,7 @@ def _sensor_postconstraint(name, m, d, qvel):
     if B == 0:
         return out
     t = _tables(m, dtype, device)
-    leaves = dict(extra, site_xpos=d.site_xpos, site_xmat=d.site_xmat, cvel=d.cvel, cacc=out.cacc, subtree_com=d.subtree_com, xipos=d.xipos, site_size=_sizes(m, size, dtype, device),
-                  sns=t["rows"], sns_cutoff=t["cutoff"])
-    _launch(name, m, device, dtype, B, SENSORS, leaves, dict(sensordata=out.sensordata), nsens=int(t["rows"].shape[0]))
+    leaves = dict(extra, site_xpos=d.site_xpos, site_xmat=d.site_xmat, cvel=d.cvel, cacc=out.cacc, subtree_com=d.subtree_com, xipos=d.xipos, site_size=upload(m, "site_size", size, dtype, device),
+                  sns=t["rows"], sns_cutoff=t["cutoff"], sensordata=out.sensordata)
+    _launch(name, m, device, dtype, B, SENSORS, leaves, nsens=int(t["rows"].shape[0]))
     return out

@@ -24,26 +24,18 @@ Every leading dimension of a leaf is the batch (S); nothing is written to the in
 
 from __future__ import annotations
 
-import ctypes
 import math
 
 import numpy as np
 import torch
 
+from . import native
 from ._enums import DisableBit
+from ._postpass import bind, cached, call, check_leaves, check_override, model_value, probe, refuse_tracing, require_device, upload
 
 POS, VEL, SENSORS = 1, 2, 4  # include/mjhip.h MJH_ENERGY_*
 E_POTENTIAL, E_KINETIC = 43, 44
 _DEV = {}   # (tables uid, device) -> the sensor rows on the device
-_HOST = {}  # (tables uid, name, dtype, device) -> (the bytes of a host value, its device copy)
-
-
-def _refuse_tracing(name, *tensors):
-    from .forward import _plain
-
-    if torch.compiler.is_compiling() or not all(_plain(t) for t in tensors if isinstance(t, torch.Tensor)):
-        raise NotImplementedError(f"{name} cannot be used under torch.vmap / torch.compile: there is no operator for it.  Call it on a "
-                                  "batched Data directly (every leading dimension of a leaf is the batch).")
 
 
 def plan(name: str, m, leaves: dict, overrides: dict):
@@ -52,42 +44,12 @@ def plan(name: str, m, leaves: dict, overrides: dict):
     nq, nv, nb, nt, nsd = int(m.nq), int(m.nv), int(m.nbody), int(m.ntendon), int(getattr(m, "nsensordata", 0) or 0)
     nefc = int(m.constraint_sizes_py[4])
     tails = dict(qpos=(nq,), qvel=(nv,), xipos=(nb, 3), ten_length=(nt,), qM=(nv, nv), efc_J=(nefc, nv), efc_force=(nefc,), sensordata=(nsd,))
-    xipos = leaves["xipos"]
-    if xipos.dim() < 2 or tuple(xipos.shape[-2:]) != (nb, 3):
-        raise ValueError(f"{name}: xipos has shape {tuple(xipos.shape)}, expected (..., {nb}, 3) for this Model")
-    batch, dtype, device = tuple(xipos.shape[:-2]), xipos.dtype, xipos.device
-    if dtype not in (torch.float64, torch.float32):
-        raise ValueError(f"{name}: unsupported Data dtype {dtype}")
-    if dtype != m.qpos0.dtype:
-        raise ValueError(f"{name}: the Data is {dtype}, the Model {m.qpos0.dtype}: it runs in the model's dtype")
-    for n, t in leaves.items():
-        want = batch + tails[n]
-        if tuple(t.shape) != want and not (len(tails[n]) == 2 and tuple(t.shape) == batch + (tails[n][0] * tails[n][1],)):
-            raise ValueError(f"{name}: {n} has shape {tuple(t.shape)}, expected {want} for a Data of batch shape {batch}")
-        if t.dtype != dtype or t.device != device:
-            raise ValueError(f"{name}: {n} is {t.dtype} on {t.device}, expected {dtype} on {device}")
+    batch, dtype, device = probe(name, m, "xipos", leaves["xipos"], (nb, 3))
+    check_leaves(name, leaves, tails, batch, dtype, device, 2)
     for n, t in overrides.items():
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor) or tuple(t.shape) != batch + tails[n]:
-            raise ValueError(f"{name}: {n}= must have shape {batch + tails[n]} (the {n} the pass ran on, per environment); got "
-                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
-        if t.dtype != dtype or t.device != device:
-            raise ValueError(f"{name}: {n}= is {t.dtype} on {t.device}, the Data is {dtype} on {device}")
+        if t is not None:
+            check_override(name, n, t, batch + tails[n], dtype, device, f"the {n} the pass ran on, per environment")
     return batch, dtype, device
-
-
-def _upload(m, name, value, dtype, device):
-    """A host value of the Model (read at each call) on the device: uploaded again only when its values changed."""
-    arr = np.ascontiguousarray(np.asarray(value, dtype=np.float64))
-    k = (m.tables.uid, name, dtype, device)
-    key = arr.tobytes()
-    hit = _HOST.get(k)
-    if hit is None or hit[0] != key:
-        if len(_HOST) > 1024:
-            _HOST.clear()
-        hit = _HOST[k] = (key, torch.tensor(arr, dtype=dtype, device=device).contiguous())
-    return hit[1]
 
 
 def _values(name, m, dtype, device, cutoff_of=None):
@@ -103,7 +65,7 @@ def _values(name, m, dtype, device, cutoff_of=None):
         v = m.opt.gravity if n == "gravity" else (getattr(m, n) if hasattr(m, n) else getattr(src, n))
         if tuple(np.shape(v)) != shape:
             raise ValueError(f"{name}: Model.{'opt.' if n == 'gravity' else ''}{n} has shape {tuple(np.shape(v))}, expected {shape}")
-        out[n] = v.detach().to(device=device, dtype=dtype).contiguous() if isinstance(v, torch.Tensor) else _upload(m, n, v, dtype, device)
+        out[n] = model_value(m, n, v, dtype, device)
     if cutoff_of is not None:
         cut = m.sensor_cutoff
         if tuple(np.shape(cut)) != (int(m.nsensor),):
@@ -111,52 +73,27 @@ def _values(name, m, dtype, device, cutoff_of=None):
         if isinstance(cut, torch.Tensor):  # (gathered where it lives: no copy to the host)
             out["sns_cutoff"] = cut.detach()[torch.as_tensor(cutoff_of, dtype=torch.int64, device=cut.device)].to(device=device, dtype=dtype).contiguous()
         else:
-            out["sns_cutoff"] = _upload(m, "sensor_cutoff", np.asarray(cut, dtype=np.float64)[cutoff_of], dtype, device)
+            out["sns_cutoff"] = upload(m, "sensor_cutoff", np.asarray(cut, dtype=np.float64)[cutoff_of], dtype, device)
     return out
 
 
 def _rows(name, m, device):
-    T = m.tables
-    k = (T.uid, device)
-    hit = _DEV.get(k)
-    if hit is None:
-        rows = T.energy_sensors["rows"]
+    def make():
+        rows = m.tables.energy_sensors["rows"]
         nefc = int(m.constraint_sizes_py[4])
         for r in rows:  # (the kernel indexes with these unchecked)
             count = int(m.ntendon) if 23 <= r[0] <= 25 else (int(m.njnt) if 20 <= r[0] <= 22 else 1)
             if not (0 <= r[1] < int(m.nsensordata) and (r[0] in (E_POTENTIAL, E_KINETIC) or 0 <= r[2] < count) and -1 <= r[3] < nefc):
                 raise RuntimeError(f"energy-sensor table row {r.tolist()} does not address this Model")
-        if len(_DEV) > 256:
-            _DEV.clear()
-        hit = _DEV[k] = torch.tensor(rows, dtype=torch.int32, device=device).contiguous()
-    return hit
+        return torch.tensor(rows, dtype=torch.int32, device=device).contiguous()
+
+    return cached(_DEV, (m.tables.uid, device), make)
 
 
 def _launch(name, m, device, dtype, B, flags, tensors, nsens=0):
-    from . import native
-    from .forward import _stream_and_guard
-    from .ray import _handle
-
-    nm = _handle(m, device, dtype)
-    if not hasattr(nm.lib, "mjh_energy"):
-        raise RuntimeError(f"{native.LIB_PATH} predates {name} (no mjh_energy): rebuild the library")
-    a = native.EnergyArgs()
-    a.flags, a.nsens, a.B = flags, nsens, B
-    keep = []
-    for n, t in tensors.items():
-        if t.numel() == 0:
-            continue
-        t = t.contiguous()
-        keep.append(t)
-        setattr(a, n, t.data_ptr())
-    stream, prev = _stream_and_guard(device)
-    try:
-        rc = nm.lib.mjh_energy(nm.handle, ctypes.byref(a), ctypes.c_void_p(stream))
-    finally:
-        if prev is not None:
-            torch.cuda.set_device(prev)
-    if rc != 0:
-        raise RuntimeError(f"native {name} failed ({rc}): {nm.lib.mjh_last_error().decode()}")
+    a = native.ARGS["mjh_energy"](flags=flags, nsens=nsens, B=B)
+    bind(a, tensors)
+    call(name, m, "mjh_energy", a, device, dtype)
 
 
 def _springs(m):
@@ -164,9 +101,7 @@ def _springs(m):
 
 
 def _run(name, m, d, flags, qpos, qvel):
-    from .forward import _require_device
-
-    _refuse_tracing(name, d.qpos, qpos, qvel)
+    refuse_tracing(name, d.qpos, qpos, qvel)
     leaves = dict(xipos=d.xipos)
     if flags & POS:
         leaves.update(qpos=d.qpos)
@@ -176,7 +111,7 @@ def _run(name, m, d, flags, qpos, qvel):
         leaves.update(qvel=d.qvel, qM=d.qM)
     batch, dtype, device = plan(name, m, leaves, dict(qpos=qpos if flags & POS else None, qvel=qvel if flags & VEL else None))
     values = _values(name, m, dtype, device) if flags & POS else {}
-    _require_device(device)
+    require_device(device)
     if qpos is not None and flags & POS:
         leaves["qpos"] = qpos
     if qvel is not None and flags & VEL:

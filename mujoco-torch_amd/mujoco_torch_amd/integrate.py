@@ -33,14 +33,14 @@ Every leading dimension of a leaf is the batch (S); nothing is written to the in
 
 from __future__ import annotations
 
-import ctypes
 import math
 
 import numpy as np
 import torch
 
+from . import native
 from ._enums import DisableBit
-from .energy import _refuse_tracing, _upload
+from ._postpass import bind, call, check_leaves, model_value, probe, refuse_tracing, require_device
 
 QDERIV, IMPLICIT, EULER, STATE, WRITE_QDERIV, WRITE_QACC = 1, 2, 4, 8, 16, 32  # include/mjhip.h MJH_INTEGRATE_*
 FLUID_MESSAGE = "fluid drag not supported for implicitfast"  # (the reference's, derivative.py:64)
@@ -56,20 +56,8 @@ def plan(name: str, m, leaves: dict):
     nq, nv, nu, na, nt = z["nq"], z["nv"], z["nu"], z["na"], z["nt"]
     tails = dict(qpos=(nq,), qvel=(nv,), act=(na,), act_dot=(na,), time=(), ctrl=(nu,), qacc=(nv,), qM=(nv, nv), qfrc_smooth=(nv,), qfrc_constraint=(nv,),
                  actuator_moment=(nu, nv), ten_J=(nt, nv))
-    qvel = leaves["qvel"]
-    if not isinstance(qvel, torch.Tensor) or qvel.dim() < 1 or int(qvel.shape[-1]) != nv:
-        raise ValueError(f"{name}: qvel has shape {tuple(getattr(qvel, 'shape', ()))}, expected (..., {nv}) for this Model")
-    batch, dtype, device = tuple(qvel.shape[:-1]), qvel.dtype, qvel.device
-    if dtype not in (torch.float64, torch.float32):
-        raise ValueError(f"{name}: unsupported Data dtype {dtype}")
-    if dtype != m.qpos0.dtype:
-        raise ValueError(f"{name}: the Data is {dtype}, the Model {m.qpos0.dtype}: it runs in the model's dtype")
-    for n, t in leaves.items():
-        want = batch + tails[n]
-        if tuple(t.shape) != want and not (len(tails[n]) == 2 and tuple(t.shape) == batch + (tails[n][0] * tails[n][1],)):
-            raise ValueError(f"{name}: {n} has shape {tuple(t.shape)}, expected {want} for a Data of batch shape {batch}")
-        if t.dtype != dtype or t.device != device:
-            raise ValueError(f"{name}: {n} is {t.dtype} on {t.device}, expected {dtype} on {device}")
+    batch, dtype, device = probe(name, m, "qvel", leaves["qvel"], (nv,))
+    check_leaves(name, leaves, tails, batch, dtype, device, 2)
     return batch, dtype, device
 
 
@@ -87,8 +75,7 @@ def _values(name, m, dtype, device, names):
         least = {"gainprm": 3, "biasprm": 3, "dynprm": 1}.get(n)
         if len(got) != len(shape) or any(w is not None and g != w for g, w in zip(got, shape)) or (least is not None and got[1] < least):
             raise ValueError(f"{name}: Model.{field} has shape {got}, expected {tuple('>= %d' % least if w is None else w for w in shape)}")
-        t = v.detach().to(device=device, dtype=dtype).contiguous() if isinstance(v, torch.Tensor) else _upload(m, field, v, dtype, device)
-        out[n] = (t, got[1] if len(got) == 2 else 1)
+        out[n] = (model_value(m, field, v, dtype, device), got[1] if len(got) == 2 else 1)
     return out
 
 
@@ -117,38 +104,14 @@ def _refuse_fluid(m):
 
 
 def _launch(name, m, device, dtype, B, flags, h, tensors, values, outs):
-    from . import native
-    from .forward import _stream_and_guard
-    from .ray import _handle
-
-    nm = _handle(m, device, dtype)
-    if not hasattr(nm.lib, "mjh_integrate"):
-        raise RuntimeError(f"{native.LIB_PATH} predates {name} (no mjh_integrate): rebuild the library")
-    a = native.IntegrateArgs()
-    a.flags, a.disableflags, a.B, a.h = flags, int(m.opt.disableflags), B, h
-    keep = []
-    for n, t in tensors.items():
-        if t.numel() == 0:
-            continue
-        t = t.contiguous()
-        keep.append(t)
-        setattr(a, n, t.data_ptr())
+    a = native.ARGS["mjh_integrate"](flags=flags, disableflags=int(m.opt.disableflags), B=B, h=h)
+    tensors = dict(tensors, **outs)
     for n, (t, stride) in values.items():
+        tensors[n] = t
         if n in ("gainprm", "biasprm", "dynprm"):
             setattr(a, n[:-3] + "_stride", stride)
-        if t.numel():
-            setattr(a, n, t.data_ptr())
-    for n, t in outs.items():
-        if t.numel():
-            setattr(a, n, t.data_ptr())
-    stream, prev = _stream_and_guard(device)
-    try:
-        rc = nm.lib.mjh_integrate(nm.handle, ctypes.byref(a), ctypes.c_void_p(stream))
-    finally:
-        if prev is not None:
-            torch.cuda.set_device(prev)
-    if rc != 0:
-        raise RuntimeError(f"native {name} failed ({rc}): {nm.lib.mjh_last_error().decode()}")
+    bind(a, tensors)
+    call(name, m, "mjh_integrate", a, device, dtype)
 
 
 def _build_leaves(m, d, actuation, tendons):
@@ -178,10 +141,8 @@ def deriv_smooth_vel(m, d):
     """The analytic derivative of the smooth forces with respect to ``qvel`` of the finished pass ``d`` holds, ``S + (nv, nv)`` (the full symmetric matrix), or
     ``None`` when no term applies (ACTUATION and DAMPER disabled, no tendons); the reference's ``derivative.deriv_smooth_vel``, its quirks included (the module
     docstring).  Raises the reference's ``NotImplementedError`` for fluid parameters unless DAMPER or SPRING is disabled."""
-    from .forward import _require_device
-
     name = "deriv_smooth_vel"
-    _refuse_tracing(name, d.qvel, d.ctrl)
+    refuse_tracing(name, d.qvel, d.ctrl)
     actuation, damper, tendons = _terms(m)
     leaves = dict(qvel=d.qvel, **_build_leaves(m, d, actuation, tendons))
     batch, dtype, device = plan(name, m, leaves)
@@ -189,7 +150,7 @@ def deriv_smooth_vel(m, d):
     if not (actuation or damper or tendons):
         return None
     _refuse_fluid(m)
-    _require_device(device)
+    require_device(device)
     nv = int(m.nv)
     B = int(math.prod(batch)) if batch else 1
     out = torch.empty(batch + (nv, nv), dtype=dtype, device=device)
@@ -201,9 +162,7 @@ def deriv_smooth_vel(m, d):
 
 
 def _integrate(name, m, d, dt, return_qacc, implicit):
-    from .forward import _require_device
-
-    _refuse_tracing(name, d.qpos, d.qvel, dt)
+    refuse_tracing(name, d.qpos, d.qvel, dt)
     h = _step_size(name, m, dt)
     z = _sizes(m)
     actuation, damper, tendons = _terms(m) if implicit else (False, False, False)
@@ -227,7 +186,7 @@ def _integrate(name, m, d, dt, return_qacc, implicit):
     values = _values(name, m, dtype, device, value_names)
     if implicit:
         _refuse_fluid(m)
-    _require_device(device)
+    require_device(device)
     B = int(math.prod(batch)) if batch else 1
     new = lambda *tail: torch.empty(batch + tail, dtype=dtype, device=device)
     outs = dict(qpos_out=new(z["nq"]), qvel_out=new(z["nv"]), act_out=new(z["na"]), time_out=new())

@@ -23,13 +23,13 @@ these functions; they raise ``NotImplementedError``.
 
 from __future__ import annotations
 
-import ctypes
 import math
 
 import numpy as np
 import torch
 
-from .energy import _refuse_tracing, _upload
+from . import native
+from ._postpass import bind, call, check_leaves, check_override, model_value, probe, refuse_tracing, require_device
 from .support import _device_ids, _query_mode, _strides, body_ids
 
 POINT, DOT, SUBTREE_COM, ANGMOM = range(4)  # include/mjhip.h MJH_JACOBIAN_*
@@ -58,20 +58,8 @@ def plan(name: str, m, op: int, leaves: dict, point, vec, ids: tuple, listed: bo
     """Shape, dtype and device checks of one call: (batch, dtype, device, P or None, the point's mode)."""
     nv, nb = int(m.nv), int(m.nbody)
     tails = dict(cdof=(nv, 6), cdof_dot=(nv, 6), cvel=(nb, 6), subtree_com=(nb, 3), xipos=(nb, 3), ximat=(nb, 3, 3))
-    cdof = leaves["cdof"]
-    if cdof.dim() < 2 or tuple(cdof.shape[-2:]) != (nv, 6):
-        raise ValueError(f"{name}: cdof has shape {tuple(cdof.shape)}, expected (..., {nv}, 6) for this Model")
-    batch, dtype, device = tuple(cdof.shape[:-2]), cdof.dtype, cdof.device
-    if dtype not in (torch.float64, torch.float32):
-        raise ValueError(f"{name}: unsupported Data dtype {dtype}")
-    if dtype != m.qpos0.dtype:
-        raise ValueError(f"{name}: the Data is {dtype}, the Model {m.qpos0.dtype}: it runs in the model's dtype")
-    for n, t in leaves.items():
-        want = batch + tails[n]
-        if tuple(t.shape) != want and not (n == "ximat" and tuple(t.shape) == batch + (nb, 9)):
-            raise ValueError(f"{name}: {n} has shape {tuple(t.shape)}, expected {want} for a Data of batch shape {batch}")
-        if t.dtype != dtype or t.device != device:
-            raise ValueError(f"{name}: {n} is {t.dtype} on {t.device}, expected {dtype} on {device}")
+    batch, dtype, device = probe(name, m, "cdof", leaves["cdof"], (nv, 6))
+    check_leaves(name, leaves, tails, batch, dtype, device, 3)
     mode, P = None, (len(ids) if listed else None)
     if point is not None:
         if not isinstance(point, torch.Tensor):
@@ -87,11 +75,7 @@ def plan(name: str, m, op: int, leaves: dict, point, vec, ids: tuple, listed: bo
                 raise ValueError(f"{name}: {len(ids)} body ids for {mode[1]} points")
             P = mode[1]
     if vec is not None:
-        if not isinstance(vec, torch.Tensor) or tuple(vec.shape) != batch + (nv,):
-            raise ValueError(f"{name}: vec= must have shape {batch + (nv,)} (one vector per environment); got "
-                             f"{tuple(vec.shape) if isinstance(vec, torch.Tensor) else type(vec).__name__}")
-        if vec.dtype != dtype or vec.device != device:
-            raise ValueError(f"{name}: vec= is {vec.dtype} on {vec.device}, the Data is {dtype} on {device}")
+        check_override(name, "vec", vec, batch + (nv,), dtype, device, "one vector per environment")
     return batch, dtype, device, P, mode
 
 
@@ -103,7 +87,7 @@ def _values(name, m, op, ids, dtype, device):
         v = getattr(m, n)
         if tuple(np.shape(v)) != shape:
             raise ValueError(f"{name}: Model.{n} has shape {tuple(np.shape(v))}, expected {shape}")
-        out[n] = v.detach().to(device=device, dtype=dtype).contiguous() if isinstance(v, torch.Tensor) else _upload(m, n, v, dtype, device)
+        out[n] = model_value(m, n, v, dtype, device)
     sm = m.body_subtreemass
     key = (sm.data_ptr(), sm._version, ids) if isinstance(sm, torch.Tensor) else None
     if key is None or _MASS_OK.get(key) is not sm:  # (one read of the P masses; a tensor is read again only after it was written or replaced)
@@ -120,10 +104,6 @@ def _values(name, m, op, ids, dtype, device):
 
 def jacobian_native(name, m, op: int, leaves: dict, values: dict, point, mode, vec, ids: tuple, listed: bool, batch, P, dtype, device):
     """One ``mjh_jacobian`` call on plain tensors."""
-    from . import native
-    from .forward import _stream_and_guard
-    from .ray import _handle
-
     nv = int(m.nv)
     count = P or 1
     tail = ((P,) if P is not None else ()) + ((nv, 3) if vec is None else (3,))
@@ -131,45 +111,20 @@ def jacobian_native(name, m, op: int, leaves: dict, values: dict, point, mode, v
     B = int(math.prod(batch)) if batch else 1
     if B == 0 or nv == 0:
         return [o.zero_() for o in outs]
-    nm = _handle(m, device, dtype)
-    if not hasattr(nm.lib, "mjh_jacobian"):
-        raise RuntimeError(f"{native.LIB_PATH} predates {name} (no mjh_jacobian): rebuild the library")
-    a = native.JacobianArgs()
-    a.op, a.P, a.B = op, count, B
-    keep = []
-
-    def ptr(t):
-        t = t.contiguous()
-        keep.append(t)
-        return t.data_ptr()
-
-    for n, t in list(leaves.items()) + list(values.items()):
-        setattr(a, n, ptr(t))
-    a.body_id = ptr(_device_ids(ids, device))
-    a.body_stride = 1 if listed else 0
+    a = native.ARGS["mjh_jacobian"](op=op, P=count, B=B, body_stride=1 if listed else 0)
+    tensors = dict(leaves, **values, body_id=_device_ids(ids, device), **{f"out{i}": o for i, o in enumerate(outs)})
     if point is not None:
-        a.point = ptr(point.to(device=device, dtype=dtype))
+        tensors["point"] = point.to(device=device, dtype=dtype)
         a.point_env, a.point_q = _strides(mode, count, 3)
     if vec is not None:
-        a.vec = ptr(vec)
-    a.out0 = outs[0].data_ptr()
-    if len(outs) == 2:
-        a.out1 = outs[1].data_ptr()
-    stream, prev = _stream_and_guard(device)
-    try:
-        rc = nm.lib.mjh_jacobian(nm.handle, ctypes.byref(a), ctypes.c_void_p(stream))
-    finally:
-        if prev is not None:
-            torch.cuda.set_device(prev)
-    if rc != 0:
-        raise RuntimeError(f"native {name} failed ({rc}): {nm.lib.mjh_last_error().decode()}")
+        tensors["vec"] = vec
+    bind(a, tensors)
+    call(name, m, "mjh_jacobian", a, device, dtype)
     return outs
 
 
 def _call(name, m, d, op, point, body_id, vec):
-    from .forward import _require_device
-
-    _refuse_tracing(name, d.cdof, point, vec)
+    refuse_tracing(name, d.cdof, point, vec)
     ids, listed = body_id if isinstance(body_id, _Resolved) else _ids(name, "body", body_id, int(m.nbody))
     leaves = dict(cdof=d.cdof, subtree_com=d.subtree_com)
     if op == DOT:
@@ -180,7 +135,7 @@ def _call(name, m, d, op, point, body_id, vec):
         leaves.update(ximat=d.ximat)
     batch, dtype, device, P, mode = plan(name, m, op, leaves, point, vec, ids, listed)
     values = _values(name, m, op, ids, dtype, device) if op in (SUBTREE_COM, ANGMOM) else {}
-    _require_device(device)
+    require_device(device)
     return jacobian_native(name, m, op, leaves, values, point, mode, vec, ids, listed, batch, P, dtype, device)
 
 
@@ -188,7 +143,7 @@ def _object(name, m, d, what, ident, count, pos, bodyid, vec):
     """jac at the gathered position of an object, on its body."""
     from . import support
 
-    _refuse_tracing(name, d.cdof, pos, vec)
+    refuse_tracing(name, d.cdof, pos, vec)
     ids, listed = _ids(name, what, ident, int(count))
     want = tuple(d.cdof.shape[:-2]) + (int(count), 3)
     if tuple(pos.shape) != want:

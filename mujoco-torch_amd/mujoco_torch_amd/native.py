@@ -285,6 +285,11 @@ class JacobianArgs(ctypes.Structure):
         ("out0", ctypes.c_void_p), ("out1", ctypes.c_void_p)]
 
 
+# the entry points that take (handle, args struct, stream): symbol -> the struct (tests/test_abi.py compares every struct with the header)
+ARGS = {"mjh_support": SupportArgs, "mjh_postconstraint": PostconArgs, "mjh_contact_sensors": ContactSensorArgs, "mjh_energy": EnergyArgs,
+        "mjh_integrate": IntegrateArgs, "mjh_jacobian": JacobianArgs}
+
+
 def load_library(path: str | None = None):
     """Loads libmjhip.so (once). Raises if it has not been built: no fallback path exists."""
     global _lib
@@ -316,24 +321,11 @@ def load_library(path: str | None = None):
         lib.mjh_render.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 6 + [ctypes.c_int64, ctypes.POINTER(RenderScene), ctypes.POINTER(RenderParams),
                                                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         lib.mjh_render.restype = ctypes.c_int
-    if hasattr(lib, "mjh_support"):  # (likewise a build from before the support functions)
-        lib.mjh_support.argtypes = [ctypes.c_void_p, ctypes.POINTER(SupportArgs), ctypes.c_void_p]
-        lib.mjh_support.restype = ctypes.c_int
-    if hasattr(lib, "mjh_postconstraint"):  # (likewise a build from before rne_postconstraint / subtree_vel)
-        lib.mjh_postconstraint.argtypes = [ctypes.c_void_p, ctypes.POINTER(PostconArgs), ctypes.c_void_p]
-        lib.mjh_postconstraint.restype = ctypes.c_int
-    if hasattr(lib, "mjh_contact_sensors"):  # (likewise a build from before contact_force / sensor_postconstraint)
-        lib.mjh_contact_sensors.argtypes = [ctypes.c_void_p, ctypes.POINTER(ContactSensorArgs), ctypes.c_void_p]
-        lib.mjh_contact_sensors.restype = ctypes.c_int
-    if hasattr(lib, "mjh_energy"):  # (likewise a build from before energy / the limit and energy sensors)
-        lib.mjh_energy.argtypes = [ctypes.c_void_p, ctypes.POINTER(EnergyArgs), ctypes.c_void_p]
-        lib.mjh_energy.restype = ctypes.c_int
-    if hasattr(lib, "mjh_integrate"):  # (likewise a build from before deriv_smooth_vel / implicit / euler)
-        lib.mjh_integrate.argtypes = [ctypes.c_void_p, ctypes.POINTER(IntegrateArgs), ctypes.c_void_p]
-        lib.mjh_integrate.restype = ctypes.c_int
-    if hasattr(lib, "mjh_jacobian"):  # (likewise a build from before the Jacobian block)
-        lib.mjh_jacobian.argtypes = [ctypes.c_void_p, ctypes.POINTER(JacobianArgs), ctypes.c_void_p]
-        lib.mjh_jacobian.restype = ctypes.c_int
+    for symbol, struct in ARGS.items():
+        if hasattr(lib, symbol):  # (likewise a build from before that entry point)
+            fn = getattr(lib, symbol)
+            fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(struct), ctypes.c_void_p]
+            fn.restype = ctypes.c_int
     if hasattr(lib, "mjh_integrate_plan"):
         lib.mjh_integrate_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         lib.mjh_integrate_plan.restype = ctypes.c_int

@@ -24,12 +24,15 @@ exerts on ``b``'s subtree (body 0 accumulates like any other body).
 
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
 
+from . import native
+from ._postpass import bind, call, check_leaves, check_override, probe, refuse_tracing, require_device
+
 RNE, SUBTREE, SENSORS = 1, 2, 4  # include/mjhip.h MJH_POSTCON_*
+CONTACT_INTS = dict(contact_dim=torch.int32, contact_geom=torch.int64, contact_efc_address=torch.int64)
 
 
 def plan(name: str, m, leaves: dict, qvel, flags: int):
@@ -39,27 +42,10 @@ def plan(name: str, m, leaves: dict, qvel, flags: int):
     tails = dict(qvel=(nv,), qacc=(nv,), cdof=(nv, 6), cdof_dot=(nv, 6), cvel=(nb, 6), cinert=(nb, 10), xipos=(nb, 3), ximat=(nb, 3, 3), subtree_com=(nb, 3),
                  xfrc_applied=(nb, 6), efc_force=(nefc,), contact_pos=(ncon, 3), contact_frame=(ncon, 3, 3), contact_friction=(ncon, 5), contact_dim=(ncon,),
                  contact_geom=(ncon, 2), contact_efc_address=(ncon,), site_xpos=(nsite, 3), site_xmat=(nsite, 3, 3), sensordata=(nsd,))
-    ints = dict(contact_dim=torch.int32, contact_geom=torch.int64, contact_efc_address=torch.int64)
-    cvel = leaves["cvel"]
-    if cvel.dim() < 2 or tuple(cvel.shape[-2:]) != (nb, 6):
-        raise ValueError(f"{name}: cvel has shape {tuple(cvel.shape)}, expected (..., {nb}, 6) for this Model")
-    batch, dtype, device = tuple(cvel.shape[:-2]), cvel.dtype, cvel.device
-    if dtype not in (torch.float64, torch.float32):
-        raise ValueError(f"{name}: unsupported Data dtype {dtype}")
-    if dtype != m.qpos0.dtype:
-        raise ValueError(f"{name}: the Data is {dtype}, the Model {m.qpos0.dtype}: it runs in the model's dtype")
-    for n, t in leaves.items():
-        want = batch + tails[n]
-        if tuple(t.shape) != want and not (len(tails[n]) == 3 and tuple(t.shape) == batch + (tails[n][0], 9)):
-            raise ValueError(f"{name}: {n} has shape {tuple(t.shape)}, expected {want} for a Data of batch shape {batch}")
-        if t.dtype != ints.get(n, dtype) or t.device != device:
-            raise ValueError(f"{name}: {n} is {t.dtype} on {t.device}, expected {ints.get(n, dtype)} on {device}")
+    batch, dtype, device = probe(name, m, "cvel", leaves["cvel"], (nb, 6))
+    check_leaves(name, leaves, tails, batch, dtype, device, 3, CONTACT_INTS)
     if qvel is not None:
-        if not isinstance(qvel, torch.Tensor) or tuple(qvel.shape) != batch + (nv,):
-            raise ValueError(f"{name}: qvel= must have shape {batch + (nv,)} (the velocity the pass ran on, per environment); got "
-                             f"{tuple(qvel.shape) if isinstance(qvel, torch.Tensor) else type(qvel).__name__}")
-        if qvel.dtype != dtype or qvel.device != device:
-            raise ValueError(f"{name}: qvel= is {qvel.dtype} on {qvel.device}, the Data is {dtype} on {device}")
+        check_override(name, "qvel", qvel, batch + (nv,), dtype, device, "the velocity the pass ran on, per environment")
     if flags & SUBTREE:
         sm = m.body_subtreemass
         if tuple(sm.shape) != (nb,) or sm.dtype != dtype or sm.device != device:
@@ -68,13 +54,7 @@ def plan(name: str, m, leaves: dict, qvel, flags: int):
 
 
 def _run(name: str, m, d, qvel, flags: int):
-    from . import native
-    from .forward import _plain, _require_device, _stream_and_guard
-    from .ray import _handle
-
-    if torch.compiler.is_compiling() or not _plain(d.qpos) or (isinstance(qvel, torch.Tensor) and not _plain(qvel)):
-        raise NotImplementedError(f"{name} cannot be used under torch.vmap / torch.compile: there is no operator for it.  Call it on a "
-                                  "batched Data directly (every leading dimension of a leaf is the batch).")
+    refuse_tracing(name, d.qpos, qvel)
     _, _, _, ncon, nefc = m.constraint_sizes_py
     nsd = int(getattr(m, "nsensordata", 0) or 0)
     leaves = dict(cvel=d.cvel, xipos=d.xipos, subtree_com=d.subtree_com)
@@ -93,7 +73,7 @@ def _run(name: str, m, d, qvel, flags: int):
     else:
         flags &= ~SENSORS
     batch, dtype, device = plan(name, m, leaves, qvel, flags)
-    _require_device(device)
+    require_device(device)
     if qvel is not None:
         leaves["qvel"] = qvel
     nb = int(m.nbody)
@@ -108,32 +88,13 @@ def _run(name: str, m, d, qvel, flags: int):
         out.update(sensordata=new(nsd))
     if B == 0 or nb == 0:
         return d.replace(**{k: v.zero_() for k, v in out.items()})
-    nm = _handle(m, device, dtype)
-    if not hasattr(nm.lib, "mjh_postconstraint"):
-        raise RuntimeError(f"{native.LIB_PATH} predates {name} (no mjh_postconstraint): rebuild the library")
-    a = native.PostconArgs()
-    a.flags, a.B = flags, B
-    keep = []
-    for n, t in leaves.items():
-        if t.numel() == 0:
-            continue
-        t = t.contiguous()
-        keep.append(t)
-        setattr(a, "sensordata_in" if n == "sensordata" else n, t.data_ptr())
+    a = native.ARGS["mjh_postconstraint"](flags=flags, B=B)
+    if "sensordata" in leaves:
+        leaves["sensordata_in"] = leaves.pop("sensordata")
     if flags & SUBTREE:
-        sm = m.body_subtreemass.contiguous()
-        keep.append(sm)
-        a.body_subtreemass = sm.data_ptr()
-    for n, t in out.items():
-        setattr(a, n, t.data_ptr())
-    stream, prev = _stream_and_guard(device)
-    try:
-        rc = nm.lib.mjh_postconstraint(nm.handle, ctypes.byref(a), ctypes.c_void_p(stream))
-    finally:
-        if prev is not None:
-            torch.cuda.set_device(prev)
-    if rc != 0:
-        raise RuntimeError(f"native {name} failed ({rc}): {nm.lib.mjh_last_error().decode()}")
+        leaves["body_subtreemass"] = m.body_subtreemass
+    bind(a, dict(leaves, **out))
+    call(name, m, "mjh_postconstraint", a, device, dtype)
     return d.replace(**out)
 
 

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from ._enums import GeomType
+from ._postpass import cached, call, require_device
 
 _MINVAL = 1e-15  # mujoco.mjMINVAL
 _NGROUP = 6  # mujoco.mjNGROUP
@@ -126,18 +127,13 @@ _DEV = {}  # (tables uid, filter key, dtype, device) -> (candidate rows [ncand, 
 
 
 def _device_candidates(m, key, dtype, device):
-    T = m.tables
-    k = (T.uid, key, dtype, device)
-    hit = _DEV.get(k)
-    if hit is None:
-        c = candidates(T.ray, key)
+    def make():
+        c = candidates(m.tables.ray, key)
         rows = np.zeros((len(c["geom"]), 4), dtype=np.int32)
         rows[:, 0], rows[:, 1], rows[:, 2:] = c["geom"], c["type"], c["tri_range"]
-        hit = (torch.tensor(rows, device=device), torch.tensor(c["tri"], dtype=dtype, device=device).contiguous())
-        if len(_DEV) > 256:
-            _DEV.clear()
-        _DEV[k] = hit
-    return hit
+        return (torch.tensor(rows, device=device), torch.tensor(c["tri"], dtype=dtype, device=device).contiguous())
+
+    return cached(_DEV, (m.tables.uid, key, dtype, device), make)
 
 
 # ---- shapes -----------------------------------------------------------------------------------------------------------------
@@ -189,29 +185,13 @@ def check_args(xpos, xmat, pnt, vec):
 
 # ---- the native call --------------------------------------------------------------------------------------------------------
 
-_HANDLES = {}  # (tables uid, device, dtype) -> a NativeModel of that structure: mjh_ray reads only the structure (ngeom, dtype) from it
-
-
-def _handle(m, device, dtype):
-    k = (m.tables.uid, device, dtype)
-    nm = _HANDLES.get(k)
-    if nm is None:
-        from . import native
-
-        if len(_HANDLES) > 64:
-            _HANDLES.clear()
-        nm = _HANDLES[k] = native.get_native_model(m, device, dtype)
-    return nm
-
-
 def ray_native(m, xpos, xmat, pnt, vec, key):
     """One ``mjh_ray`` call on plain tensors (the direct path and the eager body of ``ray_leaves``)."""
     from . import native
-    from .forward import _require_device, _stream_and_guard
 
     out_shape, R, modes = check_args(xpos, xmat, pnt, vec)
     key = filter_key(m.tables.ray, key[2], key[0], key[1])
-    _require_device(xpos.device)
+    require_device(xpos.device)
     dtype, device = xpos.dtype, xpos.device
     if dtype not in (torch.float64, torch.float32):
         raise RuntimeError(f"unsupported Data dtype {dtype}")
@@ -232,21 +212,11 @@ def ray_native(m, xpos, xmat, pnt, vec, key):
     xpos_c, xmat_c = xpos.reshape(B, ng, 3).contiguous(), xmat.reshape(B, ng, 9).contiguous()
     p, pe, pr = _flat(pnt, modes[0], B, R)
     v, ve, vr = _flat(vec, modes[1], B, R)
-    nm = _handle(m, device, dtype)
-    if not hasattr(nm.lib, "mjh_ray"):
-        raise RuntimeError(f"{native.LIB_PATH} predates ray casting (no mjh_ray): rebuild the library")
     cands = native.RayCands(cand.shape[0], ctypes.c_void_p(cand.data_ptr()), ctypes.c_void_p(tri.data_ptr() if tri.numel() else None),
                             ctypes.c_void_p(size.data_ptr()))
-    stream, prev = _stream_and_guard(device)
-    try:
-        rc = nm.lib.mjh_ray(nm.handle, ctypes.c_void_p(xpos_c.data_ptr()), ctypes.c_void_p(xmat_c.data_ptr()), ctypes.c_void_p(p.data_ptr()), pe, pr,
-                            ctypes.c_void_p(v.data_ptr()), ve, vr, B, R, ctypes.byref(cands), ctypes.c_void_p(dist.data_ptr()),
-                            ctypes.c_void_p(geomid.data_ptr()), ctypes.c_void_p(stream))
-    finally:
-        if prev is not None:
-            torch.cuda.set_device(prev)
-    if rc != 0:
-        raise RuntimeError(f"native ray failed ({rc}): {nm.lib.mjh_last_error().decode()}")
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+    call("ray", m, "mjh_ray", (ptr(xpos_c), ptr(xmat_c), ptr(p), pe, pr, ptr(v), ve, vr, B, R, ctypes.byref(cands), ptr(dist), ptr(geomid)), device, dtype,
+         what="ray casting")
     return dist, geomid
 
 

@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from ._enums import GeomType
+from ._postpass import cached, call, require_device
 
 _LIGHT_ROW = 16  # reals per light row (include/mjhip.h mjhRenderScene)
 
@@ -75,23 +76,19 @@ def _scene(m, dtype, device):
     """(candidate rows [ncand, 4] int32, primitive rows, triangles, geom_matid, mat_rgba, light rows) on the device."""
     from .ray import candidates
 
-    T = m.tables
-    k = (T.uid, dtype, device)
-    hit = _DEV.get(k)
-    if hit is None:
+    def make():
+        T = m.tables
         c = candidates(T.ray, (True, (), ()))  # the visible geoms, no filter: render.py:54-56, ray.py's tie-break order, meshes last
         rows = np.zeros((len(c["geom"]), 4), dtype=np.int32)
         rows[:, 0], rows[:, 1], rows[:, 2:] = c["geom"], c["type"], c["tri_range"]
         R = T.render
         nprim = int(np.sum(c["type"] != int(GeomType.MESH)))
         mat = R["mat_rgba"] if len(R["mat_rgba"]) else np.ones((1, 4), dtype=np.float32)
-        hit = dict(cand=torch.tensor(rows, device=device), nprim=nprim, tri=torch.tensor(c["tri"], dtype=dtype, device=device).contiguous(),
-                   matid=torch.tensor(R["geom_matid"], device=device), mat=torch.tensor(mat, device=device).contiguous(),
-                   light=light_rows(R, dtype).to(device).contiguous())
-        if len(_DEV) > 256:
-            _DEV.clear()
-        _DEV[k] = hit
-    return hit
+        return dict(cand=torch.tensor(rows, device=device), nprim=nprim, tri=torch.tensor(c["tri"], dtype=dtype, device=device).contiguous(),
+                    matid=torch.tensor(R["geom_matid"], device=device), mat=torch.tensor(mat, device=device).contiguous(),
+                    light=light_rows(R, dtype).to(device).contiguous())
+
+    return cached(_DEV, (m.tables.uid, dtype, device), make)
 
 
 def _texture_warning(m):
@@ -183,12 +180,10 @@ def check_args(m, leaves):
 def render_native(m, leaves, opts, u8=False):
     """One ``mjh_render`` call on plain tensors (the direct path and the eager body of ``render_leaves``)."""
     from . import native
-    from .forward import _require_device, _stream_and_guard
-    from .ray import _handle
 
     batch = check_args(m, leaves)
     xpos = leaves[0]
-    _require_device(xpos.device)
+    require_device(xpos.device)
     dtype, device = xpos.dtype, xpos.device
     if dtype not in (torch.float64, torch.float32):
         raise RuntimeError(f"unsupported Data dtype {dtype}")
@@ -207,9 +202,6 @@ def render_native(m, leaves, opts, u8=False):
     rgba = rgba.to(device=device, dtype=dtype).contiguous()
     nl = len(m.tables.render["light_type"])
     flat = [t.reshape((B,) + tuple(t.shape[len(batch):])).contiguous() for t in leaves]
-    nm = _handle(m, device, dtype)
-    if not hasattr(nm.lib, "mjh_render"):
-        raise RuntimeError(f"{native.LIB_PATH} predates rendering (no mjh_render): rebuild the library")
     ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else None)
     scene = native.RenderScene(sc["cand"].shape[0], sc["nprim"], ptr(sc["cand"]), ptr(sc["tri"]), ptr(size), ptr(rgba), ptr(sc["matid"]),
                                ptr(sc["mat"]), nl, ptr(sc["light"]))
@@ -223,15 +215,8 @@ def render_native(m, leaves, opts, u8=False):
                                  rgb_f32=int(rgb_dtype(m, dtype, opts) == torch.float32), u8=int(u8), half_w=float(half_w), half_h=float(half_h),
                                  background=(ctypes.c_double * 3)(*bgv), fog_color=(ctypes.c_double * 3)(*fc),
                                  fog_start=fg[3] if fg else 0.0, fog_range=(fg[4] - fg[3]) if fg else 1.0)
-    stream, prev = _stream_and_guard(device)
-    try:
-        rc = nm.lib.mjh_render(nm.handle, ptr(flat[0]), ptr(flat[1]), ptr(flat[2]), ptr(flat[3]), ptr(flat[4]), ptr(flat[5]), B, ctypes.byref(scene),
-                               ctypes.byref(params), ptr(rgb), ptr(depth), ptr(seg), ctypes.c_void_p(stream))
-    finally:
-        if prev is not None:
-            torch.cuda.set_device(prev)
-    if rc != 0:
-        raise RuntimeError(f"native render failed ({rc}): {nm.lib.mjh_last_error().decode()}")
+    call("render", m, "mjh_render", tuple(ptr(t) for t in flat) + (B, ctypes.byref(scene), ctypes.byref(params), ptr(rgb), ptr(depth), ptr(seg)), device, dtype,
+         what="rendering")
     return rgb, depth, seg
 
 

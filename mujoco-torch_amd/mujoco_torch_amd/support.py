@@ -13,12 +13,14 @@ int, a 0-d integer tensor, or P ids (a sequence or a 1-D integer tensor) shared 
 
 from __future__ import annotations
 
-import ctypes
 import math
 from collections.abc import Sequence
 
 import numpy as np
 import torch
+
+from . import native
+from ._postpass import bind, cached, call, require_device
 
 JAC, APPLY_FT, XFRC, MUL_M, SOLVE_M = range(5)  # include/mjhip.h MJH_SUPPORT_*
 _NAMES = ("jac", "apply_ft", "xfrc_accumulate", "mul_m", "solve_m")
@@ -122,13 +124,7 @@ _IDS = {}  # (ids, device) -> int32 device tensor
 
 
 def _device_ids(ids, device):
-    k = (ids, device)
-    t = _IDS.get(k)
-    if t is None:
-        if len(_IDS) > 256:
-            _IDS.clear()
-        t = _IDS[k] = torch.tensor(ids, dtype=torch.int32, device=device)
-    return t
+    return cached(_IDS, (ids, device), lambda: torch.tensor(ids, dtype=torch.int32, device=device))
 
 
 def _strides(mode, count, width):
@@ -143,14 +139,10 @@ def _strides(mode, count, width):
 
 def support_native(m, op: int, leaves, queries, ids: tuple, listed: bool):
     """One ``mjh_support`` call on plain tensors (the direct path and the eager body of ``support_leaves``)."""
-    from . import native
-    from .forward import _require_device, _stream_and_guard
-    from .ray import _handle
-
     batch, count, modes, out_shapes = plan(op, leaves, queries, ids, listed)
     ref = leaves[0]
     dtype, device = ref.dtype, ref.device
-    _require_device(device)
+    require_device(device)
     if dtype not in (torch.float64, torch.float32):
         raise RuntimeError(f"unsupported Data dtype {dtype}")
     for name, t in zip(("cdof", "subtree_com", "xipos", "xfrc_applied") if op != MUL_M and op != SOLVE_M else ("qM/qLD",), leaves):
@@ -165,53 +157,28 @@ def support_native(m, op: int, leaves, queries, ids: tuple, listed: bool):
     B = int(math.prod(batch)) if batch else 1
     if B == 0 or nv == 0:
         return [o.zero_() for o in outs]
-    nm = _handle(m, device, dtype)
-    if not hasattr(nm.lib, "mjh_support"):
-        raise RuntimeError(f"{native.LIB_PATH} predates the support functions (no mjh_support): rebuild the library")
-    a = native.SupportArgs()
-    a.op, a.B = op, B
-    keep = []
-
-    def ptr(t):
-        keep.append(t)
-        return ctypes.c_void_p(t.data_ptr())
-
+    a = native.ARGS["mjh_support"](op=op, B=B)
+    tensors = {f"out{i}": o for i, o in enumerate(outs)}
     if op in (JAC, APPLY_FT, XFRC):
-        a.cdof = ptr(leaves[0].reshape(B, nv, 6).contiguous())
-        a.subtree_com = ptr(leaves[1].reshape(B, nb, 3).contiguous())
+        tensors.update(cdof=leaves[0].reshape(B, nv, 6), subtree_com=leaves[1].reshape(B, nb, 3))
     if op == XFRC:
-        a.xipos = ptr(leaves[2].reshape(B, nb, 3).contiguous())
-        a.xfrc_applied = ptr(leaves[3].reshape(B, nb, 6).contiguous())
+        tensors.update(xipos=leaves[2].reshape(B, nb, 3), xfrc_applied=leaves[3].reshape(B, nb, 6))
     if op in (JAC, APPLY_FT):
         a.P = count
-        a.body_id = ptr(_device_ids(ids, device))
         a.body_stride = 1 if listed else 0
+        tensors.update(body_id=_device_ids(ids, device))
         for name, q, mode in zip(("point", "force", "torque"), queries, modes):
-            q = q.to(device=device, dtype=dtype).contiguous()
-            setattr(a, name, ptr(q))
+            tensors[name] = q.to(device=device, dtype=dtype)
             e, s = _strides(mode, count, 3)
             setattr(a, name + "_env", e)
             setattr(a, name + "_q", s)
     if op in (MUL_M, SOLVE_M):
         a.K = count
-        mat = ptr(leaves[0].reshape(B, nv, nv).contiguous())
-        if op == MUL_M:
-            a.qM = mat
-        else:
-            a.qLD = mat
-        a.vec = ptr(queries[0].to(device=device, dtype=dtype).contiguous())
+        tensors["qM" if op == MUL_M else "qLD"] = leaves[0].reshape(B, nv, nv)
+        tensors["vec"] = queries[0].to(device=device, dtype=dtype)
         a.vec_env, a.vec_k = _strides(modes[0], count, nv)
-    a.out0 = ptr(outs[0])
-    if op == JAC:
-        a.out1 = ptr(outs[1])
-    stream, prev = _stream_and_guard(device)
-    try:
-        rc = nm.lib.mjh_support(nm.handle, ctypes.byref(a), ctypes.c_void_p(stream))
-    finally:
-        if prev is not None:
-            torch.cuda.set_device(prev)
-    if rc != 0:
-        raise RuntimeError(f"native {_NAMES[op]} failed ({rc}): {nm.lib.mjh_last_error().decode()}")
+    bind(a, tensors)
+    call(_NAMES[op], m, "mjh_support", a, device, dtype, what="the support functions")
     return outs
 
 

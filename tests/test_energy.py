@@ -109,7 +109,7 @@ def test_an_environment_of_a_batch_equals_the_same_state_alone(xml, dtype):
 
 
 def test_a_value_only_edit_is_honoured_without_a_new_native_model():
-    from mujoco_torch_amd.ray import _handle
+    from mujoco_torch_amd._postpass import handle as _handle
 
     mc, mx, f = a_pass("humanoid", F64)
     nm = _handle(mx, f.qpos.device, F64)

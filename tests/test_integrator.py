@@ -208,7 +208,7 @@ def test_without_any_term_implicit_advances_with_the_pass_qacc():
 
 
 def test_value_only_edits_are_honoured_without_a_new_native_model():
-    from mujoco_torch_amd.ray import _handle
+    from mujoco_torch_amd._postpass import handle as _handle
 
     c, mx, f = live("integrator_rig_f64")
     nm = _handle(mx, f.qpos.device, F64)

@@ -285,7 +285,7 @@ def test_batches_past_one_launch_are_cut_on_the_host():
 # ---- 4. the model values are the caller's; the input is the caller's ---------------------------------------------------------------------------------
 
 def test_a_value_only_edit_is_honoured_without_a_new_native_model():
-    from mujoco_torch_amd.ray import _handle
+    from mujoco_torch_amd._postpass import handle as _handle
 
     mc, mx, f, T, L = a_pass("humanoid", F64)
     nm = _handle(mx, f.qpos.device, F64)

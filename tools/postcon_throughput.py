@@ -20,7 +20,7 @@ sys.path.insert(0, os.path.join(ROOT, "mujoco-torch_amd"))
 
 import mujoco_torch_amd as mt  # noqa: E402
 from mujoco_torch_amd import native  # noqa: E402
-from mujoco_torch_amd.ray import _handle  # noqa: E402
+from mujoco_torch_amd._postpass import handle as _handle  # noqa: E402
 
 HBM_BYTES_PER_S = 8e12
 POSTCON = 32
