@@ -14,6 +14,9 @@ distance (the reference's ``ray_geom`` / triangle minimum) gives the runner-up d
 either id of a tie.  Rays whose mesh hit lies within 1e-7 (barycentric) of a triangle edge are dropped before R are kept.
 
 ``ray_geom.npz`` holds a table of single-primitive cases against the reference ``ray.ray_geom``.
+``tests/golden/ray_edges/ray_geom_edges.npz`` (``edge_table``; ``python tools/gen_ray_golden.py edges`` writes it alone) holds rows that sit
+exactly on the decision boundaries of the primitives and of a mesh triangle, in a directory of its own: every other ``.npz`` of
+tests/golden/ray/ is a scene case.
 The files live in a directory of their own: tests/golden/*.npz are the step recordings the oracle suites iterate over.
 
 Run:  python tools/gen_ray_golden.py [case ...]
@@ -171,6 +174,8 @@ def main(only=None, out_dir=GOLD):
         np.savez_compressed(path, **store)
         print(f"{case}: {os.path.getsize(path) / 1024:.0f} KB, candidates {cand}, hit ids {np.unique(hits).tolist()}, misses {int(np.sum(hits < 0))}")
     geom_table(ref, out_dir)
+    if not only:
+        edge_table(ref)
 
 
 def one_ray(ref, m64, x64, p, v, cand, filters, be_prim, gtype, lite):
@@ -240,5 +245,159 @@ def geom_table(ref, out_dir):
     print(f"ray_geom: {len(D)} cases, {int(np.sum(np.isinf(D)))} misses")
 
 
+# ---- the exact edge table ---------------------------------------------------------------------------------------------------------
+
+EDGE_GOLD = os.path.join(REPO, "tests", "golden", "ray_edges")
+# one primitive per geom group 0..5 (ray(geomgroup=...) isolates it), and a mesh in group 0 on a body of its own (bodyexclude=0 drops the plane)
+EDGE_XML = """<mujoco model="ray_edges">
+  <compiler meshdir="meshes"/>
+  <asset><mesh name="tetrahedron" file="tetrahedron.stl"/></asset>
+  <default><geom contype="0" conaffinity="0"/></default>
+  <worldbody>
+    <geom name="plane" type="plane" size="1 0.5 0.1" group="0"/>
+    <body name="sphere" pos="0 0 1"><geom name="sphere" type="sphere" size="1.25" group="1"/></body>
+    <body name="capsule" pos="0 0 2"><geom name="capsule" type="capsule" size="0.5 1" group="2"/></body>
+    <body name="ellipsoid" pos="0 0 3"><geom name="ellipsoid" type="ellipsoid" size="0.5 1 0.25" group="3"/></body>
+    <body name="cylinder" pos="0 0 4"><geom name="cylinder" type="cylinder" size="0.5 1" group="4"/></body>
+    <body name="box" pos="0 0 5"><geom name="box" type="box" size="0.5 1 0.25" group="5"/></body>
+    <body name="mesh" pos="0 0 6"><geom name="mesh" type="mesh" mesh="tetrahedron" group="0"/></body>
+  </worldbody>
+</mujoco>"""
+# the tetrahedron's vertices, set by value on the compiled model (the compiler recentres a mesh file's): multiples of 1/4, every face's
+# projected determinant along z a power of two
+EDGE_MESH_VERT = [[-1.0, -1.0, 0.0], [1.0, -1.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]
+PLANE, SPHERE, CAPSULE, ELLIPSOID, CYLINDER, BOX = 0, 2, 3, 4, 5, 6
+_S = {PLANE: (1.0, 0.5, 0.1), SPHERE: (1.25, 0.0, 0.0), CAPSULE: (0.5, 1.0, 0.0), ELLIPSOID: (0.5, 1.0, 0.25), CYLINDER: (0.5, 1.0, 0.0), BOX: (0.5, 1.0, 0.25),
+      MESH: (0.0, 0.0, 0.0)}
+# (type, size or None for the type's own, origin, direction, exact?, what the row sits on).  Coordinates are multiples of 1/4 of magnitude <= 2:
+# dot products need at most 8 bits and b^2 - a c at most 16, so every intermediate up to the final division is exact in float32; the rows
+# flagged exact have a square discriminant and a power-of-two or axis-parallel |vec|^2, so the distance is exact too (edge_table checks
+# the flag: the reference gives the same value in float32 and in float64).
+EDGE_ROWS = [
+    (PLANE, None, (0.25, 0.25, 1), (0, 0, -2), True, "interior"),
+    (PLANE, None, (1, 0, 1), (0, 0, -1), True, "border |p0| == size0"),
+    (PLANE, None, (0, 0.5, 2), (0, 0, -1), True, "border |p1| == size1"),
+    (PLANE, None, (-1, -0.5, 1), (0, 0, -1), True, "corner"),
+    (PLANE, None, (1.25, 0, 1), (0, 0, -1), True, "outside the border"),
+    (PLANE, None, (0, 0, 1), (1, 0, -1), True, "oblique onto the border"),
+    (PLANE, None, (0, 0, 0), (0, 0, -1), True, "origin on the plane"),
+    (PLANE, None, (0, 0, -1), (0, 0, -1), True, "origin behind the plane"),
+    (PLANE, None, (0, 0, -1), (0, 0, 1), True, "from behind"),
+    (PLANE, None, (0, 0, 1), (1, 0, 0), True, "vec[2] == 0"),
+    (PLANE, None, (0, 0, 1), (0, 1, -1), True, "vec[0] == 0"),
+    (PLANE, None, (0, 0, 1), (0, 0, 0), True, "zero vector"),
+    (PLANE, None, (0, 0, 0), (0, 0, 0), True, "zero vector on the plane"),
+    (PLANE, (0, 0, 0.1), (2, -2, 1), (0, 0, -1), True, "size 0: infinite"),
+    (PLANE, (0, 0.5, 0.1), (2, 0.5, 1), (0, 0, -1), True, "size0 0, border of size1"),
+    (SPHERE, None, (-2, 0.75, 0), (1, 0, 0), True, "vec[1] == vec[2] == 0"),
+    (SPHERE, None, (0.75, -2, 0), (0, 1, 0), True, "vec[0] == vec[2] == 0"),
+    (SPHERE, None, (0, 0.75, -2), (0, 0, 1), True, "vec[0] == vec[1] == 0"),
+    (SPHERE, None, (-2, 1.25, 0), (1, 0, 0), True, "tangent: det == 0"),
+    (SPHERE, None, (-1.25, 0, 0), (1, 0, 0), True, "origin on the surface"),
+    (SPHERE, None, (0, 0.75, 0), (2, 0, 0), True, "origin inside"),
+    (SPHERE, None, (-2, -2, 0), (1, 1, 0), False, "diagonal, vec[2] == 0"),
+    (SPHERE, None, (2, 0, 0), (0, 0, 0), True, "zero vector outside"),
+    (SPHERE, None, (0, 0, 0), (0, 0, 0), True, "zero vector inside"),
+    (CAPSULE, None, (-2, 0, 0.5), (1, 0, 0), True, "side"),
+    (CAPSULE, None, (-2, 0, 1), (1, 0, 0), True, "seam z == +size1"),
+    (CAPSULE, None, (0, -2, -1), (0, 1, 0), True, "seam z == -size1"),
+    (CAPSULE, None, (-2, 0, 1.5), (1, 0, 0), True, "tangent to the cap"),
+    (CAPSULE, None, (0, 0, 2), (0, 0, -1), True, "cap from above, vec[0] == vec[1] == 0"),
+    (CAPSULE, None, (0, 0, -2), (0, 0, 2), True, "cap from below"),
+    (CAPSULE, None, (0, 0, 0), (1, 0, 0), True, "origin inside"),
+    (CAPSULE, None, (-0.5, 0, 0), (1, 0, 0), True, "origin on the surface"),
+    (CAPSULE, None, (-2, 0.5, 0), (1, 0, 0), True, "tangent to the side: det == 0"),
+    (CAPSULE, None, (-2, 0, -2), (1, 0, 1), False, "oblique through the seam"),
+    (CAPSULE, None, (0, 0, 0), (0, 0, 0), True, "zero vector inside"),
+    (CAPSULE, None, (2, 0, 0), (0, 0, 0), True, "zero vector outside"),
+    (ELLIPSOID, None, (-2, 0, 0), (1, 0, 0), True, "along x"),
+    (ELLIPSOID, None, (0, -2, 0), (0, 1, 0), True, "along y"),
+    (ELLIPSOID, None, (0, 0, -2), (0, 0, 1), True, "along z"),
+    (ELLIPSOID, None, (-2, 1, 0), (1, 0, 0), True, "tangent: det == 0"),
+    (ELLIPSOID, None, (-0.5, 0, 0), (1, 0, 0), True, "origin on the surface"),
+    (ELLIPSOID, None, (0, 0, 0), (1, 0, 0), True, "origin inside"),
+    (ELLIPSOID, None, (-2, -2, 0), (1, 1, 0), False, "diagonal"),
+    (ELLIPSOID, None, (0, 0, 0), (0, 0, 0), True, "zero vector inside"),
+    (ELLIPSOID, None, (2, 0, 0), (0, 0, 0), True, "zero vector outside"),
+    (CYLINDER, None, (-2, 0, 0.5), (1, 0, 0), True, "side"),
+    (CYLINDER, None, (0.5, 0, 2), (0, 0, -1), True, "rim p0^2 + p1^2 == r^2, top"),
+    (CYLINDER, None, (0, -0.5, 2), (0, 0, -1), True, "rim, top, on y"),
+    (CYLINDER, None, (0.5, 0, -2), (0, 0, 1), True, "rim, bottom"),
+    (CYLINDER, None, (-0.5, 0, 2), (1, 0, -1), True, "oblique onto the rim"),
+    (CYLINDER, None, (0.75, 0, 2), (0, 0, -1), True, "outside the rim"),
+    (CYLINDER, None, (-2, 0, 1), (1, 0, 0), True, "side at z == size1"),
+    (CYLINDER, None, (0, 0, 0), (0, 0, 1), True, "origin inside, along z"),
+    (CYLINDER, None, (0, 0, 0), (1, 0, 0), True, "origin inside, vec[2] == 0"),
+    (CYLINDER, None, (0, 0, 1), (0, 0, -1), True, "origin on the cap"),
+    (CYLINDER, None, (-2, 0.5, 0), (1, 0, 0), True, "tangent to the side: det == 0"),
+    (CYLINDER, None, (0, 0, 0), (0, 0, 0), False, "zero vector inside: a hit at 1 / mjMINVAL"),
+    (CYLINDER, None, (2, 0, 0), (0, 0, 0), True, "zero vector outside"),
+    (BOX, None, (-2, 0.25, 0), (1, 0, 0), True, "face"),
+    (BOX, None, (-2, 1, 0), (1, 0, 0), True, "edge"),
+    (BOX, None, (-2, 1, 0.25), (1, 0, 0), True, "corner"),
+    (BOX, None, (-2, 1.25, 0), (1, 0, 0), True, "outside the edge"),
+    (BOX, None, (-1.5, 0, 0), (1, 1, 0), True, "diagonal onto an edge"),
+    (BOX, None, (0, -2, 0), (0, 1, 0), True, "vec[0] == vec[2] == 0"),
+    (BOX, None, (0, 0, -2), (0, 0, 1), True, "vec[0] == vec[1] == 0"),
+    (BOX, None, (0, 0, 0), (1, 0, 0), True, "origin inside"),
+    (BOX, None, (-0.5, 0, 0), (1, 0, 0), True, "origin on the surface"),
+    (BOX, None, (0.25, 0, 0), (0, 0, 0), False, "zero vector inside: a hit at 0.25 / mjMINVAL"),
+    (BOX, None, (2, 0, 0), (0, 0, 0), True, "zero vector outside"),
+    (MESH, None, (0, -0.5, 2), (0, 0, -1), True, "face interior"),
+    (MESH, None, (-0.5, -0.5, 2), (0, 0, -1), True, "shared edge A-D"),
+    (MESH, None, (0, 0, 2), (0, 0, -2), True, "vertex D"),
+    (MESH, None, (0, -1, 2), (0, 0, -1), True, "base edge A-B"),
+    (MESH, None, (-1, -1, 2), (0, 0, -1), True, "base vertex A"),
+    (MESH, None, (0.25, -1.25, 2), (0, 0, -1), True, "outside"),
+    (MESH, None, (0, -0.25, 0.25), (0, 0, 1), True, "origin inside"),
+    (MESH, None, (0, -0.5, 0), (0, 0, 1), True, "origin on the base"),
+    (MESH, None, (0, -0.5, -1), (0, 0, 0), False, "zero vector below the base: a hit at 4 / mjMINVAL"),
+]
+# proper signed permutations: the geom frames the GPU test poses the geoms in (a ray through one is the same exact arithmetic)
+EDGE_FRAMES = [np.eye(3), np.array([[0.0, -1, 0], [1, 0, 0], [0, 0, 1]]), np.array([[0.0, 0, 1], [1, 0, 0], [0, 1, 0]]), np.array([[-1.0, 0, 0], [0, 0, 1], [0, 1, 0]])]
+
+
+def edge_table(ref=None, out_dir=EDGE_GOLD):
+    """Rows exactly on the decision boundaries, recorded from the reference's ray_geom (its _ray_triangle over the tetrahedron's faces for the mesh)."""
+    import mujoco_torch_amd as mt
+
+    ref = ref or ref_harness.load()
+    os.makedirs(out_dir, exist_ok=True)
+    lite = mt.mjcf.from_xml_string(EDGE_XML, base_dir=os.path.dirname(mt.test_data_path("ant.xml")))
+    face = np.asarray(lite.mesh_face).reshape(-1, 3)
+    assert np.asarray(lite.mesh_vert).reshape(-1, 3).shape == (4, 3) and face.shape == (4, 3)
+    tri = np.array(EDGE_MESH_VERT)[face]  # [4, 3, 3]
+
+    def ref_dist(t, size, p, v, dt):
+        size, p, v = (torch.tensor(np.asarray(x, dtype=np.float64), dtype=dt) for x in (size, p, v))
+        if t != MESH:
+            return float(ref.ray.ray_geom(size, p, v, t))
+        b, c = ref.math.orthogonals(ref.math.normalize(v))
+        basis = torch.stack([b, c]).T
+        return min(float(ref.ray._ray_triangle(torch.tensor(tri[k], dtype=dt), p, v, basis)) for k in range(len(tri)))
+
+    T, S, P, V, D, X, N, XP, XM = [], [], [], [], [], [], [], [], []
+    rng = np.random.RandomState(5)
+    for i, (t, size, p, v, exact, note) in enumerate(EDGE_ROWS):
+        size = _S[t] if size is None else size
+        d64, d32 = ref_dist(t, size, p, v, torch.float64), ref_dist(t, size, p, v, torch.float32)
+        assert np.isinf(d64) == np.isinf(d32), (note, d64, d32)
+        assert not exact or d64 == d32, f"{note}: flagged exact, but the reference gives {d64!r} in float64 and {d32!r} in float32"
+        T.append(t); S.append(size); P.append(p); V.append(v); D.append(d64); X.append(exact); N.append(note)
+        XP.append(rng.randint(-8, 9, 3) / 4.0); XM.append(EDGE_FRAMES[i % len(EDGE_FRAMES)])
+    meta = dict(xml=EDGE_XML, reference="ray.ray_geom, float64, in the geom frame; type 7: the minimum of ray._ray_triangle over the tetrahedron's faces, "
+                "basis math.orthogonals(math.normalize(vec)); exact: float64 and float32 give the same value", torch=torch.__version__, notes=N,
+                frames="geom_xpos / geom_xmat to pose the row's geom with: pnt_world = xpos + xmat @ pnt, vec_world = xmat @ vec")
+    np.savez_compressed(os.path.join(out_dir, "ray_geom_edges.npz"), type=np.array(T), size=np.array(S, dtype=np.float64), pnt=np.array(P, dtype=np.float64),
+                        vec=np.array(V, dtype=np.float64), dist=np.array(D), exact=np.array(X), geom_xpos=np.array(XP), geom_xmat=np.array(XM),
+                        mesh_vert=np.array(EDGE_MESH_VERT), meta=np.array(json.dumps(meta)))
+    for t, n, d, x in zip(T, N, D, X):
+        print(f"  type {t} {n}: {d!r}{'' if x else ' (not exact)'}")
+    print(f"ray_geom_edges: {len(D)} rows, {int(np.sum(np.isinf(D)))} misses, {int(np.sum(X))} exact")
+
+
 if __name__ == "__main__":
-    main(sys.argv[1:] or None)
+    if sys.argv[1:] == ["edges"]:
+        edge_table()
+    else:
+        main(sys.argv[1:] or None)
