@@ -1238,7 +1238,7 @@ struct Env {
       }
     }
     if (!(DEFER && W > 16 && M.kv_defer)) frame_stores();  // (fused with the velocity stage: they go out in front of its LDS-only sweep, see velocity())
-    if constexpr (XK) if (com_first) { com_pos<DEFER>(); wave_sync(); }
+    if constexpr (XK) if (com_first) { com_pos<DEFER, KEEPG>(); wave_sync(); }
     // normalised free / ball quaternions are written back into qpos (smooth.py:60-70); one lane per joint
     for (int j = l; j < M.njnt; j += W) {
       const int t = M.jnt_type[j], qa = M.jnt_qposadr[j];
@@ -1319,8 +1319,49 @@ struct Env {
     STAMP(4);
   }
 
+  // ---- batched loop forms (BATCH: compiled into the whole-pass kernel only, like KEEPG) -----------------------------------------------------------
+  // The whole-pass kernel is one wave's dependent chain, and in the rolled table-driven loops every trip paid a full memory round trip: a table entry, then the LDS operand it
+  // addresses, then one addition.  The BATCH forms request a loop's table entries for all of a lane's trips before the first trip, and the LDS operands of a chunk of addends before the
+  // chunk's first addition.  The additions are the same additions on the same values in the same order: lanes past their range skip an addend by predication (no padding with zeros).
+  // sum of src[NC * d] for d = end - 1 down to b, in that order, SUB_CH operands in flight (addresses past the range are clamped to b: a valid read whose value is not added; SUB_CH = 1: the plain loop)
+  template <int NC, int SUB_CH>
+  __device__ __forceinline__ static REAL subtree_sum_chunked(const REAL* src, int b, int end) {
+    REAL acc = 0;
+    for (int d = end - 1; d >= b; d -= SUB_CH) {
+      REAL v[SUB_CH];
+#pragma unroll
+      for (int c = 0; c < SUB_CH; c++) { const int dd = d - c; v[c] = src[NC * (dd > b ? dd : b)]; }
+#pragma unroll
+      for (int c = 0; c < SUB_CH; c++) acc = (d - c >= b) ? acc + v[c] : acc;
+    }
+    return acc;
+  }
+  // component k of body b = w / NC, w = l, l + W, ...: st(w, b, k, the subtree sum of src's component k over b's subtree); a body for which skip(b) holds gets an empty sum.
+  // MAXT trips have their subtree ends in registers (nbody <= 32 at 32 lanes); trips past them read the table as before.  Measured per site (profiles/r07/notes.md): chunks of 4 pay for crb and cfrc, none for com_pos.
+  template <int NC, int MAXT, int SUB_CH, typename SKIP, typename ST>
+  __device__ __forceinline__ void subtree_sums_batched(const REAL* src, int nb, SKIP&& skip, ST&& st) {
+    const int l = lane_here(), n = nb * NC;
+    const int* const ends_tab = M.body_subtree_end;
+    int ends[MAXT];
+#pragma unroll
+    for (int t = 0; t < MAXT; t++) { const int w = l + t * W; ends[t] = w < n ? ends_tab[w / NC] : 0; }
+#pragma unroll
+    for (int t = 0; t < MAXT; t++) {
+      if (t * W >= n) break;  // (uniform)
+      const int w = l + t * W;
+      if (w < n) {
+        const int b = w / NC, k = w - NC * b;
+        st(w, b, k, subtree_sum_chunked<NC, SUB_CH>(src + k, b, skip(b) ? b : ends[t]));
+      }
+    }
+    for (int w = l + MAXT * W; w < n; w += W) {
+      const int b = w / NC, k = w - NC * b;
+      st(w, b, k, subtree_sum_chunked<NC, SUB_CH>(src + k, b, skip(b) ? b : ends_tab[b]));
+    }
+  }
+
   // ---- com_pos (smooth.py:210-288) --------------------------------------------------------------------------------------------------------------
-  template <bool DEFER = false>
+  template <bool DEFER = false, bool BATCH = false>
   __device__ __forceinline__ void com_pos() {
     const int l = lane_here();
     const int nb = M.nbody;
@@ -1328,12 +1369,48 @@ struct Env {
     // the per-body terms first (one global read of the mass per term, staged where cinert will be written later), so the
     // subtree loops below run on LDS only
     REAL* term = S.cinert();
+    // BATCH: what the inert_com and cdof loops behind the sums read of the model for the lane's first body and joint is requested here, and the joint's root behind the first loop
+    // (joint -> body -> root is a chain of two table reads): the round trips run under the subtree sums
+    int rid0 = 0, jb0 = 0, jt0 = 0, jd0 = 0, jrid0 = 0;
+    REAL mass0 = 0, inr0[3] = {0, 0, 0};
+    if constexpr (BATCH) {
+      if (l < nb) {
+        rid0 = M.body_rootid[l]; mass0 = M.body_mass[l];
+#pragma unroll
+        for (int i = 0; i < 3; i++) inr0[i] = M.body_inertia[3 * l + i];
+      }
+      if (l < M.njnt) { jb0 = M.jnt_bodyid[l]; jt0 = M.jnt_type[l]; jd0 = M.jnt_dofadr[l]; }
+    }
+    if constexpr (BATCH) {
+      constexpr int MT = 4;  // (32 bodies at 32 lanes)
+      const REAL* const mtab = M.body_mass;
+      const REAL* const xip = S.xipos();
+      REAL ms[MT];
+#pragma unroll
+      for (int t = 0; t < MT; t++) ms[t] = l + t * W < nb * 4 ? mtab[(l + t * W) >> 2] : (REAL)0;
+#pragma unroll
+      for (int t = 0; t < MT; t++) {
+        const int w = l + t * W, b = w >> 2, k = w & 3;
+        if (w < nb * 4) term[w] = (k < 3) ? xip[3 * b + k] * ms[t] : ms[t];
+      }
+      for (int w = l + MT * W; w < nb * 4; w += W) {
+        const int b = w >> 2, k = w & 3;
+        const REAL mass = mtab[b];
+        term[w] = (k < 3) ? xip[3 * b + k] * mass : mass;
+      }
+    } else
     for (int w = l; w < nb * 4; w += W) {
       const int b = w >> 2, k = w & 3;
       const REAL mass = M.body_mass[b];
       term[w] = (k < 3) ? S.xipos()[3 * b + k] * mass : mass;
     }
+    if constexpr (BATCH) if (l < M.njnt) jrid0 = M.body_rootid[jb0];
     wave_sync();
+    if constexpr (BATCH) {
+      REAL* const sp = S.sub_pos();
+      REAL* const sm = S.sub_mass();
+      subtree_sums_batched<4, 4, 1>(term, nb, [](int) { return false; }, [&](int, int b, int k, REAL acc) { if (k < 3) sp[3 * b + k] = acc; else sm[b] = acc; });
+    } else
     for (int w = l; w < nb * 4; w += W) {
       const int b = w >> 2, k = w & 3;
       const int end = M.body_subtree_end[b];
@@ -1351,16 +1428,17 @@ struct Env {
     wave_sync();
     STAMP(5);
     for (int b = l; b < nb; b += W) {  // inert_com :236-243
-      const REAL* rc = S.subtree_com() + 3 * M.body_rootid[b];
+      const bool pre = BATCH && b == l;  // (the first trip's entries are in registers)
+      const REAL* rc = S.subtree_com() + 3 * (pre ? rid0 : M.body_rootid[b]);
       const REAL off[3] = {S.xipos()[3 * b] - rc[0], S.xipos()[3 * b + 1] - rc[1], S.xipos()[3 * b + 2] - rc[2]};
-      const REAL mass = M.body_mass[b];
+      const REAL mass = pre ? mass0 : M.body_mass[b];
       REAL xi[9];  // (a register copy either way: a pointer that may address a private array OR the arena would put the array in scratch memory)
       if (M.lds_diet) { REAL q_[4]; quat_mul(S.xquat() + 4 * b, M.body_iquat + 4 * b, q_); quat_to_mat(q_, xi); }  // support.local_to_global's orientation half, as the kinematics formed it
       else {
 #pragma unroll
         for (int i = 0; i < 9; i++) xi[i] = S.ximat()[9 * b + i];
       }
-      const REAL* inr = M.body_inertia + 3 * b;
+      const REAL inr[3] = {pre ? inr0[0] : M.body_inertia[3 * b], pre ? inr0[1] : M.body_inertia[3 * b + 1], pre ? inr0[2] : M.body_inertia[3 * b + 2]};
       const REAL h[3][3] = {{0, -off[2], off[1]}, {off[2], 0, -off[0]}, {-off[1], off[0], 0}};
       REAL I[3][3];
 #pragma unroll
@@ -1379,9 +1457,10 @@ struct Env {
       ci[6] = off[0] * mass; ci[7] = off[1] * mass; ci[8] = off[2] * mass; ci[9] = mass;
     }
     for (int j = l; j < M.njnt; j += W) {  // cdof_fn :250-273
-      const int b = M.jnt_bodyid[j], t = M.jnt_type[j];
-      int d = M.jnt_dofadr[j];
-      const REAL* rc = S.subtree_com() + 3 * M.body_rootid[b];
+      const bool pre = BATCH && j == l;
+      const int b = pre ? jb0 : M.jnt_bodyid[j], t = pre ? jt0 : M.jnt_type[j];
+      int d = pre ? jd0 : M.jnt_dofadr[j];
+      const REAL* rc = S.subtree_com() + 3 * (pre ? jrid0 : M.body_rootid[b]);
       const REAL off[3] = {rc[0] - S.xanchor()[3 * j], rc[1] - S.xanchor()[3 * j + 1], rc[2] - S.xanchor()[3 * j + 2]};
       if (t == JNT_FREE || t == JNT_BALL) {
         if (t == JNT_FREE) {
@@ -1417,7 +1496,7 @@ struct Env {
 
   // ---- crb + make_m + factor_m (smooth.py:291-332, support.make_m :50-80) ------------------------------------------------------------
   // MAXN: the largest nv the calling instantiation serves (the register Cholesky variants for more rows are not compiled: they would set the kernel's register allocation without ever running)
-  template <bool FUSED = false, int MAXN = (W == 16 ? 16 : 32)>
+  template <bool FUSED = false, int MAXN = (W == 16 ? 16 : 32), bool BATCH = false>
   __device__ __forceinline__ void crb_factor() {
     const int l = lane_here();
     const int nb = M.nbody, nv = M.nv;
@@ -1430,6 +1509,10 @@ struct Env {
     }
     wave_sync();
     STAMP(11);
+    if constexpr (BATCH) {
+      REAL* const crb = S.crb();
+      subtree_sums_batched<10, 10, 4>(S.cinert(), nb, [](int b) { return b == 0; }, [&](int w, int, int, REAL acc) { crb[w] = acc; });  // crb[0] = 0 (smooth.py:300-301)
+    } else
     for (int w = l; w < nb * 10; w += W) {
       const int b = w / 10, k = w - 10 * b;
       REAL acc = 0;
@@ -1449,6 +1532,41 @@ struct Env {
     // slot table (each address stored exactly once, coalesced).
     for (int w = l; w < (nv * (nv + 1)) / 2; w += W) S.qMp()[w] = 0;
     wave_sync();
+    if constexpr (BATCH) {
+      // every trip's pair code first, then the armature of the diagonal ones, then the dot products: two table round trips for the loop instead of two per trip.  The dot products of
+      // two trips form one block, so that the second one's LDS operands are in flight under the first; lanes past the pair count compute on pair (0, 0) and store nothing.
+      constexpr int QT = 14;  // trips with their codes in registers: 28 dofs on one chain are 406 pairs, 13 trips at 32 lanes
+      const int np = M.nqmpair;
+      const int* const ptab = M.qm_pair;
+      const REAL* const atab = M.dof_armature;
+      const REAL* const cc = S.crb_cdof();
+      const REAL* const cd = S.cdof();
+      REAL* const qmp = S.qMp();
+      int pk[QT];
+      REAL arm[QT];
+#pragma unroll
+      for (int t = 0; t < QT; t++) pk[t] = l + t * W < np ? ptab[l + t * W] : 0;
+#pragma unroll
+      for (int t = 0; t < QT; t++) arm[t] = (l + t * W < np && (pk[t] >> 8) == (pk[t] & 0xff)) ? atab[pk[t] >> 8] : (REAL)0;
+#pragma unroll
+      for (int t = 0; t < QT; t++) {
+        if (!(t & 1) && t * W >= np) break;  // (uniform, once per two trips)
+        const int i = pk[t] >> 8, j = pk[t] & 0xff;
+        REAL s = 0;
+#pragma unroll
+        for (int k = 0; k < 6; k++) s += cc[6 * i + k] * cd[6 * j + k];
+        if (i == j) s = s + arm[t];
+        if (l + t * W < np) qmp[tri_at<true>(i, j, nv)] = s;
+      }
+      for (int w = l + QT * W; w < np; w += W) {
+        const int p = ptab[w], i = p >> 8, j = p & 0xff;
+        REAL s = 0;
+#pragma unroll
+        for (int k = 0; k < 6; k++) s += cc[6 * i + k] * cd[6 * j + k];
+        if (i == j) s = s + atab[i];
+        qmp[tri_at<true>(i, j, nv)] = s;
+      }
+    } else
     for (int w = l; w < M.nqmpair; w += W) {
       const int pk = M.qm_pair[w], i = pk >> 8, j = pk & 0xff;  // j <= i, and j is an ancestor-or-self dof of i
       REAL s = 0;
@@ -1466,6 +1584,27 @@ struct Env {
       REAL* gM = out.qM + e * nv * nv;
       // (entry (i, j) is slot (max, min) of the packed copy, whose structurally zero entries hold the +0 they were initialised with: no table read per
       // pass -- behind the previous pass's stores each one waited for them to land, twelve times for the humanoid)
+      if constexpr (BATCH) {
+        // (i, j) advances by W = qW * nv + rW per trip instead of a split per trip, and the packed entries of ROW_CH trips are read ahead of their stores
+        constexpr int ROW_CH = 4;
+        const int nn = nv * nv;
+        const REAL* const qmp = S.qMp();
+        int qW, rW, i, j;
+        split_index(W, nv, M.inv_nv, qW, rW);
+        split_index(l, nv, M.inv_nv, i, j);
+        for (int w0 = l; w0 < nn; w0 += ROW_CH * W) {
+          REAL v[ROW_CH];
+#pragma unroll
+          for (int c = 0; c < ROW_CH; c++) {
+            const int hi = i > j ? i : j, lo = i > j ? j : i;
+            v[c] = qmp[w0 + c * W < nn ? (hi * (hi + 1)) / 2 + lo : 0];
+            i += qW; j += rW;
+            if (j >= nv) { j -= nv; i++; }
+          }
+#pragma unroll
+          for (int c = 0; c < ROW_CH; c++) if (w0 + c * W < nn) gM[w0 + c * W] = v[c];
+        }
+      } else
       for (int w = l; w < nv * nv; w += W) {
         int i, j;
         split_index(w, nv, M.inv_nv, i, j);
@@ -2332,7 +2471,7 @@ struct Env {
   }
 
   // ---- transmission + _velocity (smooth.py:535-591, forward.py:87-99, smooth.com_vel :385-424, passive.py:80-200, smooth.rne :427-467) ----------
-  template <bool FLUID, bool FUSED = false, bool DEFER = false>
+  template <bool FLUID, bool FUSED = false, bool DEFER = false, bool BATCH = false>
   __device__ __forceinline__ void velocity() {
     const int l = lane_here();
     const int nv = M.nv, nb = M.nbody, nu = M.nu;
@@ -2745,6 +2884,10 @@ struct Env {
         S.qfrc_bias()[d] = s;
       }
     } else {
+    if constexpr (BATCH) {
+      REAL* const cfrc = S.cfrc();
+      subtree_sums_batched<6, 6, 4>(S.cacc(), nb, [](int) { return false; }, [&](int w, int, int, REAL acc) { cfrc[w] = acc; });
+    } else
     for (int w = l; w < nb * 6; w += W) {  // subtree sums of the body forces
       const int b = w / 6, k = w - 6 * b;
       const int end = M.body_subtree_end[b];
@@ -3685,7 +3828,7 @@ struct Env {
     STAMP(1);
     const bool com_first = XK && (__builtin_popcount((unsigned)blockIdx.x & (unsigned)KA.xswap_k) & 1) != 0;
     kinematics<DEFER, KEEPG, XK>(KA.rk_stage <= 0, com_first);
-    if (!com_first) com_pos<DEFER>();
+    if (!com_first) com_pos<DEFER, KEEPG>();
   }
   __device__ __forceinline__ void run_crb() { crb_factor<false>(); }
   __device__ __forceinline__ void run_con() {
@@ -3918,10 +4061,10 @@ struct Env {
     wave_sync();
     run_sol2<NMAX, RPL, false, true, ONE>(&pre, &con);
   }
-  template <bool FLUID, bool FUSED = false, bool DEFER = false>
+  template <bool FLUID, bool FUSED = false, bool DEFER = false, bool BATCH = false>
   __device__ __forceinline__ void run_vel() {
     STAMP0();
-    velocity<FLUID, FUSED, DEFER>();
+    velocity<FLUID, FUSED, DEFER, BATCH>();
     if (KA.stages & 0x60) actuation<FLUID>();
     velocity_stores<DEFER>();
   }
@@ -5065,19 +5208,19 @@ __global__ void __launch_bounds__(MJH_WAVE, (sol2_waves<REAL, NMAX, RPL, WT>()))
         // every wave of the second requesting its inputs at the same moment.  Here an environment's wave goes straight on: what the second half reads of the first
         // (geom frames, subtree_com, cdof, the factor, qM, qfrc_smooth, the normalised qpos) it reads back from the leaves THIS wave has just stored -- behind a
         // release / acquire pair at the scope of its own CU -- through the arena layout of the second half.
-        E.template run_kin<false, true>();
+        E.template run_kin<false, true>();  // (KEEPG: with the batched loop forms, as the two stages below)
         wave_sync();
         REAL h_qv_early = 0;  // (velocity first: qvel sits in the overlay the crb stage writes over -- lifted before it)
         if (!swap_cv) {
-          E.template crb_factor<true, NMAX>();
+          E.template crb_factor<true, NMAX, true>();
           wave_sync();
-          E.template run_vel<false, true>();
+          E.template run_vel<false, true, false, true>();
         } else {
-          E.template run_vel<false, true>();
+          E.template run_vel<false, true, false, true>();
           wave_sync();
           { const int l_ = (int)(threadIdx.x & (W - 1)); h_qv_early = l_ < K.M.nv ? E.S.qvel()[l_] : (REAL)0; }
           wave_sync();
-          E.template crb_factor<true, NMAX>();
+          E.template crb_factor<true, NMAX, true>();
           wave_sync();
         }
         if (K.M.all_handoff) {
