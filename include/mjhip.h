@@ -108,6 +108,7 @@ extern "C" {
 #define MJH_KERNEL_JACOBIAN_DOT_VEC 41
 #define MJH_KERNEL_JACOBIAN_SUBTREE_COM_VEC 42
 #define MJH_KERNEL_JACOBIAN_ANGMOM_VEC 43
+#define MJH_KERNEL_QUADRIC 44    /* plane-ellipsoid / plane-cylinder narrow phase (one lane per (environment, pair))   */
 
 /* pair-function ids of the static collision table (collision_driver.py:106-125) */
 #define MJH_FN_PLANE_SPHERE 0
@@ -119,6 +120,11 @@ extern "C" {
 #define MJH_FN_SPHERE_CONVEX 6
 #define MJH_FN_CAPSULE_CONVEX 7
 #define MJH_FN_CONVEX_CONVEX 8
+/* ids from MJH_FN_PLANE_CONVEX up are narrow-phased by kernels of their own between the kinematics and the constraint stage, which picks their
+ * contacts up from the contact leaves (or, with max_contact_points, from the candidate arrays of the workspace): 5..8 by MJH_KERNEL_CONVEX, 9..10
+ * by MJH_KERNEL_QUADRIC.  The reference has no cylinder / ellipsoid pair beyond these two outside its gradient-descent SDF functions. */
+#define MJH_FN_PLANE_ELLIPSOID 9 /* collision_primitive.py:77-85, 1 contact   */
+#define MJH_FN_PLANE_CYLINDER 10 /* collision_primitive.py:88-169, 3 contacts */
 #define MJH_MAX_PAIR_CONTACTS 4
 
 /* ---- model description (host arrays; copied into a device blob by mjh_model_create) ---- */
@@ -207,7 +213,7 @@ extern "C" {
   X(act_trnid)      /* nu: joint id, or tendon id for tendon transmissions (act_trntype 3) */    \
   X(lim_ball_jnt)   /* nlb: joint id of each ball-joint limit row (constraint.py:299-335); these rows precede the slide / hinge ones */ \
   X(lim_jnt)        /* nl: joint id of each slide/hinge limit row, reference row order */        \
-  X(pair_fn)        /* npair: MJH_FN_* */                                                        \
+  X(pair_fn)        /* npair: MJH_FN_* (0..10) */                                                \
   X(pair_geom1)     /* npair */                                                                  \
   X(pair_geom2)     /* npair */                                                                  \
   X(pair_ncon)      /* npair */                                                                  \
@@ -802,7 +808,7 @@ void mjh_debug_set_stamps(void* dev_ptr);
  * (an mjh_energy call with MJH_ENERGY_POS | MJH_ENERGY_VEL): per environment, qpos, qvel, xipos, ten_length and qM once, the two energies written.  MJH_KERNEL_INTEGRATE
  * (an mjh_integrate call for implicit: QDERIV | IMPLICIT | STATE): per environment, the leaves that call reads once (qM in full), qpos, qvel, act and time written.  MJH_KERNEL_JACOBIAN_* (an mjh_jacobian call): per environment
  * for one query, the dof rows and the body rows the operation reads (DOT: cvel and cdof_dot too; the subtree operations: xipos, ximat for ANGMOM) and the matrices,
- * or, for the *_VEC ids, vec and the 3-vectors.  Returns 0, or -2 when this model's step does not launch that kernel. */
+ * or, for the *_VEC ids, vec and the 3-vectors.  MJH_KERNEL_QUADRIC: like MJH_KERNEL_CONVEX, the two geom frames of each of its pairs and the pair's contacts.  Returns 0, or -2 when this model's step does not launch that kernel. */
 int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes);
 
 /* last error message of the calling thread ("" if none) */

@@ -192,8 +192,8 @@ struct DevModel {
   const int* con_body;                     // 4 * ncon: body1, body2, root body of body1, of body2
   const unsigned long long* con_dmask;     // 2 * ncon: body_dofmask of body1, body2
   const REAL* pair_cull;                   // 2 * npair: [reach^2, r1 + r2] of the bounding-sphere test RK4 stages 1..3 put before the narrow phase (reach^2 < 0: never culled)
-  const int* cvx_pairs;                    // ncvxpair: indices (into pair_*) of the pairs with a convex pair function
-  int ncvxpair;
+  const int* cvx_pairs;                    // ncvxpair: indices (into pair_*) of the pairs narrow-phased OUTSIDE the pass kernels (pair function >= MJH_FN_PLANE_CONVEX): the box / mesh pairs of mjh_convex_kernel, then the plane-ellipsoid / plane-cylinder pairs of mjh_quadric_kernel
+  int ncvxpair;                            // (> 0: the constraint stage loads handed-over contacts; a launch of either narrow-phase kernel sees list and count narrowed to its own pairs, mjhip.hip: NarrowedPairs)
 };
 
 // ---- wave helpers --------------------------------------------------------------------------------------

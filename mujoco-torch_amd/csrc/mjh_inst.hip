@@ -15,6 +15,7 @@
 #include "mjh_energy.h"
 #include "mjh_integrate.h"
 #include "mjh_jacobian.h"
+#include "mjh_quadric.h"
 #include "mjh_instances.h"
 
 #define MJH_CAT_(a, b) a##b
@@ -61,4 +62,7 @@ template __global__ void mjh_integrate_kernel<MJH_INST_REAL>(IntegrateArgs<MJH_I
 #if MJH_INST_GROUP == 28
 template __global__ void mjh_jac_matrix_kernel<MJH_INST_REAL>(JacArgs<MJH_INST_REAL>);
 template __global__ void mjh_jac_product_kernel<MJH_INST_REAL>(JacArgs<MJH_INST_REAL>);
+#endif
+#if MJH_INST_GROUP == 29
+template __global__ void mjh_quadric_kernel<MJH_INST_REAL>(KArgs<MJH_INST_REAL>);
 #endif

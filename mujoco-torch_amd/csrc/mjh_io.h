@@ -77,9 +77,14 @@ inline int mjh_kernel_io(const DevModel<REAL>& m, int kernel, int do_step, int64
       if (m.integrator == INT_RK4 && do_step == 1) { rd += nv + na; wr += 3 * nv + 2 * na; }  // stage 0 starts the sums and keeps qvel0 / act0
       break;
     case MJH_KERNEL_CONVEX:  // mjh_convex_kernel: the two geom frames of every convex pair in, its (up to four) contacts out
-      if (m.ncvxpair == 0) return -1;
+      if (m.ncvxpair == 0) return -1;  // (for this kernel and the next, `m.ncvxpair` is the count of the kernel's OWN pairs, as in its launches: the caller narrows it)
       rd = 24 * (int64_t)m.ncvxpair;
       wr = 13 * 4 * (int64_t)m.ncvxpair;
+      break;
+    case MJH_KERNEL_QUADRIC:  // mjh_quadric_kernel: the two geom frames of every plane-ellipsoid / plane-cylinder pair in, its (one or three: counted as three) contacts out
+      if (m.ncvxpair == 0) return -1;
+      rd = 24 * (int64_t)m.ncvxpair;
+      wr = 13 * 3 * (int64_t)m.ncvxpair;
       break;
     case MJH_KERNEL_SENSOR:  // mjh_sensor_kernel: site frames of the sensors, geom frames for the rays, cvel / subtree_com of the IMU bodies, joint state
       if (m.nsensor == 0) return -1;

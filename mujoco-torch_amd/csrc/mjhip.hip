@@ -27,6 +27,7 @@
 #include "mjh_energy.h"
 #include "mjh_jacobian.h"
 #include "mjh_integrate.h"
+#include "mjh_quadric.h"
 #include "mjh_instances.h"
 
 // the kernels are compiled in their own translation units (mjh_inst.hip, one per build group): this file is the host side only
@@ -71,6 +72,8 @@ extern template __global__ void mjh_jac_product_kernel<double>(JacArgs<double>);
 extern template __global__ void mjh_jac_product_kernel<float>(JacArgs<float>);
 extern template __global__ void mjh_integrate_kernel<double>(IntegrateArgs<double>);  // (build group 27)
 extern template __global__ void mjh_integrate_kernel<float>(IntegrateArgs<float>);
+extern template __global__ void mjh_quadric_kernel<double>(KArgs<double>);  // (build group 29)
+extern template __global__ void mjh_quadric_kernel<float>(KArgs<float>);
 #undef X_
 #undef S_
 #undef C_
@@ -153,6 +156,7 @@ struct mjhModel {
   int lds_tail = 0;
   int fuse_cs = 0;                         // constraint stage + register solver + integrator run as ONE kernel (SOL2_CS, MJH_KERNEL_CS) from an arena of its own
   int cvx_lds_bytes;                       // LDS scratch of one (environment, convex pair) wave
+  int ncvx = 0, nquad = 0;                 // DevModel::cvx_pairs lists every pair narrow-phased outside the pass kernels (ncvxpair of them): first the ncvx box / mesh pairs of mjh_convex_kernel, then the nquad plane-ellipsoid / plane-cylinder pairs of mjh_quadric_kernel
   int64_t work_reals;                      // per-environment REALs of workspace: RK4 stage Data and sums + the convex candidates of max_contact_points (0 for most Euler models)
   int64_t hs_reals = 0;                    // ... of which the constraint phase's hand-over to the register solver (KArgs::hs): small models with one contact condim
   int64_t cand_reals = 0;                  // ... of which the candidate contacts (at the HEAD of the workspace: its first B * cand_reals reals; the RK4 stage Data and sums follow)
@@ -622,12 +626,17 @@ int tables(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M, BlobBuilder&
   fix.push_back({(const void**)&M.dof_limrow, bb.add(dof_limrow.data(), sizeof(int) * dof_limrow.size())});
   M.max_depth = max_depth;
   // convex pairs and the LDS scratch their wave needs (layout in mjh_convex.h)
-  std::vector<int> cvx_pairs;
+  std::vector<int> cvx_pairs, quad_pairs;
   int cvx_reals = 0;
   for (int p = 0; p < d->npair; p++) {
     const int fn = d->pair_fn[p];
     if (fn < MJH_FN_PLANE_CONVEX) continue;
-    if (fn > MJH_FN_CONVEX_CONVEX) return fail(-38, "pair function not implemented");
+    if (fn == MJH_FN_PLANE_ELLIPSOID || fn == MJH_FN_PLANE_CYLINDER) {  // mjh_quadric_kernel (mjh_quadric.h): no tables, no LDS
+      if (d->pair_ncon[p] != (fn == MJH_FN_PLANE_CYLINDER ? 3 : 1)) return fail(-22, "plane-ellipsoid pairs have one contact, plane-cylinder pairs three");
+      quad_pairs.push_back(p);
+      continue;
+    }
+    if (fn > MJH_FN_PLANE_CYLINDER) return fail(-38, "pair function not implemented");
     const int c2 = d->geom_convexid[d->pair_geom2[p]], c1 = d->geom_convexid[d->pair_geom1[p]];
     if (c2 < 0 || c2 >= d->nconvex || (fn == MJH_FN_CONVEX_CONVEX && (c1 < 0 || c1 >= d->nconvex))) return fail(-22, "convex pair without convex tables");
     int need = 0;
@@ -640,8 +649,11 @@ int tables(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M, BlobBuilder&
     if (need > cvx_reals) cvx_reals = need;
     cvx_pairs.push_back(p);
   }
+  out->ncvx = (int)cvx_pairs.size();
+  out->nquad = (int)quad_pairs.size();
+  cvx_pairs.insert(cvx_pairs.end(), quad_pairs.begin(), quad_pairs.end());
   fix.push_back({(const void**)&M.cvx_pairs, bb.add(cvx_pairs.data(), sizeof(int) * cvx_pairs.size())});
-  M.ncvxpair = (int)cvx_pairs.size();
+  M.ncvxpair = (int)cvx_pairs.size();  // what the pass kernels test: contacts handed over through the contact leaves (or the candidate arrays)
   out->cvx_lds_bytes = (cvx_reals + 8) * (int)sizeof(REAL);
   if (out->cvx_lds_bytes > kLdsWg) return fail(-12, "convex hull too large for the pair kernel's LDS scratch");
   for (int i = 0; i < nv; i++) if (d->dof_damping[i] != 0) out->any_damping = 1;
@@ -851,7 +863,7 @@ int plan(const mjhModelDesc* d, mjhModel* out, DevModel<REAL>& M) {
     out->hs_reals = (sw.handover && d->integrator == INT_RK4 && M.con_direct && M.crow_by_con && out->sol2_nmax && !out->fuse_cs && nd > 0) ? ((1 + (int64_t)d->ncon + 2 * nd + nd * d->nv + 3) & ~(int64_t)3) : 0;
     out->work_reals += out->hs_reals;
   }
-  out->cand_reals = (d->topk && M.ncvxpair > 0) ? 13 * (int64_t)d->ncand : 0;  // candidate contacts of the convex narrow phase (dist, pos, frame)
+  out->cand_reals = (d->topk && M.ncvxpair > 0) ? 13 * (int64_t)d->ncand : 0;  // candidate contacts of the convex / quadric narrow phases (dist, pos, frame)
   out->work_reals += out->cand_reals;
   return 0;
 }
@@ -1101,8 +1113,18 @@ int launch_all(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
 }
 
 // convex narrow phase: one wavefront per (environment, pair), one launch per 2^22 of them; sensors: one per environment
+// (a launch of either narrow-phase kernel sees DevModel::cvx_pairs / ncvxpair narrowed to its own pairs: NarrowedPairs)
+template <typename REAL>
+struct NarrowedPairs {
+  DevModel<REAL>& M;
+  const int* const pairs;
+  const int n;
+  NarrowedPairs(DevModel<REAL>& M_, int first, int count) : M(M_), pairs(M_.cvx_pairs), n(M_.ncvxpair) { M.cvx_pairs = pairs + first; M.ncvxpair = count; }
+  ~NarrowedPairs() { M.cvx_pairs = pairs; M.ncvxpair = n; }
+};
 template <typename REAL>
 int launch_convex(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
+  const NarrowedPairs<REAL> own(a.M, 0, m->ncvx);
   const int rc = launch_cut(a.B * a.M.ncvxpair, 1, [&](int64_t first, int64_t, unsigned grid) {
     a.env_begin = first;  // (first ITEM of this launch)
     hipLaunchKernelGGL((mjh_convex_kernel<REAL>), dim3(grid), dim3(MJH_WAVE), (size_t)m->cvx_lds_bytes, stream, a);
@@ -1110,6 +1132,19 @@ int launch_convex(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
   a.env_begin = 0;
   if (rc) return rc;
   timing_mark(stream, MJH_KERNEL_CONVEX);
+  return 0;
+}
+// plane-ellipsoid / plane-cylinder narrow phase: one LANE per (environment, pair), 64 items per one-wave workgroup
+template <typename REAL>
+int launch_quadric(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
+  const NarrowedPairs<REAL> own(a.M, m->ncvx, m->nquad);
+  const int rc = launch_cut(a.B * a.M.ncvxpair, MJH_WAVE, [&](int64_t first, int64_t n, unsigned grid) {
+    a.env_begin = first; a.env_count = n;  // (ITEMS of this launch)
+    hipLaunchKernelGGL((mjh_quadric_kernel<REAL>), dim3(grid), dim3(MJH_WAVE), 0, stream, a);
+  });
+  a.env_begin = 0; a.env_count = a.B;
+  if (rc) return rc;
+  timing_mark(stream, MJH_KERNEL_QUADRIC);
   return 0;
 }
 template <typename REAL>
@@ -1180,8 +1215,11 @@ int forward_pass(const mjhModel* m, KArgs<REAL>& a, hipStream_t stream) {
   const bool fused_kv = m->fuse_kv && (st & kFromVelocity);  // the velocity phase is asked for: it rides with the kinematics (it needs nothing of CRB / CON)
   const bool fused_kcv = fused_kv && m->fuse_kcv && (st & kFromCrb);  // ... and so does the crb / factor stage (small models)
   if ((st & MJH_STAGE_ALL) && (rc = fused_kcv ? ((m->kcv2 && a.B <= kcv2_limit(m, stream)) ? launch_phase<REAL, MJH_KERNEL_KCV2>(m, a, stream) : launch_phase<REAL, MJH_KERNEL_KCV>(m, a, stream)) : (fused_kv ? launch_phase<REAL, MJH_KERNEL_KV>(m, a, stream) : launch_phase<REAL, MJH_KERNEL_KIN>(m, a, stream)))) return rc;
-  if ((st & kFromCollision) && a.M.ncvxpair > 0) {  // convex narrow phase: one wave per (environment, pair); needs only the geom frames of PH_KIN
+  if ((st & kFromCollision) && m->ncvx > 0) {  // convex narrow phase: one wave per (environment, pair); needs only the geom frames of PH_KIN
     if ((rc = launch_convex<REAL>(m, a, stream))) return rc;
+  }
+  if ((st & kFromCollision) && m->nquad > 0) {  // ... and the plane-ellipsoid / plane-cylinder pairs, one lane each
+    if ((rc = launch_quadric<REAL>(m, a, stream))) return rc;
   }
   if ((st & kFromCrb) && !fused_kcv && (rc = launch_phase<REAL, MJH_KERNEL_CRB>(m, a, stream))) return rc;
   const bool fused_cs = m->fuse_cs && (st & kFromCollision) && (st & MJH_STAGE_SOLVE) && a.cur.efc_J && a.cur.efc_D && a.cur.efc_aref;  // the whole tail of the pass is asked for: constraint stage and solve share a kernel
@@ -1228,15 +1266,15 @@ int run(const mjhModel* m, const DevModel<REAL>& M, const mjhData* in, mjhData* 
   if ((a.stages & kFromActuation) && !(fin.qM && fin.qLD && fin.qfrc_smooth)) return fail(-22, "the solver phase reads out.qM / out.qLD: both leaves are required");
   if (M.ncon > 0 && M.nefc > 0 && (a.stages & MJH_STAGE_SOLVE) && !fin.contact_dist) return fail(-22, "the solver phase reads out.contact_dist (active-contact row compaction): the leaf is required");
   if (M.ncvxpair > 0 && (a.stages & kFromCollision) && !(fin.contact_dist && fin.contact_pos && fin.contact_frame && fin.geom_xpos && fin.geom_xmat))
-    return fail(-22, "models with convex pairs need out.geom_xpos/geom_xmat and out.contact_dist/pos/frame");
+    return fail(-22, "models with convex or plane-ellipsoid / plane-cylinder pairs need out.geom_xpos/geom_xmat and out.contact_dist/pos/frame");
   hipStream_t s = (hipStream_t)stream;
   REAL* w = (REAL*)work;
   if (m->hs_reals > 0) {  // (without a workspace the solver reads the leaves, as it always did)
     if (work) { a.hs = w; a.hs_reals = (int)m->hs_reals; }
     w += m->hs_reals * B;
   }
-  if (m->cand_reals > 0 && (a.stages & kFromCollision)) {  // max_contact_points over box / mesh pairs: the candidates live at the head of the workspace
-    if (!work) return fail(-22, "max_contact_points with box / mesh pairs needs a workspace of mjh_model_work_bytes(m) * B bytes");
+  if (m->cand_reals > 0 && (a.stages & kFromCollision)) {  // max_contact_points over pairs narrow-phased outside the pass (box / mesh, ellipsoid / cylinder): the candidates live at the head of the workspace
+    if (!work) return fail(-22, "max_contact_points with box / mesh / ellipsoid / cylinder pairs needs a workspace of mjh_model_work_bytes(m) * B bytes");
     a.cand = w;
     w += m->cand_reals * B;
   }
@@ -2088,9 +2126,12 @@ static int kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes, b
   const bool rk4 = (f64 ? m->m64.integrator : m->m32.integrator) == INT_RK4;
   auto io_of = [&](int k, int64_t* a) -> int {  // RK4: the mean over the four stage launches of a step (the sensor kernel runs once)
     int64_t b[2] = {0, 0};
-    int rc = f64 ? mjh_kernel_io<double>(m->m64, k, 1, &a[0], &a[1]) : mjh_kernel_io<float>(m->m32, k, 1, &a[0], &a[1]);
+    DevModel<double> m64 = m->m64;
+    DevModel<float> m32 = m->m32;
+    if (k == MJH_KERNEL_CONVEX || k == MJH_KERNEL_QUADRIC) m64.ncvxpair = m32.ncvxpair = k == MJH_KERNEL_CONVEX ? m->ncvx : m->nquad;  // (as their launches: the kernel's own pairs, NarrowedPairs)
+    int rc = f64 ? mjh_kernel_io<double>(m64, k, 1, &a[0], &a[1]) : mjh_kernel_io<float>(m32, k, 1, &a[0], &a[1]);
     if (rc == 0 && rk4 && k != MJH_KERNEL_SENSOR) {
-      rc = f64 ? mjh_kernel_io<double>(m->m64, k, 2, &b[0], &b[1]) : mjh_kernel_io<float>(m->m32, k, 2, &b[0], &b[1]);
+      rc = f64 ? mjh_kernel_io<double>(m64, k, 2, &b[0], &b[1]) : mjh_kernel_io<float>(m32, k, 2, &b[0], &b[1]);
       if (stages13) { a[0] = b[0]; a[1] = b[1]; }                             // the stage kernel: launches of stages 1..3 only
       else if (m->fuse_stage) {}                                               // ... whose model launches kernels 13 / 8 / 9 in stage 0 only
       else { a[0] = (a[0] + 3 * b[0]) / 4; a[1] = (a[1] + 3 * b[1]) / 4; }

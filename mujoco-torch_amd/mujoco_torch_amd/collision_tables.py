@@ -27,10 +27,13 @@ from ._enums import ConeType, DisableBit, GeomType, mjMINMU, mjMINVAL
 # (type1, type2) -> (fn id in include/mjhip.h, contacts per pair)   collision_driver.py:106-125
 FN_PLANE_SPHERE, FN_PLANE_CAPSULE, FN_SPHERE_SPHERE, FN_SPHERE_CAPSULE, FN_CAPSULE_CAPSULE = 0, 1, 2, 3, 4
 FN_PLANE_CONVEX, FN_SPHERE_CONVEX, FN_CAPSULE_CONVEX, FN_CONVEX_CONVEX = 5, 6, 7, 8
+FN_PLANE_ELLIPSOID, FN_PLANE_CYLINDER = 9, 10  # collision_primitive.py:77-169; absent from the reference's driver table, registered by tools/gen_quadric_golden.py
 _G = GeomType
 COLLISION_FN = {
     (_G.PLANE, _G.SPHERE): (FN_PLANE_SPHERE, 1),
     (_G.PLANE, _G.CAPSULE): (FN_PLANE_CAPSULE, 2),
+    (_G.PLANE, _G.ELLIPSOID): (FN_PLANE_ELLIPSOID, 1),
+    (_G.PLANE, _G.CYLINDER): (FN_PLANE_CYLINDER, 3),
     (_G.PLANE, _G.BOX): (FN_PLANE_CONVEX, 4),
     (_G.PLANE, _G.MESH): (FN_PLANE_CONVEX, 4),
     (_G.SPHERE, _G.SPHERE): (FN_SPHERE_SPHERE, 1),
