@@ -13,6 +13,7 @@
  *   mjh_render         <- render.render_batch(m, d, camera_id, ...)   (_src/render.py:719-907)
  *   mjh_fd_perturb / mjh_fd_difference <- the two ends of a finite-difference transition Jacobian (MuJoCo's mjd_transitionFD; the reference has no counterpart)
  *   mjh_fd_vjp / mjh_fd_tangent        <- its vector-Jacobian product and the quaternion coordinate maps of a gradient through one step
+ *   mjh_ifd_perturb / mjh_ifd_difference <- the two ends of a finite-difference Jacobian of inverse dynamics (MuJoCo's mjd_inverseFD; the reference has no counterpart)
  *   mjh_support        <- support.jac / apply_ft / xfrc_accumulate, smooth.mul_m / solve_m (_src/support.py:138-194, smooth.py:335-374)
  *   mjh_postconstraint <- MuJoCo's mj_rnePostConstraint / mj_subtreeVel (MJX smooth.rne_postconstraint / subtree_vel; the reference has no counterpart)
  *   mjh_contact_sensors <- MuJoCo's mj_contactForce (MJX support.contact_force) and its touch / framelinacc / frameangacc sensors (the reference evaluates none of them)
@@ -109,6 +110,8 @@ extern "C" {
 #define MJH_KERNEL_JACOBIAN_SUBTREE_COM_VEC 42
 #define MJH_KERNEL_JACOBIAN_ANGMOM_VEC 43
 #define MJH_KERNEL_QUADRIC 44    /* plane-ellipsoid / plane-cylinder narrow phase (one lane per (environment, pair))   */
+#define MJH_KERNEL_IFD_PERTURB 45 /* mjh_ifd_perturb: the perturbed input leaves of a chunk of inverse-dynamics columns */
+#define MJH_KERNEL_IFD_DIFFERENCE 46 /* mjh_ifd_difference: the columns of DfDq, DfDv, DfDa (DsDq, DsDv, DsDa) from the chunk */
 
 /* pair-function ids of the static collision table (collision_driver.py:106-125) */
 #define MJH_FN_PLANE_SPHERE 0
@@ -764,6 +767,26 @@ int mjh_fd_vjp(const mjhModel* m, const mjhData* in, const mjhData* nominal, con
 #define MJH_FD_TANGENT_PUSH 1
 int mjh_fd_tangent(const mjhModel* m, const void* qpos, const void* g_in, void* g_out, int64_t B, int mode, void* hip_stream);
 
+/* Finite-difference Jacobians of inverse dynamics (MuJoCo's mjd_inverseFD), as two launches around an mjh_inverse of the caller's own.  Column c in
+ * [0, nv) nudges qpos along dof c (tangent space), [nv, 2 nv) qvel, [2 nv, 3 nv) qacc; nothing else is perturbed.  A call serves the columns
+ * [col0, col0 + ncol) of all B environments, in the slot layout of mjh_fd_perturb: each column of an environment owns nside = (centered ? 2 : 1)
+ * environments of a scratch batch of B * ncol * nside, slot (e * ncol + (c - col0)) * nside + side; side 0 carries the nudge +eps, side 1 -eps.
+ *
+ * mjh_ifd_perturb: for every slot, copies every leaf that is non-NULL in `scratch` from environment e of `in` (which must carry it) and applies the
+ * slot's nudge by the rule of mjh_fd_perturb: addition, or for the rotational dofs of ball / free joints the rotation of the quaternion by eps about
+ * the dof's local axis.  scratch.qpos / qvel / qacc must be non-NULL (mjh_inverse reads in.qacc).  The leaves an mjh_inverse call can read from its
+ * input are those a step can read, qacc, and -- for the sensors -- the caller's actuator_force / qfrc_actuator.
+ * mjh_ifd_difference: from the nominal pass's qfrc_inverse `nominal_f` [B, nv] and sensordata `nominal_sens` [B, nsensordata], and those of the
+ * scratch batch (`stepped_f`, `stepped_sens`: [slots, ...]), writes the columns of the call into DfDq, DfDv, DfDa [B, nv, nv] and -- when all three
+ * are given -- DsDq, DsDv, DsDa [B, nsensordata, nv]: column c < nv of DfDq / DsDq, c - nv of DfDv / DsDv, c - 2 nv of DfDa / DsDa.  Rows are outputs
+ * (MuJoCo stores the transposes).  Every entry is (y+ - y0) / eps or, centered, (y+ - y-) / (2 eps): no output is a quaternion.  nominal_* are not
+ * read when centered and may then be NULL; the sensor pointers may be NULL when the sensor matrices are.
+ * Both run on hip_stream without host synchronisation; eps is rounded to the model's dtype.  Return 0 or a negative code; B == 0 is a no-op. */
+int mjh_ifd_perturb(const mjhModel* m, const mjhData* in, mjhData* scratch, int64_t B, int col0, int ncol, double eps, int centered, void* hip_stream);
+int mjh_ifd_difference(const mjhModel* m, const void* nominal_f, const void* nominal_sens, const void* stepped_f, const void* stepped_sens, int64_t B,
+                       int col0, int ncol, double eps, int centered, void* DfDq, void* DfDv, void* DfDa, void* DsDq, void* DsDv, void* DsDa,
+                       void* hip_stream);
+
 /* per-environment ELEMENT count of every mjhData leaf in ABI order (reals, then int32, then int64 leaves): a leaf handed to
  * mjh_forward / mjh_step / mjh_reset_where must hold exactly B * count elements.  The binding validates tensor sizes against
  * this before it passes raw pointers (the kernels index `ptr + env * count` unchecked).  Writes min(n, max) entries, returns n. */
@@ -784,7 +807,7 @@ int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsi
 int mjh_model_lds_bytes(const mjhModel* m, int arena);
 
 /* measurement aid used by bench.py for the per-kernel roofline: while enabled, every kernel launch of mjh_step / mjh_forward is
- * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_postconstraint, mjh_contact_sensors, mjh_energy, mjh_integrate and mjh_jacobian too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
+ * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_ifd_perturb, mjh_ifd_difference, mjh_postconstraint, mjh_contact_sensors, mjh_energy, mjh_integrate and mjh_jacobian too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
  * the elapsed milliseconds and the kernel id (MJH_KERNEL_*).  Returns the number of launches (<= max) or a negative code. */
 int mjh_debug_phase_timing(int enable);
 int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
@@ -808,7 +831,9 @@ void mjh_debug_set_stamps(void* dev_ptr);
  * (an mjh_energy call with MJH_ENERGY_POS | MJH_ENERGY_VEL): per environment, qpos, qvel, xipos, ten_length and qM once, the two energies written.  MJH_KERNEL_INTEGRATE
  * (an mjh_integrate call for implicit: QDERIV | IMPLICIT | STATE): per environment, the leaves that call reads once (qM in full), qpos, qvel, act and time written.  MJH_KERNEL_JACOBIAN_* (an mjh_jacobian call): per environment
  * for one query, the dof rows and the body rows the operation reads (DOT: cvel and cdof_dot too; the subtree operations: xipos, ximat for ANGMOM) and the matrices,
- * or, for the *_VEC ids, vec and the 3-vectors.  MJH_KERNEL_QUADRIC: like MJH_KERNEL_CONVEX, the two geom frames of each of its pairs and the pair's contacts.  Returns 0, or -2 when this model's step does not launch that kernel. */
+ * or, for the *_VEC ids, vec and the 3-vectors.  MJH_KERNEL_QUADRIC: like MJH_KERNEL_CONVEX, the two geom frames of each of its pairs and the pair's contacts.  MJH_KERNEL_IFD_PERTURB / MJH_KERNEL_IFD_DIFFERENCE:
+ * per slot, the input leaves an mjh_inverse call of this model can read, read and written (an upper bound: the caller's Data may lack some), and one slot's qfrc_inverse and
+ * sensordata read, with [1] = one column of DfD* and DsD*.  Returns 0, or -2 when this model's step does not launch that kernel. */
 int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes);
 
 /* last error message of the calling thread ("" if none) */

@@ -10,6 +10,7 @@
 #include "mjh_render.h"
 #include "mjh_support.h"
 #include "mjh_fd.h"
+#include "mjh_ifd.h"
 #include "mjh_postcon.h"
 #include "mjh_contact_sensors.h"
 #include "mjh_energy.h"
@@ -65,4 +66,8 @@ template __global__ void mjh_jac_product_kernel<MJH_INST_REAL>(JacArgs<MJH_INST_
 #endif
 #if MJH_INST_GROUP == 29
 template __global__ void mjh_quadric_kernel<MJH_INST_REAL>(KArgs<MJH_INST_REAL>);
+#endif
+#if MJH_INST_GROUP == 30
+template __global__ void mjh_ifd_perturb_kernel<MJH_INST_REAL>(IfdPerturbArgs<MJH_INST_REAL>);
+template __global__ void mjh_ifd_difference_kernel<MJH_INST_REAL>(IfdDiffArgs<MJH_INST_REAL>);
 #endif

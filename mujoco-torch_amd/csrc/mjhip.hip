@@ -22,6 +22,7 @@
 #include "mjh_render.h"
 #include "mjh_support.h"
 #include "mjh_fd.h"
+#include "mjh_ifd.h"
 #include "mjh_postcon.h"
 #include "mjh_contact_sensors.h"
 #include "mjh_energy.h"
@@ -74,6 +75,10 @@ extern template __global__ void mjh_integrate_kernel<double>(IntegrateArgs<doubl
 extern template __global__ void mjh_integrate_kernel<float>(IntegrateArgs<float>);
 extern template __global__ void mjh_quadric_kernel<double>(KArgs<double>);  // (build group 29)
 extern template __global__ void mjh_quadric_kernel<float>(KArgs<float>);
+extern template __global__ void mjh_ifd_perturb_kernel<double>(IfdPerturbArgs<double>);  // (build group 30)
+extern template __global__ void mjh_ifd_perturb_kernel<float>(IfdPerturbArgs<float>);
+extern template __global__ void mjh_ifd_difference_kernel<double>(IfdDiffArgs<double>);
+extern template __global__ void mjh_ifd_difference_kernel<float>(IfdDiffArgs<float>);
 #undef X_
 #undef S_
 #undef C_
@@ -1927,6 +1932,87 @@ int run_fd_tangent(const DevModel<REAL>& M, const void* qpos, const void* g_in, 
   return 0;
 }
 
+// ---- finite-difference Jacobians of inverse dynamics (mjh_ifd.h): the launches on either side of the caller's mjh_inverse over the perturbed environments ----
+
+template <typename REAL>
+int ifd_check(const DevModel<REAL>& M, int64_t B, int col0, int ncol, double eps) {
+  if (B < 0) return fail(-22, "ifd: B must be >= 0");
+  if (!(eps > 0) || !((REAL)eps > 0)) return fail(-22, "ifd: eps must be positive in the model's dtype");
+  if (col0 < 0 || ncol < 1 || (int64_t)col0 + ncol > 3 * (int64_t)M.nv) return fail(-22, "ifd: columns outside [0, 3 nv)");
+  if ((int64_t)ncol * 2 * (M.nv + M.nsensordata + 1) >= ((int64_t)1 << 31)) return fail(-22, "ifd: too many columns in one call");
+  return 0;
+}
+
+template <typename REAL>
+int run_ifd_perturb(const mjhModel* m, const DevModel<REAL>& M, const mjhData* in, mjhData* scratch, int64_t B, int col0, int ncol, double eps, int centered, void* stream) {
+  static_assert(sizeof(IfdPerturbArgs<REAL>) <= 4096, "kernel arguments exceed the 4 KiB kernarg segment");
+  if (B == 0 || M.nv == 0) return B < 0 ? fail(-22, "ifd: B must be >= 0") : 0;
+  if (const int rc = ifd_check(M, B, col0, ncol, eps)) return rc;
+  IfdPerturbArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+  if (!in->qpos || !in->qvel || !in->qacc || !scratch->qpos || !scratch->qvel || !scratch->qacc)
+    return fail(-22, "ifd_perturb: qpos, qvel and qacc are required in both Data");
+  const std::vector<int64_t> words = data_words(m, M);
+  if (words.size() * sizeof(void*) != sizeof(mjhData)) return fail(-22, "ifd_perturb: leaf table out of sync with mjhData");
+  void* const* dp = reinterpret_cast<void* const*>(scratch);
+  void* const* sp = reinterpret_cast<void* const*>(in);
+  for (size_t i = 0; i < words.size(); i++) {
+    if (!dp[i] || words[i] == 0) continue;
+    if (!sp[i]) return fail(-22, "ifd_perturb: a leaf of the scratch Data is missing from the input Data");
+    if (a.nleaf == MJH_FD_MAX_LEAVES) return fail(-22, "ifd_perturb: too many leaves in the scratch Data (input leaves only)");
+    FdLeaf& L = a.leaf[a.nleaf++];
+    L.dst = (unsigned*)dp[i]; L.src = (const unsigned*)sp[i]; L.words = (int)words[i];
+  }
+  a.dof_jntid = M.dof_jntid; a.jnt_type = M.jnt_type; a.jnt_qposadr = M.jnt_qposadr; a.jnt_dofadr = M.jnt_dofadr;
+  a.qpos = reinterpret_cast<const REAL*>(in->qpos); a.qvel = reinterpret_cast<const REAL*>(in->qvel); a.qacc = reinterpret_cast<const REAL*>(in->qacc);
+  a.p_qpos = reinterpret_cast<REAL*>(scratch->qpos); a.p_qvel = reinterpret_cast<REAL*>(scratch->qvel); a.p_qacc = reinterpret_cast<REAL*>(scratch->qacc);
+  a.eps = (REAL)eps;
+  a.nq = M.nq; a.nv = M.nv;
+  a.centered = centered ? 1 : 0; a.col0 = col0; a.ncol = ncol;
+  a.total = B * ncol * (centered ? 2 : 1);
+  hipStream_t s = (hipStream_t)stream;
+  timing_begin(s);
+  if (const int rc = launch_cut(a.total, 1, [&](int64_t first, int64_t, unsigned grid) {
+        a.first = first;
+        hipLaunchKernelGGL((mjh_ifd_perturb_kernel<REAL>), dim3(grid), dim3(MJH_IFD_PERTURB_WG), 0, s, a);
+      }))
+    return rc;
+  timing_mark(s, MJH_KERNEL_IFD_PERTURB);
+  return 0;
+}
+
+template <typename REAL>
+int run_ifd_difference(const DevModel<REAL>& M, const void* f0, const void* s0, const void* f, const void* sd, int64_t B, int col0, int ncol, double eps,
+                       int centered, void* DfDq, void* DfDv, void* DfDa, void* DsDq, void* DsDv, void* DsDa, void* stream) {
+  if (B == 0 || M.nv == 0) return B < 0 ? fail(-22, "ifd: B must be >= 0") : 0;
+  if (const int rc = ifd_check(M, B, col0, ncol, eps)) return rc;
+  const int given = (DsDq != nullptr) + (DsDv != nullptr) + (DsDa != nullptr);
+  if (given != 0 && given != 3) return fail(-22, "ifd_difference: DsDq, DsDv and DsDa go together");
+  const bool sens = given == 3 && M.nsensordata > 0;
+  if (!DfDq || !DfDv || !DfDa) return fail(-22, "ifd_difference: DfDq, DfDv and DfDa are required");
+  if (!f || (!centered && !f0)) return fail(-22, "ifd_difference: qfrc_inverse of the perturbed passes (and, one-sided, of the nominal pass) is required");
+  if (sens && (!sd || (!centered && !s0))) return fail(-22, "ifd_difference: sensordata of the perturbed passes (and, one-sided, of the nominal pass) is required for DsD*");
+  IfdDiffArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+  a.f0 = reinterpret_cast<const REAL*>(f0); a.s0 = reinterpret_cast<const REAL*>(s0);
+  a.f = reinterpret_cast<const REAL*>(f); a.s = reinterpret_cast<const REAL*>(sd);
+  a.DfDq = reinterpret_cast<REAL*>(DfDq); a.DfDv = reinterpret_cast<REAL*>(DfDv); a.DfDa = reinterpret_cast<REAL*>(DfDa);
+  if (sens) { a.DsDq = reinterpret_cast<REAL*>(DsDq); a.DsDv = reinterpret_cast<REAL*>(DsDv); a.DsDa = reinterpret_cast<REAL*>(DsDa); }
+  a.eps = (REAL)eps;
+  a.nv = M.nv; a.nsd = sens ? M.nsensordata : 0;
+  a.centered = centered ? 1 : 0; a.col0 = col0; a.ncol = ncol;
+  a.total = B * (a.nv + a.nsd) * ncol;
+  hipStream_t s = (hipStream_t)stream;
+  timing_begin(s);
+  if (const int rc = launch_cut(a.total, MJH_IFD_DIFF_WG, [&](int64_t first, int64_t, unsigned grid) {
+        a.first = first;
+        hipLaunchKernelGGL((mjh_ifd_difference_kernel<REAL>), dim3(grid), dim3(MJH_IFD_DIFF_WG), 0, s, a);
+      }))
+    return rc;
+  timing_mark(s, MJH_KERNEL_IFD_DIFFERENCE);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2043,6 +2129,20 @@ int mjh_fd_tangent(const mjhModel* m, const void* qpos, const void* g_in, void* 
   if (!m) return fail(-22, "null argument");
   return m->dtype == MJH_F64 ? run_fd_tangent<double>(m->m64, qpos, g_in, g_out, B, mode, stream)
                              : run_fd_tangent<float>(m->m32, qpos, g_in, g_out, B, mode, stream);
+}
+
+int mjh_ifd_perturb(const mjhModel* m, const mjhData* in, mjhData* scratch, int64_t B, int col0, int ncol, double eps, int centered, void* stream) {
+  if (!m || !in || !scratch) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_ifd_perturb<double>(m, m->m64, in, scratch, B, col0, ncol, eps, centered, stream)
+                             : run_ifd_perturb<float>(m, m->m32, in, scratch, B, col0, ncol, eps, centered, stream);
+}
+
+int mjh_ifd_difference(const mjhModel* m, const void* nominal_f, const void* nominal_sens, const void* stepped_f, const void* stepped_sens, int64_t B,
+                       int col0, int ncol, double eps, int centered, void* DfDq, void* DfDv, void* DfDa, void* DsDq, void* DsDv, void* DsDa, void* stream) {
+  if (!m) return fail(-22, "null argument");
+  return m->dtype == MJH_F64
+             ? run_ifd_difference<double>(m->m64, nominal_f, nominal_sens, stepped_f, stepped_sens, B, col0, ncol, eps, centered, DfDq, DfDv, DfDa, DsDq, DsDv, DsDa, stream)
+             : run_ifd_difference<float>(m->m32, nominal_f, nominal_sens, stepped_f, stepped_sens, B, col0, ncol, eps, centered, DfDq, DfDv, DfDa, DsDq, DsDv, DsDa, stream);
 }
 
 int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsigned char* mask, const void* qpos_rows,
@@ -2162,6 +2262,17 @@ static int kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes, b
     } else {
       read_write_bytes[0] = (nq + nv + na + nsd) * R;
       read_write_bytes[1] = (2 * nv + na + nsd) * R;
+    }
+    return 0;
+  }
+  if (kernel == MJH_KERNEL_IFD_PERTURB || kernel == MJH_KERNEL_IFD_DIFFERENCE) {  // the inverse-dynamics finite-difference kernels (mjh_ifd.h), per slot: see include/mjhip.h
+    const int64_t R = f64 ? 8 : 4, nq = f64 ? m->m64.nq : m->m32.nq, nv = f64 ? m->m64.nv : m->m32.nv, na = f64 ? m->m64.na : m->m32.na, nu = f64 ? m->m64.nu : m->m32.nu;
+    const int64_t nb = f64 ? m->m64.nbody : m->m32.nbody, nmo = f64 ? m->m64.nmocap : m->m32.nmocap, nsd = f64 ? m->m64.nsensordata : m->m32.nsensordata, neq = f64 ? m->m64.neq : m->m32.neq;
+    if (nv == 0) return -2;
+    if (kernel == MJH_KERNEL_IFD_PERTURB) {  // the leaves of MJH_KERNEL_FD_PERTURB, and qacc and qfrc_actuator
+      read_write_bytes[0] = read_write_bytes[1] = (1 + nq + 7 * nv + na + 2 * nu + 6 * nb + 7 * nmo + 3 * nb + nsd + 18 * nb) * R + 4 * neq;
+    } else {
+      read_write_bytes[0] = read_write_bytes[1] = (nv + nsd) * R;
     }
     return 0;
   }

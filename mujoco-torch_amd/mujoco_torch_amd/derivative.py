@@ -1,5 +1,6 @@
 """``transition_fd``: finite-difference Jacobians of one ``step`` with respect to state and control (MuJoCo's ``mjd_transitionFD``);
-``transition_vjp``: their product with a cotangent, without forming them; ``differentiable_step``: ``step`` with an autograd graph built on that.
+``transition_vjp``: their product with a cotangent, without forming them; ``differentiable_step``: ``step`` with an autograd graph built on that;
+``inverse_fd``: finite-difference Jacobians of ``inverse`` with respect to position, velocity and acceleration (MuJoCo's ``mjd_inverseFD``).
 
 The step is one opaque native launch sequence, so there is no autograd graph to differentiate; what the library can do cheaply is step many
 environments at once.  The ``P`` perturbed steps of an environment are ``P`` more environments of a scratch batch:
@@ -13,6 +14,10 @@ environments at once.  The ``P`` perturbed steps of an environment are ``P`` mor
 The nominal step runs once.  The scratch batch is bounded by ``max_scratch_bytes``: the columns are processed in chunks sized to it, the scratch is
 reused between chunks and kept per (model, batch, dtype, stream) for the next call.  Host work per call is a few ctypes calls per chunk; nothing
 synchronises, everything runs on the caller's current stream.
+
+``inverse_fd`` goes through the same chunk loop with another native pass between its two kernels: ``mjh_ifd_perturb`` (``csrc/mjh_ifd.h``) nudges
+``qpos`` (tangent space), ``qvel`` or ``qacc``, ``mjh_inverse`` -- the library's ordinary inverse pass, unchanged -- runs on the chunk, and
+``mjh_ifd_difference`` differences ``qfrc_inverse`` and ``sensordata``.
 """
 
 from __future__ import annotations
@@ -37,6 +42,9 @@ _SCRATCH_KEPT = 2            # scratch batches kept per model for later calls (m
 # actuation off; qfrc_constraint without constraint rows; sensordata slots no sensor fills).  Those the caller's Data holds are replicated.
 _INPUT_LEAVES = ("time qpos qvel act qacc_warmstart ctrl qfrc_applied xfrc_applied mocap_pos mocap_quat subtree_com qfrc_gravcomp actuator_force "
                  "qfrc_constraint sensordata eq_active").split()
+# ... and an inverse pass (mjh_inverse's contract, include/mjhip.h): it runs the stages of a step up to the velocity stage, then the tail, which reads
+# the caller's qacc, and the sensors, which read the caller's actuator_force / qfrc_actuator because the pass evaluates no actuation.
+_INVERSE_INPUT_LEAVES = _INPUT_LEAVES + ["qacc", "qfrc_actuator"]
 
 
 def _bind(lib):
@@ -55,13 +63,20 @@ def _bind(lib):
     lib.mjh_fd_vjp.restype = ctypes.c_int
     lib.mjh_fd_tangent.argtypes = [V, V, V, V, ctypes.c_int64, ctypes.c_int, V]
     lib.mjh_fd_tangent.restype = ctypes.c_int
+    if not hasattr(lib, "mjh_ifd_perturb"):
+        raise RuntimeError(f"{native.LIB_PATH} predates inverse_fd (no mjh_ifd_perturb): rebuild the library")
+    lib.mjh_ifd_perturb.argtypes = [V, P, P, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, V]
+    lib.mjh_ifd_perturb.restype = ctypes.c_int
+    lib.mjh_ifd_difference.argtypes = [V, V, V, V, V, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, V, V, V, V, V, V, V]
+    lib.mjh_ifd_difference.restype = ctypes.c_int
     lib._fd_bound = True
 
 
 class _Scratch:
-    """The scratch batch of ``slots`` environments: one allocation, and the two pointer structs (inputs, step outputs) into it."""
+    """The scratch batch of ``slots`` environments: one allocation, and the two pointer structs (inputs, the pass's outputs) into it; ``tail``:
+    the address of ``tail_bytes`` more per slot, for an output that is no ABI leaf (``qfrc_inverse``), or 0."""
 
-    __slots__ = ("slab", "inp", "out", "slots")
+    __slots__ = ("slab", "inp", "out", "slots", "tail")
 
 
 def _leaf_bytes(fw, counts, dtype):
@@ -73,7 +88,7 @@ def _leaf_bytes(fw, counts, dtype):
     return np.asarray(counts, dtype=np.int64) * size
 
 
-def _make_scratch(fw, in_idx, extra_idx, extra_bytes, out_idx, leaf_bytes, slots, device) -> _Scratch:
+def _make_scratch(fw, in_idx, extra_idx, extra_bytes, out_idx, leaf_bytes, slots, device, tail_bytes=0) -> _Scratch:
     s = _Scratch()
     s.slots = slots
     s.inp, s.out = native.DataPtrs(), native.DataPtrs()
@@ -86,10 +101,13 @@ def _make_scratch(fw, in_idx, extra_idx, extra_bytes, out_idx, leaf_bytes, slots
             continue
         where.append((arr, idx, off))
         off += (int(nbytes) * slots + _ALIGN - 1) // _ALIGN * _ALIGN
+    tail_off = off
+    off += (int(tail_bytes) * slots + _ALIGN - 1) // _ALIGN * _ALIGN
     s.slab = torch.empty(off, dtype=torch.uint8, device=device)
     base = s.slab.data_ptr()
     for arr, idx, o in where:
         arr[idx] = base + o
+    s.tail = base + tail_off if tail_bytes else 0
     return s
 
 
@@ -159,16 +177,24 @@ def _on_device(c: _Call, m: Model):
     c.fw._require_device(c.device)
 
 
-def _drive(name, c: _Call, m: Model, d: Data, centered, fixed_iterations, consume, nominal=None):
+def _drive(name, c: _Call, m: Model, d: Data, centered, fixed_iterations, consume, nominal=None, inverse=False):
     """The chunk loop: perturb, step, ``consume(lib, handle, in, nominal, stepped, col0, ncol, stream)`` (``mjh_fd_difference`` or ``mjh_fd_vjp``)
-    for every chunk of columns, after the nominal step -- or with ``nominal``, the pointer struct of one that has already run."""
+    for every chunk of columns, after the nominal step -- or with ``nominal``, the pointer struct of one that has already run.
+
+    ``inverse``: the native pass between perturb and consume is ``mjh_inverse`` instead of ``mjh_step`` -- the call ``inverse(m, d)`` makes, with
+    its flags -- around it ``mjh_ifd_perturb`` over the 3 nv columns of qpos / qvel / qacc, and
+    ``consume(lib, handle, nominal_f, nominal_sens, stepped_f, stepped_sens, col0, ncol, stream)`` on the raw pointers of qfrc_inverse (which is
+    no ABI leaf: the scratch batch carries it behind its leaves) and sensordata."""
     fw, dtype, device, B = c.fw, c.dtype, c.device, c.B
     nside = 2 if centered else 1
-    ncol = c.ns + c.nu
-    written = fw._written_names(m, True)
+    ncol = 3 * c.nv if inverse else c.ns + c.nu
+    written = fw._inverse_names(m) if inverse else fw._written_names(m, True)
 
-    # ---- the nominal step; the caller's pointer table ----
-    y0 = fw._run_native(m, d, bool(fixed_iterations), True) if nominal is None else None
+    # ---- the nominal pass; the caller's pointer table ----
+    if inverse:
+        y0 = fw._run_native(m, d, False, False, None, 0x1F, inverse=True)  # exactly the launches of inverse(m, d)
+    else:
+        y0 = fw._run_native(m, d, bool(fixed_iterations), True) if nominal is None else None
     nm = native.get_native_model(m, device, dtype)
     _bind(nm.lib)
     T = m.tables
@@ -181,35 +207,47 @@ def _drive(name, c: _Call, m: Model, d: Data, centered, fixed_iterations, consum
     # ---- the scratch batch ----
     stream, prev = fw._stream_and_guard(device)
     try:
-        in_idx = tuple(fw._IDX[n] for n in _INPUT_LEAVES if tab.arr[fw._IDX[n]] != 0)
+        in_idx = tuple(fw._IDX[n] for n in (_INVERSE_INPUT_LEAVES if inverse else _INPUT_LEAVES) if tab.arr[fw._IDX[n]] != 0)
         esize = torch.empty((), dtype=dtype).element_size()
         extra_idx = tuple(k for k, n in enumerate(fw._EXTRA_NAMES) if extra and n in extra and tab.xarr[k] != 0)
         extra_bytes = tuple(int(m.nbody) * fw._EXTRA_WIDTH[fw._EXTRA_NAMES[k]] * esize for k in extra_idx)
         out_idx = tuple(fw._IDX[n] for n in written)
         leaf_bytes = _leaf_bytes(fw, nm.leaf_counts, dtype)
-        per_slot = int(leaf_bytes[list(in_idx)].sum() + sum(extra_bytes) + leaf_bytes[list(out_idx)].sum()) + int(nm.work_bytes)
+        tail_bytes = c.nv * esize if inverse else 0
+        per_slot = int(leaf_bytes[list(in_idx)].sum() + sum(extra_bytes) + leaf_bytes[list(out_idx)].sum()) + int(nm.work_bytes) + tail_bytes
         cols = int(max(1, min(ncol, c.budget // max(1, per_slot * B * nside))))
         slots = B * cols * nside
         pool = T.__dict__.setdefault("_fd_scratch", {})
-        key = (device, dtype, stream, slots, in_idx, extra_idx)
+        key = (device, dtype, stream, slots, in_idx, extra_idx) + (("inverse",) if inverse else ())
         scr = pool.pop(key, None)
         if scr is None:
             while len(pool) >= _SCRATCH_KEPT:
                 pool.pop(next(iter(pool)))
-            scr = _make_scratch(fw, in_idx, extra_idx, extra_bytes, out_idx, leaf_bytes, slots, device)
+            scr = _make_scratch(fw, in_idx, extra_idx, extra_bytes, out_idx, leaf_bytes, slots, device, tail_bytes)
         pool[key] = scr  # (most recently used last)
         work = nm.workspace(slots, stream)
         wptr = ctypes.c_void_p(work.data_ptr() if work is not None else None)
-        flags = native.FLAG_FIXED_ITERATIONS if fixed_iterations else 0
+        flags = fw._inverse_flags(m) if inverse else (native.FLAG_FIXED_ITERATIONS if fixed_iterations else 0)
         lib, h, st = nm.lib, nm.handle, ctypes.c_void_p(stream)
         pin, pscr_in, pscr_out, py0 = ctypes.byref(tab.struct), ctypes.byref(scr.inp), ctypes.byref(scr.out), ctypes.byref(nominal)
+        if inverse:
+            sens = fw._IDX["sensordata"]
+            f0, s0 = _ptr(y0.qfrc_inverse), ctypes.c_void_p(int(y0.__dict__["_ptab"].arr[sens]) or None)
+            f1, s1 = ctypes.c_void_p(scr.tail), ctypes.c_void_p(int(np.frombuffer(scr.out, dtype=np.uint64)[sens]) or None)
         for c0 in range(0, ncol, cols):
             n = min(cols, ncol - c0)
-            rc = lib.mjh_fd_perturb(h, pin, pscr_in, B, c0, n, c.eps, int(bool(centered)), st)
-            if rc == 0:
-                rc = lib.mjh_step(h, pscr_in, pscr_out, wptr, B * n * nside, flags, st)
-            if rc == 0:
-                rc = consume(lib, h, pin, py0, pscr_out, c0, n, st)
+            if inverse:
+                rc = lib.mjh_ifd_perturb(h, pin, pscr_in, B, c0, n, c.eps, int(bool(centered)), st)
+                if rc == 0:
+                    rc = lib.mjh_inverse(h, pscr_in, pscr_out, f1, wptr, B * n * nside, flags, st)
+                if rc == 0:
+                    rc = consume(lib, h, f0, s0, f1, s1, c0, n, st)
+            else:
+                rc = lib.mjh_fd_perturb(h, pin, pscr_in, B, c0, n, c.eps, int(bool(centered)), st)
+                if rc == 0:
+                    rc = lib.mjh_step(h, pscr_in, pscr_out, wptr, B * n * nside, flags, st)
+                if rc == 0:
+                    rc = consume(lib, h, pin, py0, pscr_out, c0, n, st)
             if rc != 0:
                 raise RuntimeError(f"native {name} failed ({rc}): {lib.mjh_last_error().decode()}")
     finally:
@@ -263,6 +301,60 @@ def transition_fd(m: Model, d: Data, eps: float = 1e-6, centered: bool = False, 
 
     _drive("transition_fd", c, m, d, centered, fixed_iterations, difference)
     return (A, Bm) + ((C, D) if sensors else ())
+
+
+@_outside_graphs
+def inverse_fd(m: Model, d: Data, eps: float = 1e-6, centered: bool = False, *, sensors: bool = False, max_scratch_bytes: int | None = None):
+    """Finite-difference Jacobians of ``inverse`` (MuJoCo's ``mjd_inverseFD``): ``DfDq, DfDv, DfDa`` or, with ``sensors=True``,
+    ``DfDq, DfDv, DfDa, DsDq, DsDv, DsDa``.
+
+    ``DfD*``: ``S + (nv, nv)``, the derivatives of ``qfrc_inverse`` with respect to ``dq`` (``qpos`` in tangent space), ``qvel`` and ``qacc``;
+    ``DsD*``: ``S + (nsensordata, nv)``, those of ``sensordata``; ``S`` is the batch shape of ``d``.  Rows are outputs, columns what was perturbed,
+    as in ``transition_fd``: ``DfDq[..., i, j] = d qfrc_inverse_i / d dq_j``.  MuJoCo's ``mjd_inverseFD`` stores the transposes.  A model without
+    sensors returns ``DsD*`` with a zero first dimension; with sensors disabled they are zeros (``sensordata`` is then the caller's in every pass).
+
+    Column ``j`` of ``DfDq`` / ``DsDq`` nudges ``qpos`` along dof ``j`` by ``transition_fd``'s rule: slide / hinge joints and free translations add
+    ``eps``, ball joints and the rotation of free joints rotate the quaternion by ``eps`` about the dof's local axis.  Column ``j`` of ``DfDv`` /
+    ``DsDv`` adds ``eps`` to ``qvel[j]``, of ``DfDa`` / ``DsDa`` to ``qacc[j]``.  Nothing else is perturbed: ``act``, ``ctrl``, ``qfrc_applied``,
+    ``xfrc_applied``, ``mocap_*``, ``eq_active``, ``time`` and the leaves an inverse pass carries over are the caller's in every pass.  One-sided
+    differences ``(f+ - f0) / eps`` by default, ``(f+ - f-) / (2 eps)`` with ``centered`` (an extension, as in ``transition_fd``).  Outputs are
+    subtracted plainly: neither ``qfrc_inverse`` nor ``sensordata`` has quaternion rows.
+
+    Every pass, the nominal and the perturbed ones, is exactly what ``inverse(m, d)`` runs -- the same native call with the same flags, the discrete
+    form under ``EnableBit.INVDISCRETE`` included (an RK4 model then raises ``inverse``'s error before anything is launched).  No iterative solver
+    runs in an inverse pass, so the differences carry rounding error only, not the solver tolerance ``transition_fd`` warns about.
+
+    The perturbed passes run as a scratch batch of ``B x columns x (2 if centered else 1)`` environments, in chunks of columns sized so that the
+    scratch stays under ``max_scratch_bytes`` (default ``MAX_SCRATCH_BYTES``; one column at least); it comes from the pool ``transition_fd`` keeps
+    its own in.  Nothing synchronises, everything runs on the caller's current stream, ``d`` is not written.  Under ``torch.vmap`` the call raises
+    ``NotImplementedError``; it is kept out of ``torch.compile`` graphs like ``transition_vjp``.
+
+    Out of scope: MuJoCo's ``flg_actuation`` (the library's inverse pass does not evaluate actuation: ``qfrc_inverse`` is the total force, whatever
+    ``ctrl`` is); ``DmDq``, the derivative of the mass matrix; a vector-Jacobian product or an autograd wrapper; and MuJoCo's stage skipping -- the
+    acceleration columns run whole inverse passes although only the tail depends on ``qacc``.
+    """
+    c = _validate("inverse_fd", m, d, eps, max_scratch_bytes)
+    _on_device(c, m)
+    batch, dtype, device, nv, nsd = c.batch, c.dtype, c.device, c.nv, c.nsd
+    Df = [torch.empty(batch + (nv, nv), dtype=dtype, device=device) for _ in range(3)]
+    Ds = []
+    with_sens = bool(sensors) and c.nsd > 0 and "sensordata" in c.fw._inverse_names(m)
+    if sensors:
+        Ds = [torch.empty(batch + (nsd, nv), dtype=dtype, device=device) for _ in range(3)]
+        if not with_sens:  # (sensors disabled: sensordata is the caller's in every pass)
+            for t in Ds:
+                t.zero_()
+    if c.B == 0 or nv == 0:
+        return tuple(t.zero_() for t in Df) + tuple(Ds)
+    pf = [_ptr(t) for t in Df]
+    ps = [_ptr(t if with_sens else None) for t in (Ds or [None] * 3)]
+    cen = int(bool(centered))
+
+    def difference(lib, h, f0, s0, f1, s1, c0, n, st):
+        return lib.mjh_ifd_difference(h, f0, s0, f1, s1, c.B, c0, n, c.eps, cen, *pf, *ps, st)
+
+    _drive("inverse_fd", c, m, d, centered, False, difference, inverse=True)
+    return tuple(Df) + tuple(Ds)
 
 
 def _cotangent(name, what, g, batch, n, dtype, device):

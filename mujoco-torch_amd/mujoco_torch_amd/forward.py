@@ -93,6 +93,11 @@ def _inverse_names(m: Model):
     return names
 
 
+def _inverse_flags(m: Model) -> int:
+    """The flags of an ``mjh_inverse`` call: read from the Model of THAT call (not part of the cached blob)."""
+    return native.FLAG_INV_DISCRETE if int(m.opt.enableflags) & int(EnableBit.INVDISCRETE) else 0
+
+
 class _PtrTab:
     """Raw device pointers of one ``Data``'s leaves in ABI order (the ``mjhData`` struct the library takes), kept current
     incrementally: ``dirty`` holds the leaves whose tensor may have changed since the pointer was read."""
@@ -389,8 +394,7 @@ def _run_native(m: Model, d: Data, fixed_iterations: bool, step: bool, out: Data
                              "after the first outputs are written (and RK4 reads it in every stage); use distinct buffers")
     flags = native.FLAG_FIXED_ITERATIONS if fixed_iterations else 0
     if inverse:
-        if int(m.opt.enableflags) & int(EnableBit.INVDISCRETE):  # read from the Model of THIS call (not part of the cached blob)
-            flags |= native.FLAG_INV_DISCRETE
+        flags |= _inverse_flags(m)
         if qfrc_inverse is None:
             qfrc_inverse = torch.empty(batch + (int(m.nv),), dtype=dtype, device=device)
         elif qfrc_inverse.dtype != dtype or qfrc_inverse.device != device or qfrc_inverse.numel() != B * int(m.nv) or not qfrc_inverse.is_contiguous():
