@@ -18,6 +18,7 @@
  *   mjh_postconstraint <- MuJoCo's mj_rnePostConstraint / mj_subtreeVel (MJX smooth.rne_postconstraint / subtree_vel; the reference has no counterpart)
  *   mjh_contact_sensors <- MuJoCo's mj_contactForce (MJX support.contact_force) and its touch / framelinacc / frameangacc sensors (the reference evaluates none of them)
  *   mjh_energy         <- MuJoCo's mj_energyPos / mj_energyVel and its joint / tendon limit and energy sensors (the reference evaluates none of them)
+ *   mjh_geom_distance  <- MuJoCo's mj_geomDistance: signed distance and nearest points of geom pairs (the reference has no counterpart)
  *   mjh_jacobian       <- MuJoCo's mj_jacBody .. mj_jacGeom (as products), mj_jacDot, mj_jacSubtreeCom, mj_angmomMat (the reference has support.jac alone)
  *   mjh_integrate      <- derivative.deriv_smooth_vel, forward._implicit (implicitfast), forward._euler and their _advance, on a finished pass (_src/derivative.py:22-68, forward.py:255-328, 404-416)
  *
@@ -45,7 +46,7 @@
 extern "C" {
 #endif
 
-#define MJH_ABI_VERSION 20
+#define MJH_ABI_VERSION 21
 
 /* ---- dtype / flags ------------------------------------------------------------------- */
 #define MJH_F64 0
@@ -112,6 +113,7 @@ extern "C" {
 #define MJH_KERNEL_QUADRIC 44    /* plane-ellipsoid / plane-cylinder narrow phase (one lane per (environment, pair))   */
 #define MJH_KERNEL_IFD_PERTURB 45 /* mjh_ifd_perturb: the perturbed input leaves of a chunk of inverse-dynamics columns */
 #define MJH_KERNEL_IFD_DIFFERENCE 46 /* mjh_ifd_difference: the columns of DfDq, DfDv, DfDa (DsDq, DsDv, DsDa) from the chunk */
+#define MJH_KERNEL_GEOM_DISTANCE 47 /* mjh_geom_distance: signed distance and nearest points of geom pairs (one lane per (pair, environment)) */
 
 /* pair-function ids of the static collision table (collision_driver.py:106-125) */
 #define MJH_FN_PLANE_SPHERE 0
@@ -477,6 +479,16 @@ typedef struct mjhRayCands {
 int mjh_ray(const mjhModel* m, const void* geom_xpos, const void* geom_xmat, const void* pnt, int64_t pnt_env, int64_t pnt_ray, const void* vec,
             int64_t vec_env, int64_t vec_ray, int64_t B, int64_t R, const mjhRayCands* cands, void* dist, int64_t* geomid, void* hip_stream);
 
+/* signed distance and nearest points of geom pairs on a finished pass (MuJoCo's mj_geomDistance; definitions: csrc/mjh_geomdist.h).  geom_xpos [B, ngeom, 3] /
+ * geom_xmat [B, ngeom, 9]: the environments' geom frames; geom_size [ngeom][3]: the sizes to use (read on the device by every call, so value edits of the Model
+ * need no new table); reals are of the model's dtype.  `pairs`: npair rows of four int32 on the device, shared by every environment: geom1, geom2 and their types
+ * (mjtGeom: plane 0, sphere 2, capsule 3, ellipsoid 4, cylinder 5, box 6), written by the caller as the ray candidate table is.  Supported: sphere / capsule / box with each
+ * other, a plane with any of those five; the library does not validate the rows (a geom id outside the model or another type pair gives NaN).  Writes
+ * dist [B, npair] and fromto [B, npair, 6] (the nearest point on geom1, then on geom2: to - from = dist * n, n the unit vector from geom1 towards geom2, dist < 0 when
+ * they overlap); where dist > distmax (>= 0), dist = distmax and fromto = 0.  Returns 0 or a negative code; B == 0 or npair == 0 is a no-op. */
+int mjh_geom_distance(const mjhModel* m, const void* geom_xpos, const void* geom_xmat, const void* geom_size, const int32_t* pairs, int64_t npair, double distmax,
+                      void* dist, void* fromto, int64_t B, void* hip_stream);
+
 /* the scene one mjh_render call draws, built by the caller from the model (render.py:33-114 precompute_render_data).  Every pointer is device memory.
  * `cand`, `tri`, `geom_size`: as mjhRayCands, the VISIBLE geoms ((matid != -1 or rgba alpha != 0) and (matid == -1 or the material's alpha != 0)) in the
  * reference's type-major order; the `nprim` primitive rows come first, the mesh rows (ascending geom id) after them.  Shadow rays test the primitive
@@ -807,7 +819,7 @@ int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsi
 int mjh_model_lds_bytes(const mjhModel* m, int arena);
 
 /* measurement aid used by bench.py for the per-kernel roofline: while enabled, every kernel launch of mjh_step / mjh_forward is
- * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_ifd_perturb, mjh_ifd_difference, mjh_postconstraint, mjh_contact_sensors, mjh_energy, mjh_integrate and mjh_jacobian too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
+ * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_ifd_perturb, mjh_ifd_difference, mjh_postconstraint, mjh_contact_sensors, mjh_energy, mjh_integrate, mjh_jacobian and mjh_geom_distance too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
  * the elapsed milliseconds and the kernel id (MJH_KERNEL_*).  Returns the number of launches (<= max) or a negative code. */
 int mjh_debug_phase_timing(int enable);
 int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
@@ -833,7 +845,8 @@ void mjh_debug_set_stamps(void* dev_ptr);
  * for one query, the dof rows and the body rows the operation reads (DOT: cvel and cdof_dot too; the subtree operations: xipos, ximat for ANGMOM) and the matrices,
  * or, for the *_VEC ids, vec and the 3-vectors.  MJH_KERNEL_QUADRIC: like MJH_KERNEL_CONVEX, the two geom frames of each of its pairs and the pair's contacts.  MJH_KERNEL_IFD_PERTURB / MJH_KERNEL_IFD_DIFFERENCE:
  * per slot, the input leaves an mjh_inverse call of this model can read, read and written (an upper bound: the caller's Data may lack some), and one slot's qfrc_inverse and
- * sensordata read, with [1] = one column of DfD* and DsD*.  Returns 0, or -2 when this model's step does not launch that kernel. */
+ * sensordata read, with [1] = one column of DfD* and DsD*.  MJH_KERNEL_GEOM_DISTANCE (an mjh_geom_distance call): per (pair, environment), the two geom frames and sizes
+ * and the pair's row read, dist and fromto written.  Returns 0, or -2 when this model's step does not launch that kernel. */
 int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes);
 
 /* last error message of the calling thread ("" if none) */

@@ -17,6 +17,7 @@
 #include "mjh_integrate.h"
 #include "mjh_jacobian.h"
 #include "mjh_quadric.h"
+#include "mjh_geomdist.h"
 #include "mjh_instances.h"
 
 #define MJH_CAT_(a, b) a##b
@@ -70,4 +71,7 @@ template __global__ void mjh_quadric_kernel<MJH_INST_REAL>(KArgs<MJH_INST_REAL>)
 #if MJH_INST_GROUP == 30
 template __global__ void mjh_ifd_perturb_kernel<MJH_INST_REAL>(IfdPerturbArgs<MJH_INST_REAL>);
 template __global__ void mjh_ifd_difference_kernel<MJH_INST_REAL>(IfdDiffArgs<MJH_INST_REAL>);
+#endif
+#if MJH_INST_GROUP == 31
+template __global__ void mjh_geomdist_kernel<MJH_INST_REAL>(GeomDistArgs<MJH_INST_REAL>);
 #endif

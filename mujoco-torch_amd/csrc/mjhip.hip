@@ -29,6 +29,7 @@
 #include "mjh_jacobian.h"
 #include "mjh_integrate.h"
 #include "mjh_quadric.h"
+#include "mjh_geomdist.h"
 #include "mjh_instances.h"
 
 // the kernels are compiled in their own translation units (mjh_inst.hip, one per build group): this file is the host side only
@@ -79,6 +80,8 @@ extern template __global__ void mjh_ifd_perturb_kernel<double>(IfdPerturbArgs<do
 extern template __global__ void mjh_ifd_perturb_kernel<float>(IfdPerturbArgs<float>);
 extern template __global__ void mjh_ifd_difference_kernel<double>(IfdDiffArgs<double>);
 extern template __global__ void mjh_ifd_difference_kernel<float>(IfdDiffArgs<float>);
+extern template __global__ void mjh_geomdist_kernel<double>(GeomDistArgs<double>);  // (build group 31)
+extern template __global__ void mjh_geomdist_kernel<float>(GeomDistArgs<float>);
 #undef X_
 #undef S_
 #undef C_
@@ -1401,6 +1404,33 @@ int run_ray(const mjhModel* m, const DevModel<REAL>& M, const void* geom_xpos, c
   return 0;
 }
 
+// signed distance and nearest points of geom pairs (mjh_geomdist.h): one lane per (pair, environment), items pair-major, one-wave workgroups
+template <typename REAL>
+int run_geom_distance(const DevModel<REAL>& M, const void* geom_xpos, const void* geom_xmat, const void* geom_size, const int32_t* pairs, int64_t npair,
+                      double distmax, void* dist, void* fromto, int64_t B, void* stream) {
+  if (B < 0 || npair < 0) return fail(-22, "geom_distance: B and npair must be >= 0");
+  if (!(distmax >= 0)) return fail(-22, "geom_distance: distmax must be >= 0");
+  if (B == 0 || npair == 0) return 0;
+  if (npair > (1 << 30)) return fail(-22, "geom_distance: more than 2^30 pairs");
+  if (M.ngeom <= 0) return fail(-22, "geom_distance: the model has no geoms");
+  if (!geom_xpos || !geom_xmat || !geom_size || !pairs || !dist || !fromto) return fail(-22, "geom_distance: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  timing_begin(s);
+  GeomDistArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+  a.geom_xpos = reinterpret_cast<const REAL*>(geom_xpos); a.geom_xmat = reinterpret_cast<const REAL*>(geom_xmat);
+  a.geom_size = reinterpret_cast<const REAL*>(geom_size); a.pairs = pairs;
+  a.dist = reinterpret_cast<REAL*>(dist); a.fromto = reinterpret_cast<REAL*>(fromto);
+  a.B = B; a.ngeom = M.ngeom; a.npair = (int)npair; a.distmax = (REAL)distmax;
+  if (const int rc = launch_cut(B * npair, MJH_WAVE, [&](int64_t first, int64_t n, unsigned grid) {
+        a.item_begin = first; a.item_count = n;
+        hipLaunchKernelGGL((mjh_geomdist_kernel<REAL>), dim3(grid), dim3(MJH_WAVE), 0, s, a);
+      }))
+    return rc;
+  timing_mark(s, MJH_KERNEL_GEOM_DISTANCE);
+  return 0;
+}
+
 // the ray-cast renderer (render.py:719-861): one lane per (environment, output pixel), the candidates' geom frames staged in LDS (mjh_render.h)
 template <typename REAL>
 int run_render(const DevModel<REAL>& M, const void* geom_xpos, const void* geom_xmat, const void* cam_xpos, const void* cam_xmat, const void* light_xpos,
@@ -2062,6 +2092,13 @@ int mjh_ray(const mjhModel* m, const void* geom_xpos, const void* geom_xmat, con
                              : run_ray<float>(m, m->m32, geom_xpos, geom_xmat, pnt, pnt_env, pnt_ray, vec, vec_env, vec_ray, B, R, cands, dist, geomid, stream);
 }
 
+int mjh_geom_distance(const mjhModel* m, const void* geom_xpos, const void* geom_xmat, const void* geom_size, const int32_t* pairs, int64_t npair, double distmax,
+                      void* dist, void* fromto, int64_t B, void* stream) {
+  if (!m) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_geom_distance<double>(m->m64, geom_xpos, geom_xmat, geom_size, pairs, npair, distmax, dist, fromto, B, stream)
+                             : run_geom_distance<float>(m->m32, geom_xpos, geom_xmat, geom_size, pairs, npair, distmax, dist, fromto, B, stream);
+}
+
 int mjh_render(const mjhModel* m, const void* geom_xpos, const void* geom_xmat, const void* cam_xpos, const void* cam_xmat, const void* light_xpos,
                const void* light_xdir, int64_t B, const mjhRenderScene* scene, const mjhRenderParams* params, void* rgb, void* depth, int64_t* seg,
                void* stream) {
@@ -2302,6 +2339,13 @@ static int kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes, b
     const int64_t R = f64 ? 8 : 4, nq = f64 ? m->m64.nq : m->m32.nq, nv = f64 ? m->m64.nv : m->m32.nv, nb = f64 ? m->m64.nbody : m->m32.nbody, nt = f64 ? m->m64.ntendon : m->m32.ntendon;
     read_write_bytes[0] = (nq + nv + 3 * nb + nt + nv * nv) * R;
     read_write_bytes[1] = 2 * R;
+    return 0;
+  }
+  if (kernel == MJH_KERNEL_GEOM_DISTANCE) {  // one (pair, environment) item of mjh_geom_distance: two frames and sizes and the pair's row in, dist and fromto out
+    const int64_t R = f64 ? 8 : 4;
+    if ((f64 ? m->m64.ngeom : m->m32.ngeom) == 0) return -2;
+    read_write_bytes[0] = 30 * R + 16;
+    read_write_bytes[1] = 7 * R;
     return 0;
   }
   if (kernel >= MJH_KERNEL_JACOBIAN_POINT && kernel <= MJH_KERNEL_JACOBIAN_ANGMOM_VEC) {  // mjh_jacobian, per environment for one query: see include/mjhip.h

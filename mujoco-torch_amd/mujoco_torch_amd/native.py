@@ -321,6 +321,10 @@ def load_library(path: str | None = None):
         lib.mjh_render.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 6 + [ctypes.c_int64, ctypes.POINTER(RenderScene), ctypes.POINTER(RenderParams),
                                                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         lib.mjh_render.restype = ctypes.c_int
+    if hasattr(lib, "mjh_geom_distance"):  # (likewise a build from before geom distances)
+        lib.mjh_geom_distance.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_double,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+        lib.mjh_geom_distance.restype = ctypes.c_int
     for symbol, struct in ARGS.items():
         if hasattr(lib, symbol):  # (likewise a build from before that entry point)
             fn = getattr(lib, symbol)
