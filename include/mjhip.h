@@ -19,6 +19,8 @@
  *   mjh_contact_sensors <- MuJoCo's mj_contactForce (MJX support.contact_force) and its touch / framelinacc / frameangacc sensors (the reference evaluates none of them)
  *   mjh_energy         <- MuJoCo's mj_energyPos / mj_energyVel and its joint / tendon limit and energy sensors (the reference evaluates none of them)
  *   mjh_geom_distance  <- MuJoCo's mj_geomDistance: signed distance and nearest points of geom pairs (the reference has no counterpart)
+ *   mjh_qpos_arith     <- MuJoCo's mj_integratePos / mj_differentiatePos / mj_normalizeQuat on plain rows (forward._integrate_pos, math.quat_sub: _src/forward.py:231-252, math.py:276-280)
+ *   mjh_ik_site_step   <- one damped-least-squares iteration of site-pose inverse kinematics (dm_control's qpos_from_site_pose; the reference has no counterpart)
  *   mjh_jacobian       <- MuJoCo's mj_jacBody .. mj_jacGeom (as products), mj_jacDot, mj_jacSubtreeCom, mj_angmomMat (the reference has support.jac alone)
  *   mjh_integrate      <- derivative.deriv_smooth_vel, forward._implicit (implicitfast), forward._euler and their _advance, on a finished pass (_src/derivative.py:22-68, forward.py:255-328, 404-416)
  *
@@ -46,7 +48,7 @@
 extern "C" {
 #endif
 
-#define MJH_ABI_VERSION 21
+#define MJH_ABI_VERSION 22
 
 /* ---- dtype / flags ------------------------------------------------------------------- */
 #define MJH_F64 0
@@ -114,6 +116,8 @@ extern "C" {
 #define MJH_KERNEL_IFD_PERTURB 45 /* mjh_ifd_perturb: the perturbed input leaves of a chunk of inverse-dynamics columns */
 #define MJH_KERNEL_IFD_DIFFERENCE 46 /* mjh_ifd_difference: the columns of DfDq, DfDv, DfDa (DsDq, DsDv, DsDa) from the chunk */
 #define MJH_KERNEL_GEOM_DISTANCE 47 /* mjh_geom_distance: signed distance and nearest points of geom pairs (one lane per (pair, environment)) */
+#define MJH_KERNEL_QPOS_ARITH 48 /* mjh_qpos_arith: qpos (+) dt qvel, (qpos2 (-) qpos1) / dt, quaternion normalisation (one lane per (environment, joint)) */
+#define MJH_KERNEL_IK_SITE 49    /* mjh_ik_site_step: one iteration of site-pose inverse kinematics (one wavefront per environment) */
 
 /* pair-function ids of the static collision table (collision_driver.py:106-125) */
 #define MJH_FN_PLANE_SPHERE 0
@@ -489,6 +493,27 @@ int mjh_ray(const mjhModel* m, const void* geom_xpos, const void* geom_xmat, con
 int mjh_geom_distance(const mjhModel* m, const void* geom_xpos, const void* geom_xmat, const void* geom_size, const int32_t* pairs, int64_t npair, double distmax,
                       void* dist, void* fromto, int64_t B, void* hip_stream);
 
+/* configuration arithmetic on plain rows (definitions: csrc/mjh_qpos.h); joint types and addresses are the model's, reals of the model's dtype, every pointer device
+ * memory.  op MJH_QPOS_INTEGRATE: out [B, nq] = a (+) dt b, a = qpos [B, nq], b = qvel [B, nv] (the step's integrate_pos: quaternions renormalised).
+ * MJH_QPOS_DIFFERENTIATE: out [B, nv] = (b (-) a) / dt, a = qpos1, b = qpos2 [B, nq] (MuJoCo's mj_differentiatePos; dt != 0).  MJH_QPOS_NORMALIZE: out [B, nq] = a with
+ * every ball / free quaternion divided by its norm, (1, 0, 0, 0) where the norm is below 1e-15; b and dt are ignored.  out may not overlap a or b.  Returns 0 or
+ * a negative code; B == 0 is a no-op. */
+#define MJH_QPOS_INTEGRATE 0
+#define MJH_QPOS_DIFFERENTIATE 1
+#define MJH_QPOS_NORMALIZE 2
+int mjh_qpos_arith(const mjhModel* m, int op, const void* a, const void* b, double dt, void* out, int64_t B, void* hip_stream);
+
+/* one damped-least-squares iteration of site-pose inverse kinematics for every environment that is not done (definitions: csrc/mjh_ik.h).  cdof [B, nv, 6],
+ * subtree_com [B, nbody, 3], site_xpos [B, nsite, 3], site_xmat [B, nsite, 9]: the kinematics pass at the current qpos.  `site`: the site, `body` its body (the
+ * caller's site_bodyid[site]).  target_pos (3 reals per environment) / target_quat (4, unit): NULL = absent, not both; pos_stride / quat_stride: elements between
+ * the targets of consecutive environments, 0 for one shared target.  dof_sel [nv] int32 on the device: non-zero = the dof takes part.  params: tol, damping (> 0),
+ * max_update_norm, rot_weight.  In / out: qpos [B, nq]; err_norm [B] reals; steps [B] int32; done [B] bytes (non-zero: the environment is skipped and none of its
+ * entries is touched).  Per environment: err_norm is stored; err_norm < tol sets done; otherwise, unless `last` is non-zero, qpos is advanced by the update and
+ * steps incremented.  Returns 0 or a negative code; B == 0 is a no-op. */
+int mjh_ik_site_step(const mjhModel* m, const void* cdof, const void* subtree_com, const void* site_xpos, const void* site_xmat, int site, int body,
+                     const void* target_pos, int64_t pos_stride, const void* target_quat, int64_t quat_stride, const int32_t* dof_sel, const double* params,
+                     int last, void* qpos, void* err_norm, int32_t* steps, unsigned char* done, int64_t B, void* hip_stream);
+
 /* the scene one mjh_render call draws, built by the caller from the model (render.py:33-114 precompute_render_data).  Every pointer is device memory.
  * `cand`, `tri`, `geom_size`: as mjhRayCands, the VISIBLE geoms ((matid != -1 or rgba alpha != 0) and (matid == -1 or the material's alpha != 0)) in the
  * reference's type-major order; the `nprim` primitive rows come first, the mesh rows (ascending geom id) after them.  Shadow rays test the primitive
@@ -819,7 +844,7 @@ int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsi
 int mjh_model_lds_bytes(const mjhModel* m, int arena);
 
 /* measurement aid used by bench.py for the per-kernel roofline: while enabled, every kernel launch of mjh_step / mjh_forward is
- * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_ifd_perturb, mjh_ifd_difference, mjh_postconstraint, mjh_contact_sensors, mjh_energy, mjh_integrate, mjh_jacobian and mjh_geom_distance too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
+ * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_ifd_perturb, mjh_ifd_difference, mjh_postconstraint, mjh_contact_sensors, mjh_energy, mjh_integrate, mjh_jacobian, mjh_geom_distance, mjh_qpos_arith and mjh_ik_site_step too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
  * the elapsed milliseconds and the kernel id (MJH_KERNEL_*).  Returns the number of launches (<= max) or a negative code. */
 int mjh_debug_phase_timing(int enable);
 int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
@@ -846,7 +871,9 @@ void mjh_debug_set_stamps(void* dev_ptr);
  * or, for the *_VEC ids, vec and the 3-vectors.  MJH_KERNEL_QUADRIC: like MJH_KERNEL_CONVEX, the two geom frames of each of its pairs and the pair's contacts.  MJH_KERNEL_IFD_PERTURB / MJH_KERNEL_IFD_DIFFERENCE:
  * per slot, the input leaves an mjh_inverse call of this model can read, read and written (an upper bound: the caller's Data may lack some), and one slot's qfrc_inverse and
  * sensordata read, with [1] = one column of DfD* and DsD*.  MJH_KERNEL_GEOM_DISTANCE (an mjh_geom_distance call): per (pair, environment), the two geom frames and sizes
- * and the pair's row read, dist and fromto written.  Returns 0, or -2 when this model's step does not launch that kernel. */
+ * and the pair's row read, dist and fromto written.  MJH_KERNEL_QPOS_ARITH (an integrate call of mjh_qpos_arith): per environment, qpos and qvel read, qpos written.
+ * MJH_KERNEL_IK_SITE (an updating mjh_ik_site_step call with both targets): per environment, cdof, the site's frame, its root's subtree_com, the targets, qpos and the
+ * three state words read, qpos and the state words written.  Returns 0, or -2 when this model's step does not launch that kernel. */
 int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes);
 
 /* last error message of the calling thread ("" if none) */

@@ -18,6 +18,8 @@
 #include "mjh_jacobian.h"
 #include "mjh_quadric.h"
 #include "mjh_geomdist.h"
+#include "mjh_qpos.h"
+#include "mjh_ik.h"
 #include "mjh_instances.h"
 
 #define MJH_CAT_(a, b) a##b
@@ -74,4 +76,10 @@ template __global__ void mjh_ifd_difference_kernel<MJH_INST_REAL>(IfdDiffArgs<MJ
 #endif
 #if MJH_INST_GROUP == 31
 template __global__ void mjh_geomdist_kernel<MJH_INST_REAL>(GeomDistArgs<MJH_INST_REAL>);
+#endif
+#if MJH_INST_GROUP == 32
+template __global__ void mjh_qpos_arith_kernel<MJH_INST_REAL>(QposArithArgs<MJH_INST_REAL>);
+template __global__ void mjh_ik_site_kernel<MJH_INST_REAL, 1>(IkSiteArgs<MJH_INST_REAL>);
+template __global__ void mjh_ik_site_kernel<MJH_INST_REAL, 2>(IkSiteArgs<MJH_INST_REAL>);
+template __global__ void mjh_ik_site_kernel<MJH_INST_REAL, 3>(IkSiteArgs<MJH_INST_REAL>);
 #endif

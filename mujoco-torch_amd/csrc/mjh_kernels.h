@@ -3762,6 +3762,7 @@ struct Env {
   }
 
   // ---- integrators (forward.py:231-370) ---------------------------------------------------------------------------------------------------------------------------
+  // (mjh_qpos.h's qpos_integrate_joint restates the body of this loop for mjh_qpos_arith / mjh_ik_site_step: keep the two in step -- tests/test_qpos.py holds them together)
   __device__ __forceinline__ void integrate_pos(const REAL* qpos, const REAL* qvel, REAL dt, REAL* o) {  // :231-252, one lane per joint
     for (int j = lane(); j < M.njnt; j += W) {
       const int t = M.jnt_type[j], qa = M.jnt_qposadr[j], da = M.jnt_dofadr[j];

@@ -30,6 +30,8 @@
 #include "mjh_integrate.h"
 #include "mjh_quadric.h"
 #include "mjh_geomdist.h"
+#include "mjh_qpos.h"
+#include "mjh_ik.h"
 #include "mjh_instances.h"
 
 // the kernels are compiled in their own translation units (mjh_inst.hip, one per build group): this file is the host side only
@@ -82,6 +84,15 @@ extern template __global__ void mjh_ifd_difference_kernel<double>(IfdDiffArgs<do
 extern template __global__ void mjh_ifd_difference_kernel<float>(IfdDiffArgs<float>);
 extern template __global__ void mjh_geomdist_kernel<double>(GeomDistArgs<double>);  // (build group 31)
 extern template __global__ void mjh_geomdist_kernel<float>(GeomDistArgs<float>);
+extern template __global__ void mjh_qpos_arith_kernel<double>(QposArithArgs<double>);  // (build group 32)
+extern template __global__ void mjh_qpos_arith_kernel<float>(QposArithArgs<float>);
+#define IK_(R)                                                                  \
+  extern template __global__ void mjh_ik_site_kernel<R, 1>(IkSiteArgs<R>);      \
+  extern template __global__ void mjh_ik_site_kernel<R, 2>(IkSiteArgs<R>);      \
+  extern template __global__ void mjh_ik_site_kernel<R, 3>(IkSiteArgs<R>);
+IK_(double)
+IK_(float)
+#undef IK_
 #undef X_
 #undef S_
 #undef C_
@@ -1431,6 +1442,71 @@ int run_geom_distance(const DevModel<REAL>& M, const void* geom_xpos, const void
   return 0;
 }
 
+// configuration arithmetic (mjh_qpos.h): one lane per (environment, joint), environment-major, one-wave workgroups
+template <typename REAL>
+int run_qpos_arith(const DevModel<REAL>& M, int op, const void* qa, const void* qb, double dt, void* out, int64_t B, void* stream) {
+  if (op != MJH_QPOS_INTEGRATE && op != MJH_QPOS_DIFFERENTIATE && op != MJH_QPOS_NORMALIZE) return fail(-22, "qpos_arith: unknown op");
+  if (B < 0) return fail(-22, "qpos_arith: B must be >= 0");
+  if (op == MJH_QPOS_DIFFERENTIATE && !(dt != 0)) return fail(-22, "qpos_arith: differentiate needs dt != 0");
+  if (op != MJH_QPOS_NORMALIZE && !(dt == dt)) return fail(-22, "qpos_arith: dt is NaN");
+  if (B == 0 || M.njnt == 0) return 0;
+  if (B > ((int64_t)1 << 40)) return fail(-22, "qpos_arith: more than 2^40 environments");
+  if (!qa || !out || (op != MJH_QPOS_NORMALIZE && !qb)) return fail(-22, "qpos_arith: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  timing_begin(s);
+  QposArithArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+  a.a = reinterpret_cast<const REAL*>(qa); a.b = reinterpret_cast<const REAL*>(qb); a.out = reinterpret_cast<REAL*>(out);
+  a.jnt_type = M.jnt_type; a.jnt_qposadr = M.jnt_qposadr; a.jnt_dofadr = M.jnt_dofadr;
+  a.njnt = M.njnt; a.nq = M.nq; a.nv = M.nv; a.op = op; a.dt = (REAL)dt;
+  if (const int rc = launch_cut(B * M.njnt, MJH_WAVE, [&](int64_t first, int64_t n, unsigned grid) {
+        a.item_begin = first; a.item_count = n;
+        hipLaunchKernelGGL((mjh_qpos_arith_kernel<REAL>), dim3(grid), dim3(MJH_WAVE), 0, s, a);
+      }))
+    return rc;
+  timing_mark(s, MJH_KERNEL_QPOS_ARITH);
+  return 0;
+}
+
+// one iteration of site-pose inverse kinematics (mjh_ik.h): one one-wave workgroup per environment
+template <typename REAL>
+int run_ik_site_step(const DevModel<REAL>& M, const void* cdof, const void* subtree_com, const void* site_xpos, const void* site_xmat, int site, int body,
+                     const void* target_pos, int64_t pos_stride, const void* target_quat, int64_t quat_stride, const int32_t* dof_sel, const double* params,
+                     int last, void* qpos, void* err_norm, int32_t* steps, unsigned char* done, int64_t B, void* stream) {
+  if (B < 0) return fail(-22, "ik_site_step: B must be >= 0");
+  if (M.nv <= 0 || M.nsite <= 0) return fail(-22, "ik_site_step: the model has no dofs or no sites");
+  if (site < 0 || site >= M.nsite || body < 0 || body >= M.nbody) return fail(-22, "ik_site_step: site or body outside the model");
+  if (!target_pos && !target_quat) return fail(-22, "ik_site_step: neither target given");
+  if ((pos_stride != 0 && pos_stride != 3) || (quat_stride != 0 && quat_stride != 4)) return fail(-22, "ik_site_step: a target stride is 0 (shared) or the target's length");
+  if (!params) return fail(-22, "ik_site_step: null pointer");
+  if (!(params[1] > 0)) return fail(-22, "ik_site_step: damping must be > 0");
+  if (!(params[2] >= 0) || !(params[3] >= 0) || !(params[0] == params[0])) return fail(-22, "ik_site_step: tol, max_update_norm, rot_weight");
+  if (B == 0) return 0;
+  if (!cdof || !subtree_com || !site_xpos || !site_xmat || !dof_sel || !qpos || !err_norm || !steps || !done) return fail(-22, "ik_site_step: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  timing_begin(s);
+  IkSiteArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+  a.cdof = reinterpret_cast<const REAL*>(cdof); a.subtree_com = reinterpret_cast<const REAL*>(subtree_com);
+  a.site_xpos = reinterpret_cast<const REAL*>(site_xpos); a.site_xmat = reinterpret_cast<const REAL*>(site_xmat);
+  a.target_pos = reinterpret_cast<const REAL*>(target_pos); a.target_quat = reinterpret_cast<const REAL*>(target_quat);
+  a.sel = dof_sel; a.qpos = reinterpret_cast<REAL*>(qpos); a.err_norm = reinterpret_cast<REAL*>(err_norm); a.steps = steps; a.done = done;
+  a.body_dofmask = M.body_dofmask; a.body_rootid = M.body_rootid; a.jnt_type = M.jnt_type; a.jnt_qposadr = M.jnt_qposadr; a.jnt_dofadr = M.jnt_dofadr;
+  a.pos_stride = pos_stride; a.quat_stride = quat_stride;
+  a.nv = M.nv; a.nq = M.nq; a.njnt = M.njnt; a.nbody = M.nbody; a.nsite = M.nsite; a.mask_words = M.mask_words; a.site = site; a.body = body; a.last = last != 0;
+  a.tol = (REAL)params[0]; a.damping = (REAL)params[1]; a.max_update_norm = (REAL)params[2]; a.rot_weight = (REAL)params[3];
+  const int mode = (target_pos ? 1 : 0) | (target_quat ? 2 : 0);
+  if (const int rc = launch_cut(B, 1, [&](int64_t first, int64_t, unsigned grid) {
+        a.env_begin = first;
+        if (mode == 1) hipLaunchKernelGGL((mjh_ik_site_kernel<REAL, 1>), dim3(grid), dim3(MJH_WAVE), 0, s, a);
+        else if (mode == 2) hipLaunchKernelGGL((mjh_ik_site_kernel<REAL, 2>), dim3(grid), dim3(MJH_WAVE), 0, s, a);
+        else hipLaunchKernelGGL((mjh_ik_site_kernel<REAL, 3>), dim3(grid), dim3(MJH_WAVE), 0, s, a);
+      }))
+    return rc;
+  timing_mark(s, MJH_KERNEL_IK_SITE);
+  return 0;
+}
+
 // the ray-cast renderer (render.py:719-861): one lane per (environment, output pixel), the candidates' geom frames staged in LDS (mjh_render.h)
 template <typename REAL>
 int run_render(const DevModel<REAL>& M, const void* geom_xpos, const void* geom_xmat, const void* cam_xpos, const void* cam_xmat, const void* light_xpos,
@@ -2099,6 +2175,21 @@ int mjh_geom_distance(const mjhModel* m, const void* geom_xpos, const void* geom
                              : run_geom_distance<float>(m->m32, geom_xpos, geom_xmat, geom_size, pairs, npair, distmax, dist, fromto, B, stream);
 }
 
+int mjh_qpos_arith(const mjhModel* m, int op, const void* a, const void* b, double dt, void* out, int64_t B, void* stream) {
+  if (!m) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_qpos_arith<double>(m->m64, op, a, b, dt, out, B, stream) : run_qpos_arith<float>(m->m32, op, a, b, dt, out, B, stream);
+}
+
+int mjh_ik_site_step(const mjhModel* m, const void* cdof, const void* subtree_com, const void* site_xpos, const void* site_xmat, int site, int body,
+                     const void* target_pos, int64_t pos_stride, const void* target_quat, int64_t quat_stride, const int32_t* dof_sel, const double* params,
+                     int last, void* qpos, void* err_norm, int32_t* steps, unsigned char* done, int64_t B, void* stream) {
+  if (!m) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_ik_site_step<double>(m->m64, cdof, subtree_com, site_xpos, site_xmat, site, body, target_pos, pos_stride, target_quat, quat_stride,
+                                                        dof_sel, params, last, qpos, err_norm, steps, done, B, stream)
+                             : run_ik_site_step<float>(m->m32, cdof, subtree_com, site_xpos, site_xmat, site, body, target_pos, pos_stride, target_quat, quat_stride,
+                                                       dof_sel, params, last, qpos, err_norm, steps, done, B, stream);
+}
+
 int mjh_render(const mjhModel* m, const void* geom_xpos, const void* geom_xmat, const void* cam_xpos, const void* cam_xmat, const void* light_xpos,
                const void* light_xdir, int64_t B, const mjhRenderScene* scene, const mjhRenderParams* params, void* rgb, void* depth, int64_t* seg,
                void* stream) {
@@ -2346,6 +2437,20 @@ static int kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes, b
     if ((f64 ? m->m64.ngeom : m->m32.ngeom) == 0) return -2;
     read_write_bytes[0] = 30 * R + 16;
     read_write_bytes[1] = 7 * R;
+    return 0;
+  }
+  if (kernel == MJH_KERNEL_QPOS_ARITH) {  // one environment of an integrate call of mjh_qpos_arith: qpos and qvel in, qpos out
+    const int64_t R = f64 ? 8 : 4, nq = f64 ? m->m64.nq : m->m32.nq, nv = f64 ? m->m64.nv : m->m32.nv;
+    if (nq == 0) return -2;
+    read_write_bytes[0] = (nq + nv) * R;
+    read_write_bytes[1] = nq * R;
+    return 0;
+  }
+  if (kernel == MJH_KERNEL_IK_SITE) {  // one environment of an updating mjh_ik_site_step call with both targets
+    const int64_t R = f64 ? 8 : 4, nq = f64 ? m->m64.nq : m->m32.nq, nv = f64 ? m->m64.nv : m->m32.nv;
+    if (nv == 0 || (f64 ? m->m64.nsite : m->m32.nsite) == 0) return -2;
+    read_write_bytes[0] = (6 * nv + 12 + 3 + 7 + nq + 1) * R + 4 + 1;
+    read_write_bytes[1] = (nq + 1) * R + 4 + 1;
     return 0;
   }
   if (kernel >= MJH_KERNEL_JACOBIAN_POINT && kernel <= MJH_KERNEL_JACOBIAN_ANGMOM_VEC) {  // mjh_jacobian, per environment for one query: see include/mjhip.h

@@ -262,7 +262,8 @@ def transition_fd(m: Model, d: Data, eps: float = 1e-6, centered: bool = False, 
     With the state ``x = [dq (nv, tangent space), qvel (nv), act (na)]``, ``ns = 2 nv + na``, ``u = ctrl`` and ``y`` the state after one step:
     ``A = dy/dx``: ``S + (ns, ns)``, ``B = dy/du``: ``S + (ns, nu)``, ``C = dsensordata/dx``: ``S + (nsensordata, ns)``, ``D = dsensordata/du``:
     ``S + (nsensordata, nu)``, ``S`` being the batch shape of ``d``.  Rows are outputs, columns what was perturbed: ``A[..., i, j] = dy_i / dx_j``.
-    A model without sensors returns ``C``, ``D`` with a zero first dimension.
+    A model without sensors returns ``C``, ``D`` with a zero first dimension.  ``state_sub`` / ``state_add`` (``qpos.py``) form differences and sums of physics
+    states ``[qpos, qvel, act]`` in these coordinates: ``state_sub(m, step(state_add(m, x, dx)), step(x))`` is ``A dx`` to first order.
 
     Every other input of the step (``time``, ``qacc_warmstart``, ``mocap_*``, ``qfrc_applied``, ``xfrc_applied``, ``eq_active`` ...) is the caller's,
     in the nominal and in every perturbed step.  ``qpos`` is perturbed and differenced in tangent space: slide / hinge joints and free translations

@@ -325,6 +325,15 @@ def load_library(path: str | None = None):
         lib.mjh_geom_distance.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_double,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
         lib.mjh_geom_distance.restype = ctypes.c_int
+    if hasattr(lib, "mjh_qpos_arith"):  # (likewise a build from before the configuration arithmetic and the site IK)
+        lib.mjh_qpos_arith.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+        lib.mjh_qpos_arith.restype = ctypes.c_int
+    if hasattr(lib, "mjh_ik_site_step"):
+        lib.mjh_ik_site_step.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                                                   ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
+                                                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                                                   ctypes.c_void_p]
+        lib.mjh_ik_site_step.restype = ctypes.c_int
     for symbol, struct in ARGS.items():
         if hasattr(lib, symbol):  # (likewise a build from before that entry point)
             fn = getattr(lib, symbol)
