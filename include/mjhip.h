@@ -21,6 +21,7 @@
  *   mjh_geom_distance  <- MuJoCo's mj_geomDistance: signed distance and nearest points of geom pairs (the reference has no counterpart)
  *   mjh_qpos_arith     <- MuJoCo's mj_integratePos / mj_differentiatePos / mj_normalizeQuat on plain rows (forward._integrate_pos, math.quat_sub: _src/forward.py:231-252, math.py:276-280)
  *   mjh_ik_site_step   <- one damped-least-squares iteration of site-pose inverse kinematics (dm_control's qpos_from_site_pose; the reference has no counterpart)
+ *   mjh_constraint_space <- MuJoCo's mj_mulJacVec / mj_mulJacTVec / mj_constraintUpdate and the Delassus matrix efc_AR, by the reference solver's definitions (_src/solver.py:293-357, 501-508)
  *   mjh_jacobian       <- MuJoCo's mj_jacBody .. mj_jacGeom (as products), mj_jacDot, mj_jacSubtreeCom, mj_angmomMat (the reference has support.jac alone)
  *   mjh_integrate      <- derivative.deriv_smooth_vel, forward._implicit (implicitfast), forward._euler and their _advance, on a finished pass (_src/derivative.py:22-68, forward.py:255-328, 404-416)
  *
@@ -48,7 +49,7 @@
 extern "C" {
 #endif
 
-#define MJH_ABI_VERSION 22
+#define MJH_ABI_VERSION 23
 
 /* ---- dtype / flags ------------------------------------------------------------------- */
 #define MJH_F64 0
@@ -118,6 +119,10 @@ extern "C" {
 #define MJH_KERNEL_GEOM_DISTANCE 47 /* mjh_geom_distance: signed distance and nearest points of geom pairs (one lane per (pair, environment)) */
 #define MJH_KERNEL_QPOS_ARITH 48 /* mjh_qpos_arith: qpos (+) dt qvel, (qpos2 (-) qpos1) / dt, quaternion normalisation (one lane per (environment, joint)) */
 #define MJH_KERNEL_IK_SITE 49    /* mjh_ik_site_step: one iteration of site-pose inverse kinematics (one wavefront per environment) */
+#define MJH_KERNEL_EFC_MUL_J 50  /* mjh_constraint_space (50 + op), MJH_EFC_MUL_J: efc_J products                        */
+#define MJH_KERNEL_EFC_MUL_JT 51 /* ... MJH_EFC_MUL_JT: products with its transpose                                      */
+#define MJH_KERNEL_EFC_UPDATE 52 /* ... MJH_EFC_UPDATE: jar, states, forces, cost and gradient of a qacc (one fused kernel) */
+#define MJH_KERNEL_EFC_AR 53     /* ... MJH_EFC_AR: the Delassus matrix J M^-1 J^T + R and b                              */
 
 /* pair-function ids of the static collision table (collision_driver.py:106-125) */
 #define MJH_FN_PLANE_SPHERE 0
@@ -729,6 +734,66 @@ int mjh_integrate(const mjhModel* m, const mjhIntegrateArgs* args, void* hip_str
  * fit a workgroup's LDS (mjh_integrate refuses such a model), -22 for a bad argument. */
 int mjh_integrate_plan(int nv, int nu, int ntendon, int real_bytes, int* lanes_envs_chunk_lds);
 
+/* mjh_constraint_space operations (mjhConstraintSpaceArgs.op); MJH_KERNEL_EFC_MUL_J + op is the kernel id the timing aid reports */
+#define MJH_EFC_MUL_J 0
+#define MJH_EFC_MUL_JT 1
+#define MJH_EFC_UPDATE 2
+#define MJH_EFC_AR 3
+
+/* one mjh_constraint_space call (definitions: csrc/mjh_efc.h).  Every pointer is device memory, reals of the model's dtype unless stated, batch-major over B
+ * environments; the leaves are a finished pass's: efc_J [B, nefc, nv], efc_D / efc_aref / efc_frictionloss [B, nefc], qM / qLD [B, nv, nv], qfrc_smooth /
+ * qacc_smooth [B, nv].  Vector j of environment e reads vec[e * vec_env + j * vec_k + i] (element strides; 0: shared).  A NULL output is not an option: every
+ * output of the op is written.  Per op (outputs environment-major, contiguous):
+ *   MUL_J   efc_J, vec (nv entries each)   -> out [B, K, nefc] = J vec_j
+ *   MUL_JT  efc_J, vec (nefc entries each) -> out [B, K, nv] = J^T vec_j
+ *   UPDATE  efc_J, efc_D, efc_frictionloss and either
+ *           qacc [B, nv] with efc_aref, qM, qfrc_smooth, qacc_smooth -> jar = J qacc - aref, efc_force [B, nefc], efc_state [B, nefc] int32 (0 satisfied, 1 quadratic,
+ *             2 linear-neg, 3 linear-pos), qfrc_constraint [B, nv] = J^T efc_force, cost / gauss / grad_norm [B], grad [B, nv]; or
+ *           jar_in [B, nefc] with qacc NULL (MuJoCo's mj_constraintUpdate) -> efc_force, efc_state, qfrc_constraint, cost (without the Gauss term)
+ *           ne_nf: the equality and friction rows, always quadratic unless linear; floss != 0: the friction rows have their linear zones; grad_norm =
+ *           |grad| / (meaninertia * max(1, nv))
+ *   AR      efc_J, efc_D, efc_aref, qLD (lower triangle), qacc_smooth -> AR [B, nefc, nefc] = J (L L^T)^-1 J^T + diag(D > 0 ? 1 / D : 0), both triangles
+ *             from one computed value; b [B, nefc] = J qacc_smooth - aref
+ * K >= 1 (MUL_J, MUL_JT); K * max(nv, nefc) must stay below 2^30. */
+typedef struct mjhConstraintSpaceArgs {
+  int32_t op;
+  int32_t K, ne_nf, floss;
+  int64_t B;
+  double meaninertia;
+  const void* efc_J;
+  const void* efc_D;
+  const void* efc_aref;
+  const void* efc_frictionloss;
+  const void* qM;
+  const void* qLD;
+  const void* qfrc_smooth;
+  const void* qacc_smooth;
+  const void* qacc;
+  const void* jar_in;
+  const void* vec;
+  int64_t vec_env, vec_k;
+  void* out;
+  void* jar;
+  void* efc_force;
+  int32_t* efc_state;
+  void* qfrc_constraint;
+  void* cost;
+  void* gauss;
+  void* grad;
+  void* grad_norm;
+  void* AR;
+  void* b;
+} mjhConstraintSpaceArgs;
+
+/* the constraint-space functions on a finished pass (see mjhConstraintSpaceArgs).  Runs on hip_stream without host synchronisation.  Returns 0 or a negative
+ * code (AR: -12 when qLD's triangle and two row chunks do not fit the LDS of a workgroup); B == 0, nv == 0 and nefc == 0 are no-ops. */
+int mjh_constraint_space(const mjhModel* m, const mjhConstraintSpaceArgs* args, void* hip_stream);
+
+/* the chunk plan mjh_constraint_space uses for operation op on a model of nv dofs and nefc rows in reals of real_bytes (4 / 8) bytes, a host computation (no
+ * device is touched): out = {rows of efc_J per LDS chunk, number of chunks, rows of the last chunk, bytes of LDS per workgroup}.  Returns 0, -12 when the
+ * operation does not fit a workgroup's LDS, -22 for a bad argument. */
+int mjh_constraint_space_plan(int op, int nv, int nefc, int real_bytes, int* chunk_nchunk_last_lds);
+
 /* mjh_jacobian operations (mjhJacobianArgs.op); MJH_KERNEL_JACOBIAN_POINT + op (matrix form) or MJH_KERNEL_JACOBIAN_POINT_VEC + op (product form) is the kernel id
  * the timing aid reports */
 #define MJH_JACOBIAN_POINT 0
@@ -844,7 +909,7 @@ int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsi
 int mjh_model_lds_bytes(const mjhModel* m, int arena);
 
 /* measurement aid used by bench.py for the per-kernel roofline: while enabled, every kernel launch of mjh_step / mjh_forward is
- * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_ifd_perturb, mjh_ifd_difference, mjh_postconstraint, mjh_contact_sensors, mjh_energy, mjh_integrate, mjh_jacobian, mjh_geom_distance, mjh_qpos_arith and mjh_ik_site_step too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
+ * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_ifd_perturb, mjh_ifd_difference, mjh_postconstraint, mjh_contact_sensors, mjh_energy, mjh_integrate, mjh_jacobian, mjh_geom_distance, mjh_qpos_arith, mjh_ik_site_step and mjh_constraint_space too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
  * the elapsed milliseconds and the kernel id (MJH_KERNEL_*).  Returns the number of launches (<= max) or a negative code. */
 int mjh_debug_phase_timing(int enable);
 int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
@@ -873,7 +938,9 @@ void mjh_debug_set_stamps(void* dev_ptr);
  * sensordata read, with [1] = one column of DfD* and DsD*.  MJH_KERNEL_GEOM_DISTANCE (an mjh_geom_distance call): per (pair, environment), the two geom frames and sizes
  * and the pair's row read, dist and fromto written.  MJH_KERNEL_QPOS_ARITH (an integrate call of mjh_qpos_arith): per environment, qpos and qvel read, qpos written.
  * MJH_KERNEL_IK_SITE (an updating mjh_ik_site_step call with both targets): per environment, cdof, the site's frame, its root's subtree_com, the targets, qpos and the
- * three state words read, qpos and the state words written.  Returns 0, or -2 when this model's step does not launch that kernel. */
+ * three state words read, qpos and the state words written.  MJH_KERNEL_EFC_MUL_J .. MJH_KERNEL_EFC_AR (an mjh_constraint_space call): per environment, efc_J once and
+ * one vector in, one out (MUL_J, MUL_JT); efc_J, the three row leaves, qM and the three dof vectors in, the outputs of the qacc form out (UPDATE); efc_J once (a model of one
+ * chunk), qLD, efc_D, efc_aref and qacc_smooth in, AR and b out (AR); -2 for a model without dofs or rows.  Returns 0, or -2 when this model's step does not launch that kernel. */
 int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes);
 
 /* last error message of the calling thread ("" if none) */

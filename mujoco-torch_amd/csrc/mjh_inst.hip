@@ -20,6 +20,7 @@
 #include "mjh_geomdist.h"
 #include "mjh_qpos.h"
 #include "mjh_ik.h"
+#include "mjh_efc.h"
 #include "mjh_instances.h"
 
 #define MJH_CAT_(a, b) a##b
@@ -82,4 +83,10 @@ template __global__ void mjh_qpos_arith_kernel<MJH_INST_REAL>(QposArithArgs<MJH_
 template __global__ void mjh_ik_site_kernel<MJH_INST_REAL, 1>(IkSiteArgs<MJH_INST_REAL>);
 template __global__ void mjh_ik_site_kernel<MJH_INST_REAL, 2>(IkSiteArgs<MJH_INST_REAL>);
 template __global__ void mjh_ik_site_kernel<MJH_INST_REAL, 3>(IkSiteArgs<MJH_INST_REAL>);
+#endif
+#if MJH_INST_GROUP == 33
+template __global__ void mjh_efc_mulj_kernel<MJH_INST_REAL>(EfcArgs<MJH_INST_REAL>);
+template __global__ void mjh_efc_muljt_kernel<MJH_INST_REAL>(EfcArgs<MJH_INST_REAL>);
+template __global__ void mjh_efc_update_kernel<MJH_INST_REAL>(EfcArgs<MJH_INST_REAL>);
+template __global__ void mjh_efc_ar_kernel<MJH_INST_REAL>(EfcArgs<MJH_INST_REAL>);
 #endif

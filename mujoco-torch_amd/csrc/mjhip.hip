@@ -32,6 +32,7 @@
 #include "mjh_geomdist.h"
 #include "mjh_qpos.h"
 #include "mjh_ik.h"
+#include "mjh_efc.h"
 #include "mjh_instances.h"
 
 // the kernels are compiled in their own translation units (mjh_inst.hip, one per build group): this file is the host side only
@@ -93,6 +94,14 @@ extern template __global__ void mjh_qpos_arith_kernel<float>(QposArithArgs<float
 IK_(double)
 IK_(float)
 #undef IK_
+#define EFC_(R)                                                               \
+  extern template __global__ void mjh_efc_mulj_kernel<R>(EfcArgs<R>);         \
+  extern template __global__ void mjh_efc_muljt_kernel<R>(EfcArgs<R>);        \
+  extern template __global__ void mjh_efc_update_kernel<R>(EfcArgs<R>);       \
+  extern template __global__ void mjh_efc_ar_kernel<R>(EfcArgs<R>);
+EFC_(double)  // (build group 33)
+EFC_(float)
+#undef EFC_
 #undef X_
 #undef S_
 #undef C_
@@ -1622,6 +1631,74 @@ int run_support(const mjhModel* m, const DevModel<REAL>& M, const mjhSupportArgs
   return 0;
 }
 
+// The chunk plan of mjh_constraint_space (mjh_efc.h): rows of efc_J per LDS chunk (a staged row takes nv | 1 reals), the number of chunks, the rows of the last
+// one and the LDS of a workgroup.  MUL_J: the chunk alone; MUL_JT: and 64 partial sums.  UPDATE: qacc, J^T force, M qacc, the chunk's forces, the chunk, which also stages qM, and 64 partial sums.
+// AR: the packed triangle of qLD and one chunk, two when there is more than one.  Returns 0, or -12 when AR does not fit kMaxLds.
+static int efc_plan(int op, int nv, int nefc, int real_bytes, int* out) {
+  constexpr int64_t kChunkBytes = 16 * 1024, kMaxLds = 160 * 1024;  // (a workgroup is one wavefront: small chunks keep many of them on a compute unit)
+  const int64_t ld = nv | 1, rb = ld * real_bytes;
+  const int64_t most = op == MJH_EFC_UPDATE ? std::max(nefc, nv) : nefc;  // rows worth holding at once
+  int64_t chunk = kChunkBytes / rb;
+  chunk = std::max<int64_t>(1, std::min(chunk, std::max<int64_t>(most, 1)));
+  const int64_t nchunk = nefc > 0 ? (nefc + chunk - 1) / chunk : 0, last = nefc > 0 ? nefc - (nchunk - 1) * chunk : 0;
+  int64_t reals = chunk * ld;
+  if (op == MJH_EFC_UPDATE) reals += 3 * (int64_t)nv + chunk;
+  if (op == MJH_EFC_UPDATE || op == MJH_EFC_MUL_JT) reals += MJH_WAVE;  // the partial sums of efc_jt_accumulate
+  if (op == MJH_EFC_AR) reals = (int64_t)nv * (nv + 1) / 2 + (nchunk > 1 ? 2 : 1) * chunk * ld;
+  const int64_t lds = (reals * real_bytes + 15) & ~(int64_t)15;
+  if (lds > kMaxLds) return -12;
+  out[0] = (int)chunk; out[1] = (int)nchunk; out[2] = (int)last; out[3] = (int)lds;
+  return 0;
+}
+
+// the constraint-space functions on a finished pass' leaves (mjh_efc.h): one wavefront per environment
+template <typename REAL>
+int run_constraint_space(const DevModel<REAL>& M, const mjhConstraintSpaceArgs* x, void* stream) {
+  const int op = x->op, nv = M.nv, n = M.nefc;
+  if (op < MJH_EFC_MUL_J || op > MJH_EFC_AR) return fail(-22, "constraint_space: unknown op");
+  if (x->B < 0) return fail(-22, "constraint_space: B must be >= 0");
+  const bool mv = op == MJH_EFC_MUL_J || op == MJH_EFC_MUL_JT;
+  if (mv && (x->K < 1 || (int64_t)x->K * std::max(nv, n) >= (1 << 30))) return fail(-22, "constraint_space: bad vector count K");
+  if (op == MJH_EFC_UPDATE && (x->ne_nf < 0 || x->ne_nf > n)) return fail(-22, "constraint_space: ne_nf outside [0, nefc]");
+  if (op == MJH_EFC_UPDATE && x->qacc && !(x->meaninertia > 0)) return fail(-22, "constraint_space: meaninertia must be > 0");
+  if (x->B == 0 || nv == 0 || n == 0) return 0;
+  if (!x->efc_J || (mv && (!x->vec || !x->out))) return fail(-22, "constraint_space: null pointer");
+  if (op == MJH_EFC_UPDATE) {
+    if (!x->efc_D || !x->efc_frictionloss || !x->efc_force || !x->efc_state || !x->qfrc_constraint || !x->cost)
+      return fail(-22, "constraint_space: null pointer (update leaves)");
+    if (x->qacc ? (x->jar_in || !x->efc_aref || !x->qM || !x->qfrc_smooth || !x->qacc_smooth || !x->jar || !x->gauss || !x->grad || !x->grad_norm) : !x->jar_in)
+      return fail(-22, "constraint_space: update takes qacc with efc_aref, qM, qfrc_smooth, qacc_smooth and its outputs, or jar_in alone");
+  }
+  if (op == MJH_EFC_AR && (!x->efc_D || !x->efc_aref || !x->qLD || !x->qacc_smooth || !x->AR || !x->b)) return fail(-22, "constraint_space: null pointer (AR leaves)");
+  int plan[4];
+  if (efc_plan(op, nv, n, (int)sizeof(REAL), plan)) return fail(-12, "constraint_space: qLD's triangle and two row chunks do not fit the LDS of a workgroup (nv too large)");
+  hipStream_t s = (hipStream_t)stream;
+  timing_begin(s);
+  EfcArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+  a.J = reinterpret_cast<const REAL*>(x->efc_J); a.D = reinterpret_cast<const REAL*>(x->efc_D); a.aref = reinterpret_cast<const REAL*>(x->efc_aref);
+  a.fl = reinterpret_cast<const REAL*>(x->efc_frictionloss); a.qM = reinterpret_cast<const REAL*>(x->qM); a.qLD = reinterpret_cast<const REAL*>(x->qLD);
+  a.qfrc_smooth = reinterpret_cast<const REAL*>(x->qfrc_smooth); a.qacc_smooth = reinterpret_cast<const REAL*>(x->qacc_smooth);
+  a.qacc = reinterpret_cast<const REAL*>(x->qacc); a.jar_in = reinterpret_cast<const REAL*>(x->jar_in); a.vec = reinterpret_cast<const REAL*>(x->vec);
+  a.out = reinterpret_cast<REAL*>(x->out); a.jar = reinterpret_cast<REAL*>(x->jar); a.force = reinterpret_cast<REAL*>(x->efc_force); a.state = x->efc_state;
+  a.qfrc_constraint = reinterpret_cast<REAL*>(x->qfrc_constraint); a.cost = reinterpret_cast<REAL*>(x->cost); a.gauss = reinterpret_cast<REAL*>(x->gauss);
+  a.grad = reinterpret_cast<REAL*>(x->grad); a.grad_norm = reinterpret_cast<REAL*>(x->grad_norm); a.AR = reinterpret_cast<REAL*>(x->AR); a.b = reinterpret_cast<REAL*>(x->b);
+  a.vec_env = x->vec_env; a.vec_k = x->vec_k;
+  a.nv = nv; a.nefc = n; a.K = x->K; a.ne_nf = x->ne_nf; a.floss = x->floss != 0; a.chunk = plan[0];
+  a.inv_scale = (REAL)(1.0 / (x->meaninertia * std::max(1, nv)));
+  const size_t lds = (size_t)plan[3];
+  void (*kernel)(EfcArgs<REAL>) = op == MJH_EFC_MUL_J ? &mjh_efc_mulj_kernel<REAL> : op == MJH_EFC_MUL_JT ? &mjh_efc_muljt_kernel<REAL>
+                                  : op == MJH_EFC_UPDATE ? &mjh_efc_update_kernel<REAL> : &mjh_efc_ar_kernel<REAL>;
+  if (lds > 64 * 1024) HIP_TRY(allow_lds(kernel, (int)lds));
+  if (const int rc = launch_cut(x->B, 1, [&](int64_t first, int64_t, unsigned grid) {
+        a.env_base = first;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(MJH_WAVE), lds, s, a);
+      }))
+    return rc;
+  timing_mark(s, MJH_KERNEL_EFC_MUL_J + op);
+  return 0;
+}
+
 // The tail of the kernels that give every workgroup a.envs environments of a.lanes lanes and a.lds_env reals of LDS each (postcon, consens, energy, integrate): the
 // batch goes out in cuts of environments [env_begin, env_begin + env_count), timed as kernel `id`.  The caller has made its last refusal.
 template <typename REAL, template <typename> class Args>
@@ -2203,6 +2280,18 @@ int mjh_support(const mjhModel* m, const mjhSupportArgs* args, void* stream) {
   return m->dtype == MJH_F64 ? run_support<double>(m, m->m64, args, stream) : run_support<float>(m, m->m32, args, stream);
 }
 
+int mjh_constraint_space(const mjhModel* m, const mjhConstraintSpaceArgs* args, void* stream) {
+  if (!m || !args) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_constraint_space<double>(m->m64, args, stream) : run_constraint_space<float>(m->m32, args, stream);
+}
+
+int mjh_constraint_space_plan(int op, int nv, int nefc, int real_bytes, int* chunk_nchunk_last_lds) {
+  if (op < MJH_EFC_MUL_J || op > MJH_EFC_AR || nv < 0 || nefc < 0 || (real_bytes != 4 && real_bytes != 8) || !chunk_nchunk_last_lds)
+    return fail(-22, "constraint_space_plan: bad argument");
+  if (efc_plan(op, nv, nefc, real_bytes, chunk_nchunk_last_lds)) return fail(-12, "constraint_space_plan: the operation does not fit the LDS of a workgroup");
+  return 0;
+}
+
 int mjh_postconstraint(const mjhModel* m, const mjhPostconArgs* args, void* stream) {
   if (!m || !args) return fail(-22, "null argument");
   return m->dtype == MJH_F64 ? run_postcon<double>(m, m->m64, args, stream) : run_postcon<float>(m, m->m32, args, stream);
@@ -2451,6 +2540,14 @@ static int kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes, b
     if (nv == 0 || (f64 ? m->m64.nsite : m->m32.nsite) == 0) return -2;
     read_write_bytes[0] = (6 * nv + 12 + 3 + 7 + nq + 1) * R + 4 + 1;
     read_write_bytes[1] = (nq + 1) * R + 4 + 1;
+    return 0;
+  }
+  if (kernel >= MJH_KERNEL_EFC_MUL_J && kernel <= MJH_KERNEL_EFC_AR) {  // mjh_constraint_space, per environment: see include/mjhip.h
+    const int64_t R = f64 ? 8 : 4, nv = f64 ? m->m64.nv : m->m32.nv, n = f64 ? m->m64.nefc : m->m32.nefc;
+    if (nv == 0 || n == 0) return -2;
+    const int64_t io[4][2] = {{n * nv + nv, n}, {n * nv + n, nv}, {n * nv + 3 * n + nv * nv + 3 * nv, 2 * n + 2 * nv + 3}, {n * nv + nv * nv + 2 * n + nv, n * n + n}};
+    read_write_bytes[0] = io[kernel - MJH_KERNEL_EFC_MUL_J][0] * R;
+    read_write_bytes[1] = io[kernel - MJH_KERNEL_EFC_MUL_J][1] * R + (kernel == MJH_KERNEL_EFC_UPDATE ? 4 * n : 0);
     return 0;
   }
   if (kernel >= MJH_KERNEL_JACOBIAN_POINT && kernel <= MJH_KERNEL_JACOBIAN_ANGMOM_VEC) {  // mjh_jacobian, per environment for one query: see include/mjhip.h

@@ -285,6 +285,17 @@ class JacobianArgs(ctypes.Structure):
         ("out0", ctypes.c_void_p), ("out1", ctypes.c_void_p)]
 
 
+class ConstraintSpaceArgs(ctypes.Structure):
+    """include/mjhip.h mjhConstraintSpaceArgs: one mjh_constraint_space call (device pointers, element strides).  Bound below like ``mjh_ray`` and its
+    ``RayCands``, beside the ``ARGS`` table (tests/test_constraint_space_host.py compares it with the header)."""
+
+    _fields_ = [("op", ctypes.c_int32), ("K", ctypes.c_int32), ("ne_nf", ctypes.c_int32), ("floss", ctypes.c_int32), ("B", ctypes.c_int64),
+                ("meaninertia", ctypes.c_double)] + [(n, ctypes.c_void_p) for n in (
+        "efc_J", "efc_D", "efc_aref", "efc_frictionloss", "qM", "qLD", "qfrc_smooth", "qacc_smooth", "qacc", "jar_in", "vec")] + [
+        ("vec_env", ctypes.c_int64), ("vec_k", ctypes.c_int64)] + [(n, ctypes.c_void_p) for n in (
+        "out", "jar", "efc_force", "efc_state", "qfrc_constraint", "cost", "gauss", "grad", "grad_norm", "AR", "b")]
+
+
 # the entry points that take (handle, args struct, stream): symbol -> the struct (tests/test_abi.py compares every struct with the header)
 ARGS = {"mjh_support": SupportArgs, "mjh_postconstraint": PostconArgs, "mjh_contact_sensors": ContactSensorArgs, "mjh_energy": EnergyArgs,
         "mjh_integrate": IntegrateArgs, "mjh_jacobian": JacobianArgs}
@@ -339,6 +350,11 @@ def load_library(path: str | None = None):
             fn = getattr(lib, symbol)
             fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(struct), ctypes.c_void_p]
             fn.restype = ctypes.c_int
+    if hasattr(lib, "mjh_constraint_space"):  # (likewise a build from before the constraint-space functions)
+        lib.mjh_constraint_space.argtypes = [ctypes.c_void_p, ctypes.POINTER(ConstraintSpaceArgs), ctypes.c_void_p]
+        lib.mjh_constraint_space.restype = ctypes.c_int
+        lib.mjh_constraint_space_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        lib.mjh_constraint_space_plan.restype = ctypes.c_int
     if hasattr(lib, "mjh_integrate_plan"):
         lib.mjh_integrate_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         lib.mjh_integrate_plan.restype = ctypes.c_int
