@@ -21,6 +21,7 @@
 #include "mjh_qpos.h"
 #include "mjh_ik.h"
 #include "mjh_efc.h"
+#include "mjh_pgs.h"
 #include "mjh_instances.h"
 
 #define MJH_CAT_(a, b) a##b
@@ -89,4 +90,7 @@ template __global__ void mjh_efc_mulj_kernel<MJH_INST_REAL>(EfcArgs<MJH_INST_REA
 template __global__ void mjh_efc_muljt_kernel<MJH_INST_REAL>(EfcArgs<MJH_INST_REAL>);
 template __global__ void mjh_efc_update_kernel<MJH_INST_REAL>(EfcArgs<MJH_INST_REAL>);
 template __global__ void mjh_efc_ar_kernel<MJH_INST_REAL>(EfcArgs<MJH_INST_REAL>);
+#endif
+#if MJH_INST_GROUP == 34
+template __global__ void mjh_pgs_kernel<MJH_INST_REAL>(PgsArgs<MJH_INST_REAL>);
 #endif

@@ -33,6 +33,7 @@
 #include "mjh_qpos.h"
 #include "mjh_ik.h"
 #include "mjh_efc.h"
+#include "mjh_pgs.h"
 #include "mjh_instances.h"
 
 // the kernels are compiled in their own translation units (mjh_inst.hip, one per build group): this file is the host side only
@@ -102,6 +103,8 @@ IK_(float)
 EFC_(double)  // (build group 33)
 EFC_(float)
 #undef EFC_
+extern template __global__ void mjh_pgs_kernel<double>(PgsArgs<double>);  // (build group 34)
+extern template __global__ void mjh_pgs_kernel<float>(PgsArgs<float>);
 #undef X_
 #undef S_
 #undef C_
@@ -1699,6 +1702,63 @@ int run_constraint_space(const DevModel<REAL>& M, const mjhConstraintSpaceArgs* 
   return 0;
 }
 
+// The plan of mjh_pgs (mjh_pgs.h): rows of efc_J per staging step (16 KB of rows of nv | 1 reals, as mjh_constraint_space stages them), the number of steps, the
+// rows of the last one and the LDS of a workgroup: the packed triangle of qLD, all nefc rows of W, five reals a row (R, b, the friction bound, w_i . w_i, f), y and
+// J^T f, and 64 partial sums.  Returns 0, or -12 when that does not fit kMaxLds.
+static int pgs_plan(int nv, int nefc, int real_bytes, int* out) {
+  constexpr int64_t kChunkBytes = 16 * 1024, kMaxLds = 160 * 1024;
+  const int64_t ld = nv | 1, rb = ld * real_bytes;
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(kChunkBytes / rb, std::max(nefc, 1)));
+  const int64_t nchunk = nefc > 0 ? (nefc + chunk - 1) / chunk : 0, last = nefc > 0 ? nefc - (nchunk - 1) * chunk : 0;
+  const int64_t reals = (int64_t)nv * (nv + 1) / 2 + (int64_t)nefc * ld + 5 * (int64_t)nefc + 2 * (int64_t)nv + MJH_WAVE;
+  const int64_t lds = (reals * real_bytes + 15) & ~(int64_t)15;
+  out[0] = (int)chunk; out[1] = (int)nchunk; out[2] = (int)last; out[3] = (int)std::min<int64_t>(lds, INT32_MAX);
+  return lds > kMaxLds ? -12 : 0;
+}
+
+// projected Gauss-Seidel on the dual problem of a finished pass' leaves (mjh_pgs.h): one wavefront per environment
+template <typename REAL>
+int run_pgs(const DevModel<REAL>& M, const mjhPgsArgs* x, void* stream) {
+  const int nv = M.nv, n = M.nefc;
+  if (x->B < 0) return fail(-22, "pgs: B must be >= 0");
+  if (x->iterations < 0) return fail(-22, "pgs: iterations must be >= 0");
+  if (x->ne < 0 || x->nf < 0 || x->ne + x->nf > n) return fail(-22, "pgs: ne + nf outside [0, nefc]");
+  if (!(x->meaninertia > 0)) return fail(-22, "pgs: meaninertia must be > 0");
+  if (!(x->tolerance >= 0)) return fail(-22, "pgs: tolerance must be >= 0");
+  if (x->force0_env != 0 && x->force0_env < n) return fail(-22, "pgs: force0_env must be 0 (shared) or at least nefc");
+  if (x->B == 0 || nv == 0 || n == 0) return 0;
+  if (!x->efc_J || !x->efc_D || !x->efc_aref || !x->efc_frictionloss || !x->qLD || !x->qacc_smooth || !x->efc_force || !x->qfrc_constraint || !x->qacc || !x->cost ||
+      !x->improvement || !x->niter)
+    return fail(-22, "pgs: null pointer");
+  int plan[4];
+  if (pgs_plan(nv, n, (int)sizeof(REAL), plan)) {
+    char msg[200];
+    snprintf(msg, sizeof(msg), "pgs: nv = %d, nefc = %d need %d bytes of LDS (qLD's triangle and all nefc rows of nv | 1 reals); a workgroup has %d", nv, n, plan[3],
+             160 * 1024);
+    return fail(-12, msg);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  timing_begin(s);
+  PgsArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+  a.J = reinterpret_cast<const REAL*>(x->efc_J); a.D = reinterpret_cast<const REAL*>(x->efc_D); a.aref = reinterpret_cast<const REAL*>(x->efc_aref);
+  a.fl = reinterpret_cast<const REAL*>(x->efc_frictionloss); a.qLD = reinterpret_cast<const REAL*>(x->qLD); a.qacc_smooth = reinterpret_cast<const REAL*>(x->qacc_smooth);
+  a.force0 = reinterpret_cast<const REAL*>(x->force0); a.force0_env = x->force0_env;
+  a.force = reinterpret_cast<REAL*>(x->efc_force); a.qfrc_constraint = reinterpret_cast<REAL*>(x->qfrc_constraint); a.qacc = reinterpret_cast<REAL*>(x->qacc);
+  a.cost = reinterpret_cast<REAL*>(x->cost); a.improvement = reinterpret_cast<REAL*>(x->improvement); a.niter = x->niter;
+  a.tolerance = (REAL)x->tolerance; a.inv_scale = (REAL)(1.0 / (x->meaninertia * std::max(1, nv)));
+  a.nv = nv; a.nefc = n; a.ne = x->ne; a.nf = x->nf; a.iterations = x->iterations; a.chunk = plan[0];
+  const size_t lds = (size_t)plan[3];
+  if (lds > 64 * 1024) HIP_TRY(allow_lds(&mjh_pgs_kernel<REAL>, (int)lds));
+  if (const int rc = launch_cut(x->B, 1, [&](int64_t first, int64_t, unsigned grid) {
+        a.env_base = first;
+        hipLaunchKernelGGL(mjh_pgs_kernel<REAL>, dim3(grid), dim3(MJH_WAVE), lds, s, a);
+      }))
+    return rc;
+  timing_mark(s, MJH_KERNEL_PGS);
+  return 0;
+}
+
 // The tail of the kernels that give every workgroup a.envs environments of a.lanes lanes and a.lds_env reals of LDS each (postcon, consens, energy, integrate): the
 // batch goes out in cuts of environments [env_begin, env_begin + env_count), timed as kernel `id`.  The caller has made its last refusal.
 template <typename REAL, template <typename> class Args>
@@ -2292,6 +2352,17 @@ int mjh_constraint_space_plan(int op, int nv, int nefc, int real_bytes, int* chu
   return 0;
 }
 
+int mjh_pgs(const mjhModel* m, const mjhPgsArgs* args, void* stream) {
+  if (!m || !args) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_pgs<double>(m->m64, args, stream) : run_pgs<float>(m->m32, args, stream);
+}
+
+int mjh_pgs_plan(int nv, int nefc, int real_bytes, int* chunk_nchunk_last_lds) {
+  if (nv < 0 || nefc < 0 || (real_bytes != 4 && real_bytes != 8) || !chunk_nchunk_last_lds) return fail(-22, "pgs_plan: bad argument");
+  if (pgs_plan(nv, nefc, real_bytes, chunk_nchunk_last_lds)) return fail(-12, "pgs_plan: the model does not fit the LDS of a workgroup");
+  return 0;
+}
+
 int mjh_postconstraint(const mjhModel* m, const mjhPostconArgs* args, void* stream) {
   if (!m || !args) return fail(-22, "null argument");
   return m->dtype == MJH_F64 ? run_postcon<double>(m, m->m64, args, stream) : run_postcon<float>(m, m->m32, args, stream);
@@ -2548,6 +2619,13 @@ static int kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes, b
     const int64_t io[4][2] = {{n * nv + nv, n}, {n * nv + n, nv}, {n * nv + 3 * n + nv * nv + 3 * nv, 2 * n + 2 * nv + 3}, {n * nv + nv * nv + 2 * n + nv, n * n + n}};
     read_write_bytes[0] = io[kernel - MJH_KERNEL_EFC_MUL_J][0] * R;
     read_write_bytes[1] = io[kernel - MJH_KERNEL_EFC_MUL_J][1] * R + (kernel == MJH_KERNEL_EFC_UPDATE ? 4 * n : 0);
+    return 0;
+  }
+  if (kernel == MJH_KERNEL_PGS) {  // mjh_pgs, per environment: see include/mjhip.h
+    const int64_t R = f64 ? 8 : 4, nv = f64 ? m->m64.nv : m->m32.nv, n = f64 ? m->m64.nefc : m->m32.nefc;
+    if (nv == 0 || n == 0) return -2;
+    read_write_bytes[0] = (2 * n * nv + nv * nv + 3 * n + nv) * R;
+    read_write_bytes[1] = (n + 2 * nv + 2) * R + 4;
     return 0;
   }
   if (kernel >= MJH_KERNEL_JACOBIAN_POINT && kernel <= MJH_KERNEL_JACOBIAN_ANGMOM_VEC) {  // mjh_jacobian, per environment for one query: see include/mjhip.h

@@ -296,6 +296,16 @@ class ConstraintSpaceArgs(ctypes.Structure):
         "out", "jar", "efc_force", "efc_state", "qfrc_constraint", "cost", "gauss", "grad", "grad_norm", "AR", "b")]
 
 
+class PgsArgs(ctypes.Structure):
+    """include/mjhip.h mjhPgsArgs: one mjh_pgs call (device pointers, an element stride).  Bound below beside the ``ARGS`` table, like ``ConstraintSpaceArgs``
+    (tests/test_pgs_host.py compares it with the header)."""
+
+    _fields_ = [("ne", ctypes.c_int32), ("nf", ctypes.c_int32), ("iterations", ctypes.c_int32), ("pad_", ctypes.c_int32), ("B", ctypes.c_int64),
+                ("meaninertia", ctypes.c_double), ("tolerance", ctypes.c_double)] + [(n, ctypes.c_void_p) for n in (
+        "efc_J", "efc_D", "efc_aref", "efc_frictionloss", "qLD", "qacc_smooth", "force0")] + [("force0_env", ctypes.c_int64)] + [(n, ctypes.c_void_p) for n in (
+        "efc_force", "qfrc_constraint", "qacc", "cost", "improvement", "niter")]
+
+
 # the entry points that take (handle, args struct, stream): symbol -> the struct (tests/test_abi.py compares every struct with the header)
 ARGS = {"mjh_support": SupportArgs, "mjh_postconstraint": PostconArgs, "mjh_contact_sensors": ContactSensorArgs, "mjh_energy": EnergyArgs,
         "mjh_integrate": IntegrateArgs, "mjh_jacobian": JacobianArgs}
@@ -355,6 +365,11 @@ def load_library(path: str | None = None):
         lib.mjh_constraint_space.restype = ctypes.c_int
         lib.mjh_constraint_space_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         lib.mjh_constraint_space_plan.restype = ctypes.c_int
+    if hasattr(lib, "mjh_pgs"):  # (likewise a build from before solve_pgs)
+        lib.mjh_pgs.argtypes = [ctypes.c_void_p, ctypes.POINTER(PgsArgs), ctypes.c_void_p]
+        lib.mjh_pgs.restype = ctypes.c_int
+        lib.mjh_pgs_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        lib.mjh_pgs_plan.restype = ctypes.c_int
     if hasattr(lib, "mjh_integrate_plan"):
         lib.mjh_integrate_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         lib.mjh_integrate_plan.restype = ctypes.c_int
