@@ -23,6 +23,7 @@
  *   mjh_ik_site_step   <- one damped-least-squares iteration of site-pose inverse kinematics (dm_control's qpos_from_site_pose; the reference has no counterpart)
  *   mjh_constraint_space <- MuJoCo's mj_mulJacVec / mj_mulJacTVec / mj_constraintUpdate and the Delassus matrix efc_AR, by the reference solver's definitions (_src/solver.py:293-357, 501-508)
  *   mjh_pgs            <- MuJoCo's mj_solPGS for rows of dimension one, on the dual problem of a finished pass (the reference's solvers are CG and Newton alone)
+ *   mjh_noslip         <- MuJoCo's mj_solNoSlip (noslip_iterations): Gauss-Seidel on the friction dimensions with the unregularised matrix, after the main solver (the reference has no counterpart)
  *   mjh_jacobian       <- MuJoCo's mj_jacBody .. mj_jacGeom (as products), mj_jacDot, mj_jacSubtreeCom, mj_angmomMat (the reference has support.jac alone)
  *   mjh_integrate      <- derivative.deriv_smooth_vel, forward._implicit (implicitfast), forward._euler and their _advance, on a finished pass (_src/derivative.py:22-68, forward.py:255-328, 404-416)
  *
@@ -50,7 +51,7 @@
 extern "C" {
 #endif
 
-#define MJH_ABI_VERSION 24
+#define MJH_ABI_VERSION 25
 
 /* ---- dtype / flags ------------------------------------------------------------------- */
 #define MJH_F64 0
@@ -125,6 +126,7 @@ extern "C" {
 #define MJH_KERNEL_EFC_UPDATE 52 /* ... MJH_EFC_UPDATE: jar, states, forces, cost and gradient of a qacc (one fused kernel) */
 #define MJH_KERNEL_EFC_AR 53     /* ... MJH_EFC_AR: the Delassus matrix J M^-1 J^T + R and b                              */
 #define MJH_KERNEL_PGS 54        /* mjh_pgs: projected Gauss-Seidel sweeps on the dual problem (one wavefront per environment) */
+#define MJH_KERNEL_NOSLIP 55     /* mjh_noslip: no-slip sweeps on the friction dimensions, pyramidal pairs and elliptic QCQPs (one wavefront per environment) */
 
 /* pair-function ids of the static collision table (collision_driver.py:106-125) */
 #define MJH_FN_PLANE_SPHERE 0
@@ -834,6 +836,46 @@ int mjh_pgs(const mjhModel* m, const mjhPgsArgs* args, void* hip_stream);
  * (out is filled all the same: the bytes it would need), -22 for a bad argument. */
 int mjh_pgs_plan(int nv, int nefc, int real_bytes, int* chunk_nchunk_last_lds);
 
+/* one mjh_noslip call (definitions: csrc/mjh_noslip.h).  Every pointer is device memory, reals of the model's dtype unless stated, batch-major over B environments;
+ * the leaves are a finished pass's, as for mjhPgsArgs, and contact_friction [B, ncon, 5] (read when the model's cone is elliptic; may be NULL otherwise).  The
+ * sweeps run on A = J (L L^T)^-1 J^T (no regulariser) over the friction dimensions only: the friction-loss rows ne <= i < ne + nf, then every contact of
+ * condim > 1 in slot order (the model's static contact tables and cone) -- the pairs of opposing edges of a pyramidal contact, or the dim - 1 friction rows of an
+ * elliptic one through a QCQP in its normal force.  force0 (required; environment e reads force0[e * force0_env + i], force0_env 0: shared) is NOT projected;
+ * every other row leaves as it came.  At most `iterations` sweeps, each followed by improvement *= 1 / (meaninertia * max(1, nv)); an environment stops when
+ * improvement < tolerance.  Outputs, every one written: efc_force [B, nefc], qfrc_constraint [B, nv] = J^T f, qacc [B, nv] = qacc_smooth + (L L^T)^-1 J^T f,
+ * cost [B] = 1/2 f^T A f + f . b, improvement [B] (of the last sweep; 0 without one), niter [B] int32 (the sweeps run). */
+typedef struct mjhNoslipArgs {
+  int32_t ne, nf, iterations, pad_;
+  int64_t B;
+  double meaninertia, tolerance;
+  const void* efc_J;
+  const void* efc_D;
+  const void* efc_aref;
+  const void* efc_frictionloss;
+  const void* qLD;
+  const void* qacc_smooth;
+  const void* force0;
+  const void* contact_friction;
+  int64_t force0_env;
+  void* efc_force;
+  void* qfrc_constraint;
+  void* qacc;
+  void* cost;
+  void* improvement;
+  int32_t* niter;
+} mjhNoslipArgs;
+
+/* the no-slip friction post-solver on a finished pass (see mjhNoslipArgs; MuJoCo's mj_solNoSlip).  One launch, one wavefront per environment, cut at the launch cap
+ * like mjh_pgs; runs on hip_stream without host synchronisation.  Returns 0 or a negative code (-12 when the model does not fit the LDS of a workgroup:
+ * mjh_last_error names the sizes); B == 0, nv == 0 and nefc == 0 are no-ops. */
+int mjh_noslip(const mjhModel* m, const mjhNoslipArgs* args, void* hip_stream);
+
+/* the plan mjh_noslip uses for a model of nv dofs, nefc rows and ncon contact slots in reals of real_bytes (4 / 8) bytes, a host computation (no device is
+ * touched): out = {rows of efc_J per staging step, number of steps, rows of the last step, bytes of LDS per workgroup}: mjh_pgs_plan's, plus 22 reals a contact
+ * slot (the blocks of A, 15; mu, 5; the table entry, 2).  Returns 0, -12 when the model does not fit a workgroup's LDS (out is filled all the same: the bytes it
+ * would need), -22 for a bad argument. */
+int mjh_noslip_plan(int nv, int nefc, int ncon, int real_bytes, int* chunk_nchunk_last_lds);
+
 /* mjh_jacobian operations (mjhJacobianArgs.op); MJH_KERNEL_JACOBIAN_POINT + op (matrix form) or MJH_KERNEL_JACOBIAN_POINT_VEC + op (product form) is the kernel id
  * the timing aid reports */
 #define MJH_JACOBIAN_POINT 0
@@ -949,7 +991,7 @@ int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsi
 int mjh_model_lds_bytes(const mjhModel* m, int arena);
 
 /* measurement aid used by bench.py for the per-kernel roofline: while enabled, every kernel launch of mjh_step / mjh_forward is
- * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_ifd_perturb, mjh_ifd_difference, mjh_postconstraint, mjh_contact_sensors, mjh_energy, mjh_integrate, mjh_jacobian, mjh_geom_distance, mjh_qpos_arith, mjh_ik_site_step, mjh_constraint_space and mjh_pgs too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
+ * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_ifd_perturb, mjh_ifd_difference, mjh_postconstraint, mjh_contact_sensors, mjh_energy, mjh_integrate, mjh_jacobian, mjh_geom_distance, mjh_qpos_arith, mjh_ik_site_step, mjh_constraint_space, mjh_pgs and mjh_noslip too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
  * the elapsed milliseconds and the kernel id (MJH_KERNEL_*).  Returns the number of launches (<= max) or a negative code. */
 int mjh_debug_phase_timing(int enable);
 int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
@@ -982,7 +1024,9 @@ void mjh_debug_set_stamps(void* dev_ptr);
  * one vector in, one out (MUL_J, MUL_JT); efc_J, the three row leaves, qM and the three dof vectors in, the outputs of the qacc form out (UPDATE); efc_J once (a model of one
  * chunk), qLD, efc_D, efc_aref and qacc_smooth in, AR and b out (AR); -2 for a model without dofs or rows.  MJH_KERNEL_PGS (an mjh_pgs call
  * from zeros, without force0): per environment, efc_J twice (W, then J^T f), qLD, the three row leaves and qacc_smooth in, efc_force, qfrc_constraint, qacc and the
- * three scalars out; -2 for a model without dofs or rows.  Returns 0, or -2 when this model's step does not launch that kernel. */
+ * three scalars out; -2 for a model without dofs or rows.  MJH_KERNEL_NOSLIP (an mjh_noslip call): per environment, efc_J twice, qLD, the three row leaves, force0,
+ * qacc_smooth and, with an elliptic cone, the friction of every contact slot in -- (2 nefc nv + nv^2 + 4 nefc + nv [+ 5 ncon]) reals --, efc_force, qfrc_constraint,
+ * qacc and the three scalars out -- (nefc + 2 nv + 2) reals + 4 bytes; -2 for a model without dofs or rows.  Returns 0, or -2 when this model's step does not launch that kernel. */
 int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes);
 
 /* last error message of the calling thread ("" if none) */

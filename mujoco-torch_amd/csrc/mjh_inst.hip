@@ -22,6 +22,7 @@
 #include "mjh_ik.h"
 #include "mjh_efc.h"
 #include "mjh_pgs.h"
+#include "mjh_noslip.h"
 #include "mjh_instances.h"
 
 #define MJH_CAT_(a, b) a##b
@@ -93,4 +94,7 @@ template __global__ void mjh_efc_ar_kernel<MJH_INST_REAL>(EfcArgs<MJH_INST_REAL>
 #endif
 #if MJH_INST_GROUP == 34
 template __global__ void mjh_pgs_kernel<MJH_INST_REAL>(PgsArgs<MJH_INST_REAL>);
+#endif
+#if MJH_INST_GROUP == 35
+template __global__ void mjh_noslip_kernel<MJH_INST_REAL>(NoslipArgs<MJH_INST_REAL>);
 #endif

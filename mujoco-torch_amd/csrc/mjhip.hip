@@ -34,6 +34,7 @@
 #include "mjh_ik.h"
 #include "mjh_efc.h"
 #include "mjh_pgs.h"
+#include "mjh_noslip.h"
 #include "mjh_instances.h"
 
 // the kernels are compiled in their own translation units (mjh_inst.hip, one per build group): this file is the host side only
@@ -105,6 +106,8 @@ EFC_(float)
 #undef EFC_
 extern template __global__ void mjh_pgs_kernel<double>(PgsArgs<double>);  // (build group 34)
 extern template __global__ void mjh_pgs_kernel<float>(PgsArgs<float>);
+extern template __global__ void mjh_noslip_kernel<double>(NoslipArgs<double>);  // (build group 35)
+extern template __global__ void mjh_noslip_kernel<float>(NoslipArgs<float>);
 #undef X_
 #undef S_
 #undef C_
@@ -1759,6 +1762,64 @@ int run_pgs(const DevModel<REAL>& M, const mjhPgsArgs* x, void* stream) {
   return 0;
 }
 
+// The plan of mjh_noslip (mjh_noslip.h): mjh_pgs's staging and arrays, and per contact slot the block(s) of A (15 reals), mu (5 reals) and the table entry (two
+// ints, counted as two reals).  Returns 0, or -12 when that does not fit kMaxLds.
+static int noslip_plan(int nv, int nefc, int ncon, int real_bytes, int* out) {
+  constexpr int64_t kChunkBytes = 16 * 1024, kMaxLds = 160 * 1024;
+  const int64_t ld = nv | 1, rb = ld * real_bytes;
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(kChunkBytes / rb, std::max(nefc, 1)));
+  const int64_t nchunk = nefc > 0 ? (nefc + chunk - 1) / chunk : 0, last = nefc > 0 ? nefc - (nchunk - 1) * chunk : 0;
+  const int64_t reals = (int64_t)nv * (nv + 1) / 2 + (int64_t)nefc * ld + 5 * (int64_t)nefc + 2 * (int64_t)nv + MJH_WAVE + (MJH_NOSLIP_BLOCK + 5 + 2) * (int64_t)ncon;
+  const int64_t lds = (reals * real_bytes + 15) & ~(int64_t)15;
+  out[0] = (int)chunk; out[1] = (int)nchunk; out[2] = (int)last; out[3] = (int)std::min<int64_t>(lds, INT32_MAX);
+  return lds > kMaxLds ? -12 : 0;
+}
+
+// the no-slip sweeps on a finished pass' leaves (mjh_noslip.h): one wavefront per environment
+template <typename REAL>
+int run_noslip(const DevModel<REAL>& M, const mjhNoslipArgs* x, void* stream) {
+  const int nv = M.nv, n = M.nefc;
+  if (x->B < 0) return fail(-22, "noslip: B must be >= 0");
+  if (x->iterations < 0) return fail(-22, "noslip: iterations must be >= 0");
+  if (x->ne < 0 || x->nf < 0 || x->ne + x->nf > n) return fail(-22, "noslip: ne + nf outside [0, nefc]");
+  if (!(x->meaninertia > 0)) return fail(-22, "noslip: meaninertia must be > 0");
+  if (!(x->tolerance >= 0)) return fail(-22, "noslip: tolerance must be >= 0");
+  if (x->force0_env != 0 && x->force0_env < n) return fail(-22, "noslip: force0_env must be 0 (shared) or at least nefc");
+  if (x->B == 0 || nv == 0 || n == 0) return 0;
+  const bool elliptic = M.cone == CONE_ELLIPTIC;
+  if (!x->efc_J || !x->efc_D || !x->efc_aref || !x->efc_frictionloss || !x->qLD || !x->qacc_smooth || !x->force0 || !x->efc_force || !x->qfrc_constraint || !x->qacc ||
+      !x->cost || !x->improvement || !x->niter || (elliptic && M.ncon > 0 && !x->contact_friction))
+    return fail(-22, "noslip: null pointer");
+  int plan[4];
+  if (noslip_plan(nv, n, M.ncon, (int)sizeof(REAL), plan)) {
+    char msg[240];
+    snprintf(msg, sizeof(msg), "noslip: nv = %d, nefc = %d, ncon = %d need %d bytes of LDS (qLD's triangle, all nefc rows of nv | 1 reals, 22 reals a contact); a workgroup has %d",
+             nv, n, M.ncon, plan[3], 160 * 1024);
+    return fail(-12, msg);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  timing_begin(s);
+  NoslipArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+  a.J = reinterpret_cast<const REAL*>(x->efc_J); a.D = reinterpret_cast<const REAL*>(x->efc_D); a.aref = reinterpret_cast<const REAL*>(x->efc_aref);
+  a.fl = reinterpret_cast<const REAL*>(x->efc_frictionloss); a.qLD = reinterpret_cast<const REAL*>(x->qLD); a.qacc_smooth = reinterpret_cast<const REAL*>(x->qacc_smooth);
+  a.force0 = reinterpret_cast<const REAL*>(x->force0); a.force0_env = x->force0_env; a.friction = reinterpret_cast<const REAL*>(x->contact_friction);
+  a.con_dim = M.con_dim; a.con_adr = M.con_efc_address; a.ncon = M.ncon; a.elliptic = elliptic ? 1 : 0;
+  a.force = reinterpret_cast<REAL*>(x->efc_force); a.qfrc_constraint = reinterpret_cast<REAL*>(x->qfrc_constraint); a.qacc = reinterpret_cast<REAL*>(x->qacc);
+  a.cost = reinterpret_cast<REAL*>(x->cost); a.improvement = reinterpret_cast<REAL*>(x->improvement); a.niter = x->niter;
+  a.tolerance = (REAL)x->tolerance; a.inv_scale = (REAL)(1.0 / (x->meaninertia * std::max(1, nv)));
+  a.nv = nv; a.nefc = n; a.ne = x->ne; a.nf = x->nf; a.iterations = x->iterations; a.chunk = plan[0];
+  const size_t lds = (size_t)plan[3];
+  if (lds > 64 * 1024) HIP_TRY(allow_lds(&mjh_noslip_kernel<REAL>, (int)lds));
+  if (const int rc = launch_cut(x->B, 1, [&](int64_t first, int64_t, unsigned grid) {
+        a.env_base = first;
+        hipLaunchKernelGGL(mjh_noslip_kernel<REAL>, dim3(grid), dim3(MJH_WAVE), lds, s, a);
+      }))
+    return rc;
+  timing_mark(s, MJH_KERNEL_NOSLIP);
+  return 0;
+}
+
 // The tail of the kernels that give every workgroup a.envs environments of a.lanes lanes and a.lds_env reals of LDS each (postcon, consens, energy, integrate): the
 // batch goes out in cuts of environments [env_begin, env_begin + env_count), timed as kernel `id`.  The caller has made its last refusal.
 template <typename REAL, template <typename> class Args>
@@ -2363,6 +2424,17 @@ int mjh_pgs_plan(int nv, int nefc, int real_bytes, int* chunk_nchunk_last_lds) {
   return 0;
 }
 
+int mjh_noslip(const mjhModel* m, const mjhNoslipArgs* args, void* stream) {
+  if (!m || !args) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_noslip<double>(m->m64, args, stream) : run_noslip<float>(m->m32, args, stream);
+}
+
+int mjh_noslip_plan(int nv, int nefc, int ncon, int real_bytes, int* chunk_nchunk_last_lds) {
+  if (nv < 0 || nefc < 0 || ncon < 0 || (real_bytes != 4 && real_bytes != 8) || !chunk_nchunk_last_lds) return fail(-22, "noslip_plan: bad argument");
+  if (noslip_plan(nv, nefc, ncon, real_bytes, chunk_nchunk_last_lds)) return fail(-12, "noslip_plan: the model does not fit the LDS of a workgroup");
+  return 0;
+}
+
 int mjh_postconstraint(const mjhModel* m, const mjhPostconArgs* args, void* stream) {
   if (!m || !args) return fail(-22, "null argument");
   return m->dtype == MJH_F64 ? run_postcon<double>(m, m->m64, args, stream) : run_postcon<float>(m, m->m32, args, stream);
@@ -2625,6 +2697,14 @@ static int kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes, b
     const int64_t R = f64 ? 8 : 4, nv = f64 ? m->m64.nv : m->m32.nv, n = f64 ? m->m64.nefc : m->m32.nefc;
     if (nv == 0 || n == 0) return -2;
     read_write_bytes[0] = (2 * n * nv + nv * nv + 3 * n + nv) * R;
+    read_write_bytes[1] = (n + 2 * nv + 2) * R + 4;
+    return 0;
+  }
+  if (kernel == MJH_KERNEL_NOSLIP) {  // mjh_noslip, per environment: see include/mjhip.h
+    const int64_t R = f64 ? 8 : 4, nv = f64 ? m->m64.nv : m->m32.nv, n = f64 ? m->m64.nefc : m->m32.nefc, ncon = f64 ? m->m64.ncon : m->m32.ncon;
+    const bool elliptic = (f64 ? m->m64.cone : m->m32.cone) == CONE_ELLIPTIC;
+    if (nv == 0 || n == 0) return -2;
+    read_write_bytes[0] = (2 * n * nv + nv * nv + 4 * n + nv + (elliptic ? 5 * ncon : 0)) * R;
     read_write_bytes[1] = (n + 2 * nv + 2) * R + 4;
     return 0;
   }

@@ -306,6 +306,16 @@ class PgsArgs(ctypes.Structure):
         "efc_force", "qfrc_constraint", "qacc", "cost", "improvement", "niter")]
 
 
+class NoslipArgs(ctypes.Structure):
+    """include/mjhip.h mjhNoslipArgs: one mjh_noslip call (device pointers, an element stride).  Bound below beside the ``ARGS`` table, like ``PgsArgs``
+    (tests/test_noslip_host.py compares it with the header)."""
+
+    _fields_ = [("ne", ctypes.c_int32), ("nf", ctypes.c_int32), ("iterations", ctypes.c_int32), ("pad_", ctypes.c_int32), ("B", ctypes.c_int64),
+                ("meaninertia", ctypes.c_double), ("tolerance", ctypes.c_double)] + [(n, ctypes.c_void_p) for n in (
+        "efc_J", "efc_D", "efc_aref", "efc_frictionloss", "qLD", "qacc_smooth", "force0", "contact_friction")] + [("force0_env", ctypes.c_int64)] + [
+        (n, ctypes.c_void_p) for n in ("efc_force", "qfrc_constraint", "qacc", "cost", "improvement", "niter")]
+
+
 # the entry points that take (handle, args struct, stream): symbol -> the struct (tests/test_abi.py compares every struct with the header)
 ARGS = {"mjh_support": SupportArgs, "mjh_postconstraint": PostconArgs, "mjh_contact_sensors": ContactSensorArgs, "mjh_energy": EnergyArgs,
         "mjh_integrate": IntegrateArgs, "mjh_jacobian": JacobianArgs}
@@ -370,6 +380,11 @@ def load_library(path: str | None = None):
         lib.mjh_pgs.restype = ctypes.c_int
         lib.mjh_pgs_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         lib.mjh_pgs_plan.restype = ctypes.c_int
+    if hasattr(lib, "mjh_noslip"):  # (likewise a build from before solve_noslip)
+        lib.mjh_noslip.argtypes = [ctypes.c_void_p, ctypes.POINTER(NoslipArgs), ctypes.c_void_p]
+        lib.mjh_noslip.restype = ctypes.c_int
+        lib.mjh_noslip_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        lib.mjh_noslip_plan.restype = ctypes.c_int
     if hasattr(lib, "mjh_integrate_plan"):
         lib.mjh_integrate_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         lib.mjh_integrate_plan.restype = ctypes.c_int
