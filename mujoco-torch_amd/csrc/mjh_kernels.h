@@ -2621,13 +2621,30 @@ struct Env {
         int pkj[MJH_CHAIN_PRE];
 #pragma unroll
         for (int jj = 0; jj < MJH_CHAIN_PRE; jj++) pkj[jj] = b0 == 0 ? pkj0[jj] : ((depth > 0 && jj < mj) ? own[jj] : 0);
+        // (whole-pass kernel) the sums of the body's own hinge / slide / ball joints take nothing from the parent: formed here, all bodies at once, and added inside the sweep
+        // in joint order -- dof_sum's additions, then the same v + s; the cdof_dot pass behind the sweep takes them from the same registers (a free joint stays cvel_add_joint)
+        REAL sj[MJH_CHAIN_PRE][6];
+        if constexpr (BATCH) {
+#pragma unroll
+          for (int jj = 0; jj < MJH_CHAIN_PRE; jj++) {
+            const int t = (pkj[jj] & 0xff) - 1, d = pkj[jj] >> 8;
+#pragma unroll
+            for (int k = 0; k < 6; k++) sj[jj][k] = 0;
+            if (pkj[jj] && t != JNT_FREE) dof_sum(d, t == JNT_BALL ? 3 : 1, sj[jj]);
+          }
+        }
         for (int kk = 0; kk < md; kk++) {
           if (depth == kk + 1) {
             REAL v[6];
 #pragma unroll
             for (int k = 0; k < 6; k++) v[k] = S.cvel()[6 * par + k];
 #pragma unroll
-            for (int jj = 0; jj < MJH_CHAIN_PRE; jj++) if (pkj[jj]) cvel_add_joint(pkj[jj], v);
+            for (int jj = 0; jj < MJH_CHAIN_PRE; jj++) if (pkj[jj]) {
+              if (BATCH && (pkj[jj] & 0xff) - 1 != JNT_FREE) {
+#pragma unroll
+                for (int k = 0; k < 6; k++) v[k] = v[k] + sj[jj][k];
+              } else cvel_add_joint(pkj[jj], v);
+            }
             for (int jj = MJH_CHAIN_PRE; jj < mj; jj++) { const int pk = own[jj]; if (pk) cvel_add_joint(pk, v); }
 #pragma unroll
             for (int k = 0; k < 6; k++) S.cvel()[6 * b + k] = v[k];
@@ -2638,7 +2655,7 @@ struct Env {
           REAL v[6];
 #pragma unroll
           for (int k = 0; k < 6; k++) v[k] = S.cvel()[6 * par + k];
-          auto own_joint = [&](int pk) {
+          auto own_joint = [&](int pk, const REAL* pre = nullptr) {  // pre: the joint's sum where the sweep formed it ahead (not a free joint's)
             if (pk == 0) return;
             const int t = (pk & 0xff) - 1, d = pk >> 8;
             if (t == JNT_FREE) {
@@ -2653,15 +2670,18 @@ struct Env {
               for (int k = 0; k < 6; k++) v[k] = v[k] + rot[k];
             } else {
               const int width = (t == JNT_BALL) ? 3 : 1;
-              REAL sj[6];
-              dof_sum(d, width, sj);
+              REAL s1[6];
+              if (pre) {
+#pragma unroll
+                for (int k = 0; k < 6; k++) s1[k] = pre[k];
+              } else dof_sum(d, width, s1);
               for (int r = 0; r < width; r++) motion_cross(v, S.cdof() + 6 * (d + r), S.cdof_dot() + 6 * (d + r));
 #pragma unroll
-              for (int k = 0; k < 6; k++) v[k] = v[k] + sj[k];
+              for (int k = 0; k < 6; k++) v[k] = v[k] + s1[k];
             }
           };
 #pragma unroll
-          for (int jj = 0; jj < MJH_CHAIN_PRE; jj++) own_joint(pkj[jj]);
+          for (int jj = 0; jj < MJH_CHAIN_PRE; jj++) own_joint(pkj[jj], BATCH ? sj[jj] : nullptr);
           for (int jj = MJH_CHAIN_PRE; jj < mj; jj++) own_joint(own[jj]);
         }
         wave_sync();
