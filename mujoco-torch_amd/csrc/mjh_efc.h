@@ -16,7 +16,8 @@
 //   LDS.  A chunk of rows of J is turned into W = rows of (L^-1 J^T)^T in place, one row per lane by forward substitution (element i subtracts L[i][k] w[k] in
 //   k order, as math.small_cholesky_solve does), so that AR[i][j] = w_i . w_j.  Chunk a against itself gives the diagonal block, against every later chunk b
 //   (staged and substituted into the second buffer) the off-diagonal blocks: each entry is computed once and stored to both triangles.  Neither W nor any
-//   other (nefc, nv) intermediate goes to global memory; chunk b's rows of J are read again for every a < b.
+//   other (nefc, nv) intermediate goes to global memory; chunk b's rows of J are read again for every a < b.  Its triangle load, its b and its substitution (efc_load_triangle, efc_rows_b,
+//   efc_forward_rows) are also the staging of the dual solvers, which keep ALL of W on chip (mjh_dual.h).
 #pragma once
 #include "mjh_device.h"
 
@@ -209,6 +210,28 @@ __global__ __launch_bounds__(MJH_WAVE) void mjh_efc_update_kernel(EfcArgs<REAL> 
   if (l == 0) a.cost[e] = cost;
 }
 
+// qLD (nv x nv, row-major) -> its packed lower triangle in LDS, row i at i (i + 1) / 2: every row is read whole (coalesced), its upper part dropped
+template <typename REAL>
+__device__ __forceinline__ void efc_load_triangle(REAL* Lp, const REAL* src, int nv, int l) {
+  for (int t = l; t < nv * nv; t += MJH_WAVE) {
+    const int i = t / nv, k = t - i * nv;
+    const REAL v = src[t];
+    if (k <= i) Lp[i * (i + 1) / 2 + k] = v;
+  }
+}
+
+// b[r] = w_r . qacc_smooth - aref[r] of the staged rows while the rows are still J's (before efc_forward_rows), one row per lane, its sum in column order; b may
+// be LDS or global memory
+template <typename REAL>
+__device__ __forceinline__ void efc_rows_b(REAL* b, const REAL* w, int ld, const REAL* as, const REAL* aref, int rows, int nv, int l) {
+  for (int r = l; r < rows; r += MJH_WAVE) {
+    const REAL* m = w + r * ld;
+    REAL s = 0;
+    for (int k = 0; k < nv; k++) s += m[k] * as[k];
+    b[r] = s - aref[r];
+  }
+}
+
 // the rows of `w` (rows x ld, J's rows on entry) -> L^-1 J_r^T, one row per lane; Lp: the packed lower triangle, row i at i (i + 1) / 2
 template <typename REAL>
 __device__ __forceinline__ void efc_forward_rows(REAL* w, int ld, const REAL* Lp, int rows, int nv, int l) {
@@ -231,12 +254,7 @@ __global__ __launch_bounds__(MJH_WAVE) void mjh_efc_ar_kernel(EfcArgs<REAL> a) {
   REAL* wa = Lp + nv * (nv + 1) / 2;
   REAL* wb = wa + a.chunk * ld;  // (used, and allocated, only when there is more than one chunk)
   const int64_t e = a.env_base + blockIdx.x;
-  const REAL* src = a.qLD + e * nv * nv;
-  for (int t = l; t < nv * nv; t += MJH_WAVE) {  // every row whole (coalesced), its upper part dropped
-    const int i = t / nv, k = t - i * nv;
-    const REAL v = src[t];
-    if (k <= i) Lp[i * (i + 1) / 2 + k] = v;
-  }
+  efc_load_triangle<REAL>(Lp, a.qLD + e * nv * nv, nv, l);
   const REAL* J = a.J + e * n * nv;
   const REAL *D = a.D + e * n, *aref = a.aref + e * n, *as = a.qacc_smooth + e * nv;
   REAL* AR = a.AR + e * n * n;
@@ -244,12 +262,7 @@ __global__ __launch_bounds__(MJH_WAVE) void mjh_efc_ar_kernel(EfcArgs<REAL> a) {
     const int ra = n - a0 < a.chunk ? n - a0 : a.chunk;
     efc_load_rows<REAL>(wa, ld, J + (int64_t)a0 * nv, ra, nv, l);
     wave_sync();
-    for (int r = l; r < ra; r += MJH_WAVE) {  // b, while the rows are still J's
-      const REAL* m = wa + r * ld;
-      REAL s = 0;
-      for (int k = 0; k < nv; k++) s += m[k] * as[k];
-      a.b[e * n + a0 + r] = s - aref[a0 + r];
-    }
+    efc_rows_b<REAL>(a.b + e * n + a0, wa, ld, as, aref + a0, ra, nv, l);
     efc_forward_rows<REAL>(wa, ld, Lp, ra, nv, l);  // (a lane reads and writes its own rows only)
     wave_sync();
     // Blocks go out in tiles of 8 x 8 entries, one entry per lane: the store of an entry and the store of its mirror image then both cover runs of 8

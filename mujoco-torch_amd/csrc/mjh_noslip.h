@@ -1,9 +1,10 @@
 // mjh_noslip.h -- the kernel behind mjh_noslip: MuJoCo's no-slip post-solver (mj_solNoSlip, `noslip_iterations`) on a finished pass: Gauss-Seidel sweeps on
 // the UNREGULARISED matrix A = J (L L^T)^-1 J^T over the friction dimensions only -- friction-loss rows, the opposing edge pairs of pyramidal contacts, the
 // tangential / torsional / rolling rows of elliptic contacts -- from the force the main solver left.  Every other row (equality, limit, frictionless contact rows,
-// elliptic normals) is returned bit for bit.  Dense models only; one wavefront (the whole workgroup) per environment; mjh_pgs.h's shape.
+// elliptic normals) is returned bit for bit.  Dense models only; one wavefront (the whole workgroup) per environment; the arguments, the LDS arrays,
+// the staging and the ending are mjh_dual.h's.
 //
-// With W = rows of (L^-1 J^T)^T, y = sum_j f_j w_j, b = J qacc_smooth - aref, R = 1 / D where D > 0 else 0 as mjh_pgs.h defines them: A_ij = w_i . w_j, the row
+// With W = rows of (L^-1 J^T)^T, y = sum_j f_j w_j, b = J qacc_smooth - aref, R = 1 / D where D > 0 else 0 as mjh_dual.h defines them: A_ij = w_i . w_j, the row
 // residual is res_i = w_i . y + b_i, scale = 1 / (meaninertia max(1, nv)), MINVAL = 1e-15.  force0 is NOT projected.  One sweep, improvement = 0 at its start (the
 // first sweep: 1/2 sum_i R_i f_i^2 over all rows, the cost of dropping the regulariser):
 //   1. friction-loss rows ne <= i < ne + nf: A_ii < MINVAL: skipped; f_i <- clamp(f_i - res_i / A_ii, +-frictionloss_i); improvement -= delta (1/2 delta A_ii + res_i)
@@ -20,37 +21,26 @@
 // then improvement *= scale, niter += 1, and the environment stops when improvement < tolerance or niter == iterations: the loop is bounded by the argument.
 // Outputs: cost = 1/2 y . y + f . b (no R term), qfrc_constraint = J^T f, qacc = qacc_smooth + L^-T y.
 //
-// LDS: mjh_pgs.h's arrays (the packed triangle of qLD, ALL of W at ld = nv | 1 reals a row -- an odd stride, so the lanes that walk down a column of rows in
-// efc_forward_rows hit different banks, while the sweeps read rows along k, consecutive lanes consecutive reals --, R, b, the friction bounds, w_i . w_i, f, y,
-// J^T f, 64 partial sums), then per contact slot: the block(s) A_c, 15 reals (an elliptic contact: the packed lower triangle of its up to 5 x 5 block; a pyramidal
+// LDS: mjh_dual.h's arrays, then per contact slot: the block(s) A_c, 15 reals (an elliptic contact: the packed lower triangle of its up to 5 x 5 block; a pyramidal
 // one: A_00, A_01, A_11 of each pair), mu (5 reals), and the table (first row, condim) as two ints.  The blocks are constant over the sweeps: formed once, after W.
 // The dot products of a block -- up to five residuals, or the i + 1 entries of row i of A_c -- go through ONE multi-value wave reduction (noslip_wave_sums: the DPP stages
-// of wave_sum, every value at each stage before the next, so the chains overlap); lane l sums k = l, l + 64, ... in ascending order: an order that depends on nv
-// alone.  Every lane carries the same scalars; the pair update and the QCQP are scalar code on them, their branches go through noslip_uniform and the contact table's entries through readfirstlane
+// of wave_sum, every value at each stage before the next, so the chains overlap), lane l summing as mjh_dual.h has it.
+// Every lane carries the same scalars; the pair update and the QCQP are scalar code on them, their branches go through noslip_uniform and the contact table's entries through readfirstlane
 // (one lane's value, read as a scalar: no divergence); a lane updates the y_k it owns.
 //
-// Per environment: efc_J twice (W, then J^T f), qLD, D, aref, frictionloss, force0, qacc_smooth and, with an elliptic cone, the friction of every contact slot in;
-// efc_force, qfrc_constraint, qacc, cost, improvement, niter out: read (2 nefc nv + nv^2 + 4 nefc + nv [+ 5 ncon]) reals, written (nefc + 2 nv + 2) reals + 4 bytes
-// (the account of mjh_model_kernel_io).
+// Per environment, on top of mjh_dual.h's account: force0 and, with an elliptic cone, the friction of every contact slot in: read (2 nefc nv + nv^2 + 4 nefc + nv
+// [+ 5 ncon]) reals (the account of mjh_model_kernel_io).
 #pragma once
-#include "mjh_efc.h"
+#include "mjh_dual.h"
 
 #define MJH_NOSLIP_BLOCK 15       // reals of A_c per contact slot
 #define MJH_NOSLIP_QCQP_ITERS 30  // factorisations of the multiplier's Newton iteration
 
 template <typename REAL>
-struct NoslipArgs {
-  const REAL *J, *D, *aref, *fl, *qLD, *qacc_smooth;  // [B, ...] leaves
-  const REAL* force0;                                 // [nefc] per environment at element stride force0_env (0: shared)
-  const REAL* friction;                               // [B, ncon, 5] contact.friction (read for elliptic cones)
-  const int *con_dim, *con_adr;                       // the model's static contact tables (ncon)
-  REAL *force, *qfrc_constraint, *qacc, *cost, *improvement;
-  int* niter;
-  int64_t force0_env;
-  int64_t env_base;  // first environment of this launch
-  REAL tolerance, inv_scale;
-  int nv, nefc, ne, nf, ncon, elliptic, iterations;
-  int chunk;  // rows of J per staging step
+struct NoslipArgs : DualArgs<REAL> {  // (force0 is required)
+  const REAL* friction;          // [B, ncon, 5] contact.friction (read for elliptic cones)
+  const int *con_dim, *con_adr;  // the model's static contact tables (ncon)
+  int ncon, elliptic;
 };
 
 // a condition every lane holds alike, as a scalar: the branch on it is uniform by construction
@@ -289,61 +279,21 @@ template <typename REAL>
 __global__ __launch_bounds__(MJH_WAVE) void mjh_noslip_kernel(NoslipArgs<REAL> a) {
   extern __shared__ double noslip_lds_raw[];
   const int l = (int)threadIdx.x, nv = a.nv, n = a.nefc, ld = nv | 1, ne = a.ne, ne_nf = a.ne + a.nf, nc = a.ncon;
-  REAL* Lp = reinterpret_cast<REAL*>(noslip_lds_raw);
-  REAL* W = Lp + nv * (nv + 1) / 2;
-  REAL* R = W + n * ld;
-  REAL* bb = R + n;
-  REAL* bound = bb + n;
-  REAL* ww = bound + n;  // w_i . w_i = A_ii
-  REAL* f = ww + n;
-  REAL* y = f + n;
-  REAL* c = y + nv;
-  REAL* red = c + nv;              // 64 reals
-  REAL* blk = red + MJH_WAVE;      // MJH_NOSLIP_BLOCK reals per contact slot
-  REAL* mu = blk + MJH_NOSLIP_BLOCK * nc;  // 5 reals per contact slot
+  const DualLds<REAL> s = dual_lds<REAL>(reinterpret_cast<REAL*>(noslip_lds_raw), nv, n);
+  REAL *W = s.W, *R = s.R, *bb = s.b, *bound = s.bound, *ww = s.ww, *f = s.f, *y = s.y;  // (ww_i = A_ii)
+  REAL* blk = s.end;                               // MJH_NOSLIP_BLOCK reals per contact slot
+  REAL* mu = blk + MJH_NOSLIP_BLOCK * nc;          // 5 reals per contact slot
   int* tab = reinterpret_cast<int*>(mu + 5 * nc);  // (first row, condim) per contact slot
   const int64_t e = a.env_base + blockIdx.x;
-  const REAL* src = a.qLD + e * nv * nv;
-  for (int t = l; t < nv * nv; t += MJH_WAVE) {  // every row whole (coalesced), its upper part dropped
-    const int i = t / nv, k = t - i * nv;
-    const REAL v = src[t];
-    if (k <= i) Lp[i * (i + 1) / 2 + k] = v;
-  }
   for (int t = l; t < nc; t += MJH_WAVE) {
     tab[2 * t] = a.con_adr[t];
     tab[2 * t + 1] = a.con_dim[t];
   }
   if (a.elliptic)
     for (int t = l; t < 5 * nc; t += MJH_WAVE) mu[t] = a.friction[e * 5 * nc + t];
-  const REAL* J = a.J + e * n * nv;
-  const REAL *D = a.D + e * n, *aref = a.aref + e * n, *fl = a.fl + e * n, *as = a.qacc_smooth + e * nv;
+  const REAL *J = a.J + e * n * nv, *as = a.qacc_smooth + e * nv;  // this environment's efc_J and qacc_smooth
   const REAL* f0 = a.force0 + e * a.force0_env;
-  for (int r0 = 0; r0 < n; r0 += a.chunk) {
-    const int rows = n - r0 < a.chunk ? n - r0 : a.chunk;
-    REAL* w = W + r0 * ld;
-    efc_load_rows<REAL>(w, ld, J + (int64_t)r0 * nv, rows, nv, l);
-    wave_sync();
-    for (int r = l; r < rows; r += MJH_WAVE) {  // b, while the rows are still J's
-      const REAL* m = w + r * ld;
-      REAL s = 0;
-      for (int k = 0; k < nv; k++) s += m[k] * as[k];
-      bb[r0 + r] = s - aref[r0 + r];
-    }
-    efc_forward_rows<REAL>(w, ld, Lp, rows, nv, l);  // (a lane reads and writes its own rows only)
-    for (int r = l; r < rows; r += MJH_WAVE) {
-      const int row = r0 + r;
-      const REAL* m = w + r * ld;
-      REAL s = 0;
-      for (int k = 0; k < nv; k++) s += m[k] * m[k];
-      const REAL d = D[row];
-      R[row] = d > 0 ? (REAL)1 / d : (REAL)0;
-      ww[row] = s;
-      bound[row] = fl[row];
-      f[row] = f0[row];
-    }
-  }
-  wave_sync();
-  efc_jt_accumulate<REAL>(y, true, W, ld, f, n, nv, red, l);  // y = sum_j f_j w_j
+  dual_stage<REAL>(a, s, e, J, as, l, [=](int row, REAL) { return f0[row]; });
   for (int ci = 0; ci < nc; ci++) {  // the blocks of A: constant over the sweeps
     const int adr = __builtin_amdgcn_readfirstlane(tab[2 * ci]), dim = __builtin_amdgcn_readfirstlane(tab[2 * ci + 1]);  // (scalars: the dispatch below is uniform)
     REAL* bk = blk + MJH_NOSLIP_BLOCK * ci;
@@ -403,33 +353,5 @@ __global__ __launch_bounds__(MJH_WAVE) void mjh_noslip_kernel(NoslipArgs<REAL> a
   }
   wave_sync();
 
-  REAL yy = 0, fb = 0;
-  for (int k = l; k < nv; k += MJH_WAVE) yy += y[k] * y[k];
-  for (int i = l; i < n; i += MJH_WAVE) {
-    const REAL fi = f[i];
-    fb += fi * bb[i];
-    a.force[e * n + i] = fi;
-  }
-  const REAL cost = (REAL)0.5 * wave_sum(yy) + wave_sum(fb);
-  if (l == 0) { a.cost[e] = cost; a.improvement[e] = improvement; a.niter[e] = niter; }
-
-  for (int r0 = 0; r0 < n; r0 += a.chunk) {  // J^T f: W is no longer needed, its first chunk stages J again
-    const int rows = n - r0 < a.chunk ? n - r0 : a.chunk;
-    wave_sync();
-    efc_load_rows<REAL>(W, ld, J + (int64_t)r0 * nv, rows, nv, l);
-    wave_sync();
-    efc_jt_accumulate<REAL>(c, r0 == 0, W, ld, f + r0, rows, nv, red, l);
-  }
-  for (int k = l; k < nv; k += MJH_WAVE) a.qfrc_constraint[e * nv + k] = c[k];
-
-  for (int i = nv - 1; i >= 0; i--) {  // L^T x = y in place
-    const REAL* Li = Lp + i * (i + 1) / 2;
-    wave_sync();
-    const REAL xi = y[i] / Li[i];
-    wave_sync();  // (every lane has read y[i] before it is overwritten)
-    for (int k = l; k < i; k += MJH_WAVE) y[k] = y[k] - Li[k] * xi;
-    if (l == 0) y[i] = xi;
-  }
-  wave_sync();
-  for (int k = l; k < nv; k += MJH_WAVE) a.qacc[e * nv + k] = as[k] + y[k];
+  dual_finish<REAL, false>(a, s, e, J, as, l, niter, improvement);
 }

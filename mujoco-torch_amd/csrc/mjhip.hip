@@ -1637,23 +1637,39 @@ int run_support(const mjhModel* m, const DevModel<REAL>& M, const mjhSupportArgs
   return 0;
 }
 
+// The kernels that stage efc_J in LDS (mjh_efc.h, mjh_dual.h): a workgroup is one wavefront, and small chunks keep many of them on a compute unit.
+constexpr int64_t kChunkBytes = 16 * 1024, kMaxLds = 160 * 1024;
+
+// out[0 .. 2] = rows of efc_J per LDS chunk (a staged row takes nv | 1 reals; never more than `most`, the rows worth holding at once), the number of chunks and
+// the rows of the last one; returns the chunk.
+static int64_t efc_chunks(int nv, int nefc, int64_t most, int real_bytes, int* out) {
+  const int64_t rb = (int64_t)(nv | 1) * real_bytes;
+  const int64_t chunk = std::max<int64_t>(1, std::min(kChunkBytes / rb, std::max<int64_t>(most, 1)));
+  const int64_t nchunk = nefc > 0 ? (nefc + chunk - 1) / chunk : 0, last = nefc > 0 ? nefc - (nchunk - 1) * chunk : 0;
+  out[0] = (int)chunk; out[1] = (int)nchunk; out[2] = (int)last;
+  return chunk;
+}
+
+// out[3] = the bytes of LDS that hold `reals`; returns 0, or -12 when they do not fit kMaxLds
+static int efc_lds(int64_t reals, int real_bytes, int* out) {
+  const int64_t lds = (reals * real_bytes + 15) & ~(int64_t)15;
+  out[3] = (int)std::min<int64_t>(lds, INT32_MAX);
+  return lds > kMaxLds ? -12 : 0;
+}
+
 // The chunk plan of mjh_constraint_space (mjh_efc.h): rows of efc_J per LDS chunk (a staged row takes nv | 1 reals), the number of chunks, the rows of the last
 // one and the LDS of a workgroup.  MUL_J: the chunk alone; MUL_JT: and 64 partial sums.  UPDATE: qacc, J^T force, M qacc, the chunk's forces, the chunk, which also stages qM, and 64 partial sums.
 // AR: the packed triangle of qLD and one chunk, two when there is more than one.  Returns 0, or -12 when AR does not fit kMaxLds.
 static int efc_plan(int op, int nv, int nefc, int real_bytes, int* out) {
-  constexpr int64_t kChunkBytes = 16 * 1024, kMaxLds = 160 * 1024;  // (a workgroup is one wavefront: small chunks keep many of them on a compute unit)
-  const int64_t ld = nv | 1, rb = ld * real_bytes;
-  const int64_t most = op == MJH_EFC_UPDATE ? std::max(nefc, nv) : nefc;  // rows worth holding at once
-  int64_t chunk = kChunkBytes / rb;
-  chunk = std::max<int64_t>(1, std::min(chunk, std::max<int64_t>(most, 1)));
-  const int64_t nchunk = nefc > 0 ? (nefc + chunk - 1) / chunk : 0, last = nefc > 0 ? nefc - (nchunk - 1) * chunk : 0;
+  const int64_t ld = nv | 1;
+  int plan[4];
+  const int64_t chunk = efc_chunks(nv, nefc, op == MJH_EFC_UPDATE ? std::max(nefc, nv) : nefc, real_bytes, plan);
   int64_t reals = chunk * ld;
   if (op == MJH_EFC_UPDATE) reals += 3 * (int64_t)nv + chunk;
   if (op == MJH_EFC_UPDATE || op == MJH_EFC_MUL_JT) reals += MJH_WAVE;  // the partial sums of efc_jt_accumulate
-  if (op == MJH_EFC_AR) reals = (int64_t)nv * (nv + 1) / 2 + (nchunk > 1 ? 2 : 1) * chunk * ld;
-  const int64_t lds = (reals * real_bytes + 15) & ~(int64_t)15;
-  if (lds > kMaxLds) return -12;
-  out[0] = (int)chunk; out[1] = (int)nchunk; out[2] = (int)last; out[3] = (int)lds;
+  if (op == MJH_EFC_AR) reals = (int64_t)nv * (nv + 1) / 2 + (plan[1] > 1 ? 2 : 1) * chunk * ld;
+  if (efc_lds(reals, real_bytes, plan)) return -12;  // (out stays as it came)
+  std::copy(plan, plan + 4, out);
   return 0;
 }
 
@@ -1705,44 +1721,47 @@ int run_constraint_space(const DevModel<REAL>& M, const mjhConstraintSpaceArgs* 
   return 0;
 }
 
-// The plan of mjh_pgs (mjh_pgs.h): rows of efc_J per staging step (16 KB of rows of nv | 1 reals, as mjh_constraint_space stages them), the number of steps, the
-// rows of the last one and the LDS of a workgroup: the packed triangle of qLD, all nefc rows of W, five reals a row (R, b, the friction bound, w_i . w_i, f), y and
-// J^T f, and 64 partial sums.  Returns 0, or -12 when that does not fit kMaxLds.
-static int pgs_plan(int nv, int nefc, int real_bytes, int* out) {
-  constexpr int64_t kChunkBytes = 16 * 1024, kMaxLds = 160 * 1024;
-  const int64_t ld = nv | 1, rb = ld * real_bytes;
-  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(kChunkBytes / rb, std::max(nefc, 1)));
-  const int64_t nchunk = nefc > 0 ? (nefc + chunk - 1) / chunk : 0, last = nefc > 0 ? nefc - (nchunk - 1) * chunk : 0;
-  const int64_t reals = (int64_t)nv * (nv + 1) / 2 + (int64_t)nefc * ld + 5 * (int64_t)nefc + 2 * (int64_t)nv + MJH_WAVE;
-  const int64_t lds = (reals * real_bytes + 15) & ~(int64_t)15;
-  out[0] = (int)chunk; out[1] = (int)nchunk; out[2] = (int)last; out[3] = (int)std::min<int64_t>(lds, INT32_MAX);
-  return lds > kMaxLds ? -12 : 0;
+// The plan of mjh_pgs (ncon = 0) and mjh_noslip (mjh_dual.h): rows of efc_J per staging step (as mjh_constraint_space stages them), the number of steps, the rows of
+// the last one and the LDS of a workgroup: the packed triangle of qLD, all nefc rows of W, five reals a row (R, b, the friction bound, w_i . w_i, f), y and J^T f,
+// 64 partial sums, and per contact slot the block(s) of A (15 reals), mu (5 reals) and the table entry (two ints, counted as two reals).  Returns 0, or -12 when
+// that does not fit kMaxLds (out is filled all the same).
+static int dual_plan(int nv, int nefc, int ncon, int real_bytes, int* out) {
+  efc_chunks(nv, nefc, nefc, real_bytes, out);
+  return efc_lds((int64_t)nv * (nv + 1) / 2 + (int64_t)nefc * (nv | 1) + 5 * (int64_t)nefc + 2 * (int64_t)nv + MJH_WAVE + (MJH_NOSLIP_BLOCK + 5 + 2) * (int64_t)ncon,
+                 real_bytes, out);
 }
 
-// projected Gauss-Seidel on the dual problem of a finished pass' leaves (mjh_pgs.h): one wavefront per environment
-template <typename REAL>
-int run_pgs(const DevModel<REAL>& M, const mjhPgsArgs* x, void* stream) {
-  const int nv = M.nv, n = M.nefc;
-  if (x->B < 0) return fail(-22, "pgs: B must be >= 0");
-  if (x->iterations < 0) return fail(-22, "pgs: iterations must be >= 0");
-  if (x->ne < 0 || x->nf < 0 || x->ne + x->nf > n) return fail(-22, "pgs: ne + nf outside [0, nefc]");
-  if (!(x->meaninertia > 0)) return fail(-22, "pgs: meaninertia must be > 0");
-  if (!(x->tolerance >= 0)) return fail(-22, "pgs: tolerance must be >= 0");
-  if (x->force0_env != 0 && x->force0_env < n) return fail(-22, "pgs: force0_env must be 0 (shared) or at least nefc");
+// mjh_pgs and mjh_noslip on a finished pass' leaves (mjh_pgs.h, mjh_noslip.h; X: mjhPgsArgs or mjhNoslipArgs): one wavefront per environment.  `noslip`: force0 is
+// required, the model's contact tables and cone go along with `friction` (x->contact_friction), and the kernel is mjh_noslip_kernel.
+template <typename REAL, typename X>
+int run_dual(const DevModel<REAL>& M, const X* x, void* stream, bool noslip, const void* friction) {
+  const std::string who = noslip ? "noslip" : "pgs";
+  const int nv = M.nv, n = M.nefc, ncon = noslip ? M.ncon : 0;
+  if (x->B < 0) return fail(-22, who + ": B must be >= 0");
+  if (x->iterations < 0) return fail(-22, who + ": iterations must be >= 0");
+  if (x->ne < 0 || x->nf < 0 || x->ne + x->nf > n) return fail(-22, who + ": ne + nf outside [0, nefc]");
+  if (!(x->meaninertia > 0)) return fail(-22, who + ": meaninertia must be > 0");
+  if (!(x->tolerance >= 0)) return fail(-22, who + ": tolerance must be >= 0");
+  if (x->force0_env != 0 && x->force0_env < n) return fail(-22, who + ": force0_env must be 0 (shared) or at least nefc");
   if (x->B == 0 || nv == 0 || n == 0) return 0;
+  const bool elliptic = noslip && M.cone == CONE_ELLIPTIC;
   if (!x->efc_J || !x->efc_D || !x->efc_aref || !x->efc_frictionloss || !x->qLD || !x->qacc_smooth || !x->efc_force || !x->qfrc_constraint || !x->qacc || !x->cost ||
-      !x->improvement || !x->niter)
-    return fail(-22, "pgs: null pointer");
+      !x->improvement || !x->niter || (noslip && !x->force0) || (elliptic && ncon > 0 && !friction))
+    return fail(-22, who + ": null pointer");
   int plan[4];
-  if (pgs_plan(nv, n, (int)sizeof(REAL), plan)) {
-    char msg[200];
-    snprintf(msg, sizeof(msg), "pgs: nv = %d, nefc = %d need %d bytes of LDS (qLD's triangle and all nefc rows of nv | 1 reals); a workgroup has %d", nv, n, plan[3],
-             160 * 1024);
+  if (dual_plan(nv, n, ncon, (int)sizeof(REAL), plan)) {
+    char msg[240];
+    if (noslip)
+      snprintf(msg, sizeof(msg), "noslip: nv = %d, nefc = %d, ncon = %d need %d bytes of LDS (qLD's triangle, all nefc rows of nv | 1 reals, 22 reals a contact); a workgroup has %d",
+               nv, n, ncon, plan[3], (int)kMaxLds);
+    else
+      snprintf(msg, sizeof(msg), "pgs: nv = %d, nefc = %d need %d bytes of LDS (qLD's triangle and all nefc rows of nv | 1 reals); a workgroup has %d", nv, n, plan[3],
+               (int)kMaxLds);
     return fail(-12, msg);
   }
   hipStream_t s = (hipStream_t)stream;
   timing_begin(s);
-  PgsArgs<REAL> a;
+  NoslipArgs<REAL> a;  // (mjh_pgs launches its DualArgs part)
   memset(&a, 0, sizeof(a));
   a.J = reinterpret_cast<const REAL*>(x->efc_J); a.D = reinterpret_cast<const REAL*>(x->efc_D); a.aref = reinterpret_cast<const REAL*>(x->efc_aref);
   a.fl = reinterpret_cast<const REAL*>(x->efc_frictionloss); a.qLD = reinterpret_cast<const REAL*>(x->qLD); a.qacc_smooth = reinterpret_cast<const REAL*>(x->qacc_smooth);
@@ -1751,72 +1770,21 @@ int run_pgs(const DevModel<REAL>& M, const mjhPgsArgs* x, void* stream) {
   a.cost = reinterpret_cast<REAL*>(x->cost); a.improvement = reinterpret_cast<REAL*>(x->improvement); a.niter = x->niter;
   a.tolerance = (REAL)x->tolerance; a.inv_scale = (REAL)(1.0 / (x->meaninertia * std::max(1, nv)));
   a.nv = nv; a.nefc = n; a.ne = x->ne; a.nf = x->nf; a.iterations = x->iterations; a.chunk = plan[0];
-  const size_t lds = (size_t)plan[3];
-  if (lds > 64 * 1024) HIP_TRY(allow_lds(&mjh_pgs_kernel<REAL>, (int)lds));
-  if (const int rc = launch_cut(x->B, 1, [&](int64_t first, int64_t, unsigned grid) {
-        a.env_base = first;
-        hipLaunchKernelGGL(mjh_pgs_kernel<REAL>, dim3(grid), dim3(MJH_WAVE), lds, s, a);
-      }))
-    return rc;
-  timing_mark(s, MJH_KERNEL_PGS);
-  return 0;
-}
-
-// The plan of mjh_noslip (mjh_noslip.h): mjh_pgs's staging and arrays, and per contact slot the block(s) of A (15 reals), mu (5 reals) and the table entry (two
-// ints, counted as two reals).  Returns 0, or -12 when that does not fit kMaxLds.
-static int noslip_plan(int nv, int nefc, int ncon, int real_bytes, int* out) {
-  constexpr int64_t kChunkBytes = 16 * 1024, kMaxLds = 160 * 1024;
-  const int64_t ld = nv | 1, rb = ld * real_bytes;
-  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(kChunkBytes / rb, std::max(nefc, 1)));
-  const int64_t nchunk = nefc > 0 ? (nefc + chunk - 1) / chunk : 0, last = nefc > 0 ? nefc - (nchunk - 1) * chunk : 0;
-  const int64_t reals = (int64_t)nv * (nv + 1) / 2 + (int64_t)nefc * ld + 5 * (int64_t)nefc + 2 * (int64_t)nv + MJH_WAVE + (MJH_NOSLIP_BLOCK + 5 + 2) * (int64_t)ncon;
-  const int64_t lds = (reals * real_bytes + 15) & ~(int64_t)15;
-  out[0] = (int)chunk; out[1] = (int)nchunk; out[2] = (int)last; out[3] = (int)std::min<int64_t>(lds, INT32_MAX);
-  return lds > kMaxLds ? -12 : 0;
-}
-
-// the no-slip sweeps on a finished pass' leaves (mjh_noslip.h): one wavefront per environment
-template <typename REAL>
-int run_noslip(const DevModel<REAL>& M, const mjhNoslipArgs* x, void* stream) {
-  const int nv = M.nv, n = M.nefc;
-  if (x->B < 0) return fail(-22, "noslip: B must be >= 0");
-  if (x->iterations < 0) return fail(-22, "noslip: iterations must be >= 0");
-  if (x->ne < 0 || x->nf < 0 || x->ne + x->nf > n) return fail(-22, "noslip: ne + nf outside [0, nefc]");
-  if (!(x->meaninertia > 0)) return fail(-22, "noslip: meaninertia must be > 0");
-  if (!(x->tolerance >= 0)) return fail(-22, "noslip: tolerance must be >= 0");
-  if (x->force0_env != 0 && x->force0_env < n) return fail(-22, "noslip: force0_env must be 0 (shared) or at least nefc");
-  if (x->B == 0 || nv == 0 || n == 0) return 0;
-  const bool elliptic = M.cone == CONE_ELLIPTIC;
-  if (!x->efc_J || !x->efc_D || !x->efc_aref || !x->efc_frictionloss || !x->qLD || !x->qacc_smooth || !x->force0 || !x->efc_force || !x->qfrc_constraint || !x->qacc ||
-      !x->cost || !x->improvement || !x->niter || (elliptic && M.ncon > 0 && !x->contact_friction))
-    return fail(-22, "noslip: null pointer");
-  int plan[4];
-  if (noslip_plan(nv, n, M.ncon, (int)sizeof(REAL), plan)) {
-    char msg[240];
-    snprintf(msg, sizeof(msg), "noslip: nv = %d, nefc = %d, ncon = %d need %d bytes of LDS (qLD's triangle, all nefc rows of nv | 1 reals, 22 reals a contact); a workgroup has %d",
-             nv, n, M.ncon, plan[3], 160 * 1024);
-    return fail(-12, msg);
+  if (noslip) {
+    a.friction = reinterpret_cast<const REAL*>(friction); a.con_dim = M.con_dim; a.con_adr = M.con_efc_address; a.ncon = ncon; a.elliptic = elliptic ? 1 : 0;
   }
-  hipStream_t s = (hipStream_t)stream;
-  timing_begin(s);
-  NoslipArgs<REAL> a;
-  memset(&a, 0, sizeof(a));
-  a.J = reinterpret_cast<const REAL*>(x->efc_J); a.D = reinterpret_cast<const REAL*>(x->efc_D); a.aref = reinterpret_cast<const REAL*>(x->efc_aref);
-  a.fl = reinterpret_cast<const REAL*>(x->efc_frictionloss); a.qLD = reinterpret_cast<const REAL*>(x->qLD); a.qacc_smooth = reinterpret_cast<const REAL*>(x->qacc_smooth);
-  a.force0 = reinterpret_cast<const REAL*>(x->force0); a.force0_env = x->force0_env; a.friction = reinterpret_cast<const REAL*>(x->contact_friction);
-  a.con_dim = M.con_dim; a.con_adr = M.con_efc_address; a.ncon = M.ncon; a.elliptic = elliptic ? 1 : 0;
-  a.force = reinterpret_cast<REAL*>(x->efc_force); a.qfrc_constraint = reinterpret_cast<REAL*>(x->qfrc_constraint); a.qacc = reinterpret_cast<REAL*>(x->qacc);
-  a.cost = reinterpret_cast<REAL*>(x->cost); a.improvement = reinterpret_cast<REAL*>(x->improvement); a.niter = x->niter;
-  a.tolerance = (REAL)x->tolerance; a.inv_scale = (REAL)(1.0 / (x->meaninertia * std::max(1, nv)));
-  a.nv = nv; a.nefc = n; a.ne = x->ne; a.nf = x->nf; a.iterations = x->iterations; a.chunk = plan[0];
   const size_t lds = (size_t)plan[3];
-  if (lds > 64 * 1024) HIP_TRY(allow_lds(&mjh_noslip_kernel<REAL>, (int)lds));
+  if (lds > 64 * 1024 && noslip) HIP_TRY(allow_lds(&mjh_noslip_kernel<REAL>, (int)lds));
+  if (lds > 64 * 1024 && !noslip) HIP_TRY(allow_lds(&mjh_pgs_kernel<REAL>, (int)lds));
   if (const int rc = launch_cut(x->B, 1, [&](int64_t first, int64_t, unsigned grid) {
         a.env_base = first;
-        hipLaunchKernelGGL(mjh_noslip_kernel<REAL>, dim3(grid), dim3(MJH_WAVE), lds, s, a);
+        PgsArgs<REAL> p;
+        static_cast<DualArgs<REAL>&>(p) = a;
+        if (noslip) hipLaunchKernelGGL(mjh_noslip_kernel<REAL>, dim3(grid), dim3(MJH_WAVE), lds, s, a);
+        else hipLaunchKernelGGL(mjh_pgs_kernel<REAL>, dim3(grid), dim3(MJH_WAVE), lds, s, p);
       }))
     return rc;
-  timing_mark(s, MJH_KERNEL_NOSLIP);
+  timing_mark(s, noslip ? MJH_KERNEL_NOSLIP : MJH_KERNEL_PGS);
   return 0;
 }
 
@@ -2415,23 +2383,23 @@ int mjh_constraint_space_plan(int op, int nv, int nefc, int real_bytes, int* chu
 
 int mjh_pgs(const mjhModel* m, const mjhPgsArgs* args, void* stream) {
   if (!m || !args) return fail(-22, "null argument");
-  return m->dtype == MJH_F64 ? run_pgs<double>(m->m64, args, stream) : run_pgs<float>(m->m32, args, stream);
+  return m->dtype == MJH_F64 ? run_dual<double>(m->m64, args, stream, false, nullptr) : run_dual<float>(m->m32, args, stream, false, nullptr);
 }
 
 int mjh_pgs_plan(int nv, int nefc, int real_bytes, int* chunk_nchunk_last_lds) {
   if (nv < 0 || nefc < 0 || (real_bytes != 4 && real_bytes != 8) || !chunk_nchunk_last_lds) return fail(-22, "pgs_plan: bad argument");
-  if (pgs_plan(nv, nefc, real_bytes, chunk_nchunk_last_lds)) return fail(-12, "pgs_plan: the model does not fit the LDS of a workgroup");
+  if (dual_plan(nv, nefc, 0, real_bytes, chunk_nchunk_last_lds)) return fail(-12, "pgs_plan: the model does not fit the LDS of a workgroup");
   return 0;
 }
 
 int mjh_noslip(const mjhModel* m, const mjhNoslipArgs* args, void* stream) {
   if (!m || !args) return fail(-22, "null argument");
-  return m->dtype == MJH_F64 ? run_noslip<double>(m->m64, args, stream) : run_noslip<float>(m->m32, args, stream);
+  return m->dtype == MJH_F64 ? run_dual<double>(m->m64, args, stream, true, args->contact_friction) : run_dual<float>(m->m32, args, stream, true, args->contact_friction);
 }
 
 int mjh_noslip_plan(int nv, int nefc, int ncon, int real_bytes, int* chunk_nchunk_last_lds) {
   if (nv < 0 || nefc < 0 || ncon < 0 || (real_bytes != 4 && real_bytes != 8) || !chunk_nchunk_last_lds) return fail(-22, "noslip_plan: bad argument");
-  if (noslip_plan(nv, nefc, ncon, real_bytes, chunk_nchunk_last_lds)) return fail(-12, "noslip_plan: the model does not fit the LDS of a workgroup");
+  if (dual_plan(nv, nefc, ncon, real_bytes, chunk_nchunk_last_lds)) return fail(-12, "noslip_plan: the model does not fit the LDS of a workgroup");
   return 0;
 }
 
@@ -2693,18 +2661,12 @@ static int kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes, b
     read_write_bytes[1] = io[kernel - MJH_KERNEL_EFC_MUL_J][1] * R + (kernel == MJH_KERNEL_EFC_UPDATE ? 4 * n : 0);
     return 0;
   }
-  if (kernel == MJH_KERNEL_PGS) {  // mjh_pgs, per environment: see include/mjhip.h
-    const int64_t R = f64 ? 8 : 4, nv = f64 ? m->m64.nv : m->m32.nv, n = f64 ? m->m64.nefc : m->m32.nefc;
-    if (nv == 0 || n == 0) return -2;
-    read_write_bytes[0] = (2 * n * nv + nv * nv + 3 * n + nv) * R;
-    read_write_bytes[1] = (n + 2 * nv + 2) * R + 4;
-    return 0;
-  }
-  if (kernel == MJH_KERNEL_NOSLIP) {  // mjh_noslip, per environment: see include/mjhip.h
+  if (kernel == MJH_KERNEL_PGS || kernel == MJH_KERNEL_NOSLIP) {  // mjh_pgs / mjh_noslip, per environment: see include/mjhip.h
     const int64_t R = f64 ? 8 : 4, nv = f64 ? m->m64.nv : m->m32.nv, n = f64 ? m->m64.nefc : m->m32.nefc, ncon = f64 ? m->m64.ncon : m->m32.ncon;
     const bool elliptic = (f64 ? m->m64.cone : m->m32.cone) == CONE_ELLIPTIC;
     if (nv == 0 || n == 0) return -2;
-    read_write_bytes[0] = (2 * n * nv + nv * nv + 4 * n + nv + (elliptic ? 5 * ncon : 0)) * R;
+    const int64_t start = kernel == MJH_KERNEL_PGS ? 0 : n + (elliptic ? 5 * ncon : 0);  // (no-slip: force0 and, with an elliptic cone, the friction)
+    read_write_bytes[0] = (2 * n * nv + nv * nv + 3 * n + nv + start) * R;
     read_write_bytes[1] = (n + 2 * nv + 2) * R + 4;
     return 0;
   }

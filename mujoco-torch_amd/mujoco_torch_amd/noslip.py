@@ -34,15 +34,13 @@ Every leading dimension of a leaf is the batch (S); nothing is written to the in
 
 from __future__ import annotations
 
-import ctypes
 import math
-import operator
 from typing import NamedTuple
 
 import numpy as np
 import torch
 
-from . import native
+from . import _dual, native
 from ._enums import ConeType
 from ._postpass import bind, call, check_leaves, probe, refuse_tracing, require_device
 
@@ -65,18 +63,8 @@ def plan(nv: int, nefc: int, ncon: int, dtype) -> tuple[int, int, int, int]:
     """(rows of ``efc_J`` per staging step, steps, rows of the last step, bytes of LDS per workgroup) of one call: the library's own plan (``mjh_noslip_plan``, a
     host computation).  A model whose ``qLD`` triangle, ``nefc`` rows of ``nv | 1`` reals and 22 reals a contact slot exceed a workgroup's LDS is a
     ``RuntimeError`` naming the sizes."""
-    lib = native.load_library()
-    fn = getattr(lib, "mjh_noslip_plan", None)
-    if fn is None:
-        raise RuntimeError(f"{native.LIB_PATH} predates {_WHAT} (no mjh_noslip_plan): rebuild the library")
-    out = (ctypes.c_int * 4)()
-    rc = fn(int(nv), int(nefc), int(ncon), 8 if dtype == torch.float64 else 4, out)
-    if rc == -12:
-        raise RuntimeError(f"solve_noslip: nv = {nv}, nefc = {nefc}, ncon = {ncon} in {dtype} need {out[3]} bytes of LDS (the qLD triangle, all nefc rows of "
-                           f"nv | 1 reals and 22 reals a contact slot); a workgroup has {160 * 1024}")
-    if rc != 0:
-        raise RuntimeError(f"noslip.plan failed ({rc}): {lib.mjh_last_error().decode()}")
-    return tuple(out)
+    return _dual.plan(_WHAT, "mjh_noslip_plan", dict(nv=nv, nefc=nefc, ncon=ncon), dtype,
+                      "the qLD triangle, all nefc rows of nv | 1 reals and 22 reals a contact slot")
 
 
 def solve_noslip(m, d, *, iterations: int | None = None, tolerance: float | None = None, force0: torch.Tensor | None = None) -> NoslipResult:
@@ -97,15 +85,7 @@ def solve_noslip(m, d, *, iterations: int | None = None, tolerance: float | None
         if iterations is None:
             raise ValueError(f"{name}: iterations must be given: this Model's options carry no noslip_iterations to default to")
     tolerance = NOSLIP_TOLERANCE if tolerance is None else tolerance
-    try:
-        iterations = operator.index(iterations)
-    except TypeError:
-        raise ValueError(f"{name}: iterations must be an integer >= 0; got {iterations!r}") from None
-    if iterations < 0 or iterations >= 2 ** 31:
-        raise ValueError(f"{name}: iterations must be an integer >= 0; got {iterations!r}")
-    tolerance = float(tolerance)
-    if not tolerance >= 0:
-        raise ValueError(f"{name}: tolerance must be >= 0; got {tolerance!r}")
+    iterations, tolerance = _dual.check_sweeps(name, iterations, tolerance)
     dims = np.asarray(m.tables.con_dim)[:ncon]
     odd = sorted(set(int(x) for x in dims if int(x) not in (1, 3, 4, 6)))
     if odd:
@@ -121,18 +101,10 @@ def solve_noslip(m, d, *, iterations: int | None = None, tolerance: float | None
     B = int(math.prod(batch)) if batch else 1
     stride = nefc if batch else 0
     if force0 is not None:
-        if not isinstance(force0, torch.Tensor) or tuple(force0.shape) not in (batch + (nefc,), (nefc,)):
-            got = tuple(force0.shape) if isinstance(force0, torch.Tensor) else type(force0).__name__
-            raise ValueError(f"{name}: force0= must have shape {batch + (nefc,)} (per environment) or {(nefc,)} (shared); got {got}")
-        if force0.dtype != dtype or force0.device != device:
-            raise ValueError(f"{name}: force0= is {force0.dtype} on {force0.device}, the Data is {dtype} on {device}")
-        stride = nefc if tuple(force0.shape) == batch + (nefc,) and batch else 0
-    meaninertia = float(m.stat.meaninertia)
-    if not meaninertia > 0:
-        raise ValueError(f"{name}: Model.stat.meaninertia is {meaninertia}, expected a positive number")
+        stride = _dual.check_force0(name, force0, batch, nefc, dtype, device)
+    meaninertia = _dual.check_meaninertia(name, m)
     require_device(device)
-    new = lambda *tail, dt=dtype: torch.empty(batch + tail, dtype=dt, device=device)
-    outs = dict(efc_force=new(nefc), qfrc_constraint=new(nv), qacc=new(nv), cost=new(), improvement=new(), niter=new(dt=torch.int32))
+    outs = _dual.new_outputs(batch, nefc, nv, dtype, device)
     if B == 0 or nv == 0 or nefc == 0:  # (no rows or no dofs: no force, qacc is qacc_smooth; without dofs J is empty and the rows are untouched)
         for t in outs.values():
             t.zero_()

@@ -23,15 +23,13 @@ Every leading dimension of a leaf is the batch (S); nothing is written to the in
 
 from __future__ import annotations
 
-import ctypes
 import math
-import operator
 from typing import NamedTuple
 
 import numpy as np
 import torch
 
-from . import native
+from . import _dual, native
 from ._enums import ConeType
 from ._postpass import bind, call, check_leaves, probe, refuse_tracing, require_device
 
@@ -52,18 +50,7 @@ class PGSResult(NamedTuple):
 def plan(nv: int, nefc: int, dtype) -> tuple[int, int, int, int]:
     """(rows of ``efc_J`` per staging step, steps, rows of the last step, bytes of LDS per workgroup) of one call: the library's own plan (``mjh_pgs_plan``, a
     host computation).  A model whose ``qLD`` triangle and ``nefc`` rows of ``nv | 1`` reals exceed a workgroup's LDS is a ``RuntimeError`` naming the sizes."""
-    lib = native.load_library()
-    fn = getattr(lib, "mjh_pgs_plan", None)
-    if fn is None:
-        raise RuntimeError(f"{native.LIB_PATH} predates {_WHAT} (no mjh_pgs_plan): rebuild the library")
-    out = (ctypes.c_int * 4)()
-    rc = fn(int(nv), int(nefc), 8 if dtype == torch.float64 else 4, out)
-    if rc == -12:
-        raise RuntimeError(f"solve_pgs: nv = {nv}, nefc = {nefc} in {dtype} need {out[3]} bytes of LDS (the qLD triangle and all nefc rows of nv | 1 reals); "
-                           f"a workgroup has {160 * 1024}")
-    if rc != 0:
-        raise RuntimeError(f"pgs.plan failed ({rc}): {lib.mjh_last_error().decode()}")
-    return tuple(out)
+    return _dual.plan(_WHAT, "mjh_pgs_plan", dict(nv=nv, nefc=nefc), dtype, "the qLD triangle and all nefc rows of nv | 1 reals")
 
 
 def _refuse_elliptic(m):
@@ -90,15 +77,7 @@ def solve_pgs(m, d, *, iterations: int | None = None, tolerance: float | None = 
     nv = int(m.nv)
     iterations = int(m.opt.iterations) if iterations is None else iterations
     tolerance = float(m.opt.tolerance) if tolerance is None else tolerance
-    try:
-        iterations = operator.index(iterations)
-    except TypeError:
-        raise ValueError(f"{name}: iterations must be an integer >= 0; got {iterations!r}") from None
-    if iterations < 0 or iterations >= 2 ** 31:
-        raise ValueError(f"{name}: iterations must be an integer >= 0; got {iterations!r}")
-    tolerance = float(tolerance)
-    if not tolerance >= 0:
-        raise ValueError(f"{name}: tolerance must be >= 0; got {tolerance!r}")
+    iterations, tolerance = _dual.check_sweeps(name, iterations, tolerance)
     _refuse_elliptic(m)
     tails = dict(efc_J=(nefc, nv), efc_D=(nefc,), efc_aref=(nefc,), efc_frictionloss=(nefc,), qLD=(nv, nv), qacc_smooth=(nv,))
     leaves = {n: getattr(d, n) for n in tails}
@@ -107,18 +86,10 @@ def solve_pgs(m, d, *, iterations: int | None = None, tolerance: float | None = 
     B = int(math.prod(batch)) if batch else 1
     stride = 0
     if force0 is not None:
-        if not isinstance(force0, torch.Tensor) or tuple(force0.shape) not in (batch + (nefc,), (nefc,)):
-            got = tuple(force0.shape) if isinstance(force0, torch.Tensor) else type(force0).__name__
-            raise ValueError(f"{name}: force0= must have shape {batch + (nefc,)} (per environment) or {(nefc,)} (shared); got {got}")
-        if force0.dtype != dtype or force0.device != device:
-            raise ValueError(f"{name}: force0= is {force0.dtype} on {force0.device}, the Data is {dtype} on {device}")
-        stride = nefc if tuple(force0.shape) == batch + (nefc,) and batch else 0
-    meaninertia = float(m.stat.meaninertia)
-    if not meaninertia > 0:
-        raise ValueError(f"{name}: Model.stat.meaninertia is {meaninertia}, expected a positive number")
+        stride = _dual.check_force0(name, force0, batch, nefc, dtype, device)
+    meaninertia = _dual.check_meaninertia(name, m)
     require_device(device)
-    new = lambda *tail, dt=dtype: torch.empty(batch + tail, dtype=dt, device=device)
-    outs = dict(efc_force=new(nefc), qfrc_constraint=new(nv), qacc=new(nv), cost=new(), improvement=new(), niter=new(dt=torch.int32))
+    outs = _dual.new_outputs(batch, nefc, nv, dtype, device)
     if B == 0 or nv == 0 or nefc == 0:  # (no rows or no dofs: no force, qacc is qacc_smooth; without dofs J is empty and the rows are untouched zeros)
         for t in outs.values():
             t.zero_()

@@ -1,4 +1,4 @@
-"""The constraint-space, PGS and no-slip kernels (csrc/mjh_efc.h, mjh_pgs.h, mjh_noslip.h) off their models' shapes and values: the family and the synthetic
+"""The constraint-space, PGS and no-slip kernels (csrc/mjh_efc.h, mjh_dual.h, mjh_pgs.h, mjh_noslip.h) off their models' shapes and values: the family and the synthetic
 leaves of tests/_efc_synth.py against the longdouble references tests/_efc_ref.py, _pgs_ref.py and _noslip_ref.py on the SAME rounded inputs, B = 3.  No ``forward``
 runs here: the kernels under test are the only device code.  tests/test_constraint_shapes_host.py pins the family's sizes, the table's conditions and the
 references on these inputs without a device.
@@ -20,6 +20,7 @@ Measured (one MI355X), worst error over bound per function, float64 / float32, a
   solve_pgs                    1.0e-5 (nv5 cold, 3 sweeps, improvement: 1.0e-14) / 9.3e-3 (nv33-f32 force0, 3 sweeps, qfrc_constraint: 1.9e-6)
   solve_noslip                 0.67 (nv5 elliptic, 3 sweeps, improvement: the sweep starts at the fixed point, the exact figure is 3e-20 and
                                any float64 evaluation leaves a rounding residue -- 1.1e-9 of rel_err's floor here, 4.2e-10 from the float64 reference) / 2.0e-2 (nv65-f32-last-one pyramidal, 3 sweeps, improvement: 4.0e-6)
+  cost(pgs) - cost(noslip)     6.2e-6 (nv33: 6.2e-15) / 1.7e-2 (nv33-f32: 3.4e-6), without a sweep; every other output of the two the same bits
 The first no-slip sweep's blocks over the table [no normal force, inside, boundary, put back, degenerate]: pyramidal [0, 942, 913, 0, 125], elliptic
 [0, 42, 129, 48, 183]; friction-loss rows [skipped, inside, on a bound] [0, 42, 30].  The zone-boundary test sees all four states on every model.
 """
@@ -276,6 +277,28 @@ def test_vectors_and_environments_are_independent(name):
     assert len(one) == len(whole) == 2 + 8 + 5 + 2 + 6 + 6
     for i, (a, b) in enumerate(zip(one, whole)):
         assert torch.equal(a, b[1:2]), i
+
+
+@pytest.mark.parametrize("name", ("nv5", "nv33", "nv33-f32", "nv65-f32-last-one"))
+def test_the_two_solvers_share_their_staging_and_ending(name):
+    """Without a sweep, from one feasible ``force0`` (the table's random start, projected by ``_pgs_ref.project``: ``solve_pgs`` projects it onto itself),
+    ``solve_pgs`` and ``solve_noslip`` run csrc/mjh_dual.h's staging and ending alone: ``efc_force``, ``qfrc_constraint`` and ``qacc`` come back with the same bits,
+    ``qfrc_constraint`` with the bits of ``mul_jac_t_vec(force0)`` as well (``efc_jt_accumulate`` over the same chunks), and the costs differ by the regulariser's
+    ``1/2 sum_i R_i f_i^2`` at TOL_PRE.  The entries: both paths of ``efc_jt_accumulate`` (5 and 33 / 65 dofs), three staging chunks and a last chunk of one row."""
+    m, mx, d, A, q = placed(name)
+    dtype = sy.BY_NAME[name].dtype
+    _, ne, nf, _, _, _ = sy.sizes(m)
+    f = pr.project(q["pgs0"], A["efc_frictionloss"], ne, nf)
+    assert feasible(m, A, f) and not np.array_equal(f, q["pgs0"]) and f.any()
+    f0 = dev(f, dtype)
+    p, n = mt.solve_pgs(mx, d, iterations=0, force0=f0), mt.solve_noslip(mx, d, iterations=0, force0=f0)
+    assert not p.niter.any() and not n.niter.any() and not p.improvement.any() and not n.improvement.any()
+    assert np.array_equal(host(p.efc_force), f)
+    for what in ("efc_force", "qfrc_constraint", "qacc"):
+        assert torch.equal(getattr(p, what), getattr(n, what)), what
+    assert torch.equal(p.qfrc_constraint, mt.mul_jac_t_vec(mx, d, f0))
+    R = np.where(A["efc_D"] > 0, 1 / np.where(A["efc_D"] > 0, er.ld(A["efc_D"]), 1), 0)
+    check("cost(pgs) - cost(noslip)", f64(host(p.cost)) - f64(host(n.cost)), (R * er.ld(f) ** 2).sum(-1) / 2, TOL_PRE[dtype])
 
 
 # ---- the value edges -------------------------------------------------------------------------------------------------------------------------------------
