@@ -24,6 +24,7 @@
  *   mjh_constraint_space <- MuJoCo's mj_mulJacVec / mj_mulJacTVec / mj_constraintUpdate and the Delassus matrix efc_AR, by the reference solver's definitions (_src/solver.py:293-357, 501-508)
  *   mjh_pgs            <- MuJoCo's mj_solPGS for rows of dimension one, on the dual problem of a finished pass (the reference's solvers are CG and Newton alone)
  *   mjh_noslip         <- MuJoCo's mj_solNoSlip (noslip_iterations): Gauss-Seidel on the friction dimensions with the unregularised matrix, after the main solver (the reference has no counterpart)
+ *   mjh_solve          <- solver.solve(m, d, fixed_iterations) on a caller's Data: the CG / Newton primal solver with its exact line search (_src/solver.py:244-553)
  *   mjh_jacobian       <- MuJoCo's mj_jacBody .. mj_jacGeom (as products), mj_jacDot, mj_jacSubtreeCom, mj_angmomMat (the reference has support.jac alone)
  *   mjh_integrate      <- derivative.deriv_smooth_vel, forward._implicit (implicitfast), forward._euler and their _advance, on a finished pass (_src/derivative.py:22-68, forward.py:255-328, 404-416)
  *
@@ -51,7 +52,7 @@
 extern "C" {
 #endif
 
-#define MJH_ABI_VERSION 25
+#define MJH_ABI_VERSION 26
 
 /* ---- dtype / flags ------------------------------------------------------------------- */
 #define MJH_F64 0
@@ -127,6 +128,7 @@ extern "C" {
 #define MJH_KERNEL_EFC_AR 53     /* ... MJH_EFC_AR: the Delassus matrix J M^-1 J^T + R and b                              */
 #define MJH_KERNEL_PGS 54        /* mjh_pgs: projected Gauss-Seidel sweeps on the dual problem (one wavefront per environment) */
 #define MJH_KERNEL_NOSLIP 55     /* mjh_noslip: no-slip sweeps on the friction dimensions, pyramidal pairs and elliptic QCQPs (one wavefront per environment) */
+#define MJH_KERNEL_SOLVE 56      /* mjh_solve: the CG / Newton primal solver with its exact line search on a finished pass (one wavefront per environment) */
 
 /* pair-function ids of the static collision table (collision_driver.py:106-125) */
 #define MJH_FN_PLANE_SPHERE 0
@@ -876,6 +878,51 @@ int mjh_noslip(const mjhModel* m, const mjhNoslipArgs* args, void* hip_stream);
  * would need), -22 for a bad argument. */
 int mjh_noslip_plan(int nv, int nefc, int ncon, int real_bytes, int* chunk_nchunk_last_lds);
 
+/* one mjh_solve call (definitions: csrc/mjh_solve.h; the algorithm is the reference's solver.solve, _src/solver.py:244-553).  Every pointer is device memory, reals of
+ * the model's dtype unless stated, batch-major over B environments; the leaves are a finished pass's: efc_J [B, nefc, nv], efc_D / efc_aref / efc_frictionloss
+ * [B, nefc], qM [B, nv, nv] (dense; the lower triangle is read), qLD [B, nv, nv] (lower triangle; CG only, may be NULL for Newton), qfrc_smooth / qacc_smooth /
+ * qacc_warmstart [B, nv] (qacc_warmstart: read when `warmstart`, may be NULL otherwise).  ne, nf: the model's equality and friction row counts; floss: the
+ * friction-loss linear zones apply (nf > 0 and DisableBit.FRICTIONLOSS clear); solver: 1 (CG) or 2 (Newton), mjtSolver's values; fixed: exactly `iterations` bodies
+ * and `ls_iterations` line-search bodies; warmstart: the start is qacc_warmstart when its cost is strictly below qacc_smooth's (0: qacc_smooth).  iterations == 1
+ * runs one body unconditionally; otherwise an environment stops when niter >= iterations, (prev_cost - cost) / scale < tolerance or |grad| / scale < tolerance,
+ * scale = meaninertia * max(1, nv).  Outputs, every one written: qacc_out and qacc_warmstart_out [B, nv] (the same values), qfrc_constraint_out [B, nv],
+ * efc_force_out [B, nefc], cost [B] (at the returned qacc), improvement [B] ((prev_cost - cost) / scale of the last body; +inf without one), grad_norm [B]
+ * (|grad| / scale at the returned qacc), niter [B] int32 (the bodies run).  No output may alias an input. */
+typedef struct mjhSolveArgs {
+  int32_t ne, nf, floss, solver, iterations, ls_iterations, fixed, warmstart;
+  int64_t B;
+  double tolerance, ls_tolerance, meaninertia;
+  const void* efc_J;
+  const void* efc_D;
+  const void* efc_aref;
+  const void* efc_frictionloss;
+  const void* qM;
+  const void* qLD;
+  const void* qfrc_smooth;
+  const void* qacc_smooth;
+  const void* qacc_warmstart;
+  void* qacc_out;
+  void* qacc_warmstart_out;
+  void* qfrc_constraint_out;
+  void* efc_force_out;
+  void* cost;
+  void* improvement;
+  void* grad_norm;
+  int32_t* niter;
+} mjhSolveArgs;
+
+/* the reference's constraint solver on a finished pass (see mjhSolveArgs).  One launch, one wavefront per environment, cut at the launch cap like mjh_pgs; runs on
+ * hip_stream without host synchronisation.  Returns 0 or a negative code (-12 when the working set does not fit the LDS of a workgroup: mjh_last_error names nv,
+ * nefc, the solver and the bytes; -22 for a null pointer or a bad size, before anything is launched); B == 0, nv == 0 and nefc == 0 are no-ops. */
+int mjh_solve(const mjhModel* m, const mjhSolveArgs* args, void* hip_stream);
+
+/* the plan mjh_solve uses for `solver` (1: CG, 2: Newton) on a model of nv dofs and nefc rows in reals of real_bytes (4 / 8) bytes, a host computation (no device is
+ * touched): out = {rows of efc_J per staging step, number of steps, rows of the last step, bytes of LDS per workgroup}.  The LDS holds two packed triangles (qM; qLD
+ * or Newton's H and its factor), all nefc rows of nv | 1 reals, five reals a row (six for Newton), ten dof vectors and 64 partial sums:
+ * nv (nv + 1) + nefc (nv | 1) + (5 | 6) nefc + 10 nv + 64 reals.  Returns 0, -12 when that does not fit a workgroup's LDS (out is filled all the same: the bytes
+ * it would need), -22 for a bad argument. */
+int mjh_solve_plan(int solver, int nv, int nefc, int real_bytes, int* chunk_nchunk_last_lds);
+
 /* mjh_jacobian operations (mjhJacobianArgs.op); MJH_KERNEL_JACOBIAN_POINT + op (matrix form) or MJH_KERNEL_JACOBIAN_POINT_VEC + op (product form) is the kernel id
  * the timing aid reports */
 #define MJH_JACOBIAN_POINT 0
@@ -991,7 +1038,7 @@ int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsi
 int mjh_model_lds_bytes(const mjhModel* m, int arena);
 
 /* measurement aid used by bench.py for the per-kernel roofline: while enabled, every kernel launch of mjh_step / mjh_forward is
- * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_ifd_perturb, mjh_ifd_difference, mjh_postconstraint, mjh_contact_sensors, mjh_energy, mjh_integrate, mjh_jacobian, mjh_geom_distance, mjh_qpos_arith, mjh_ik_site_step, mjh_constraint_space, mjh_pgs and mjh_noslip too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
+ * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_ifd_perturb, mjh_ifd_difference, mjh_postconstraint, mjh_contact_sensors, mjh_energy, mjh_integrate, mjh_jacobian, mjh_geom_distance, mjh_qpos_arith, mjh_ik_site_step, mjh_constraint_space, mjh_pgs, mjh_noslip and mjh_solve too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
  * the elapsed milliseconds and the kernel id (MJH_KERNEL_*).  Returns the number of launches (<= max) or a negative code. */
 int mjh_debug_phase_timing(int enable);
 int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
@@ -1026,7 +1073,10 @@ void mjh_debug_set_stamps(void* dev_ptr);
  * from zeros, without force0): per environment, efc_J twice (W, then J^T f), qLD, the three row leaves and qacc_smooth in, efc_force, qfrc_constraint, qacc and the
  * three scalars out; -2 for a model without dofs or rows.  MJH_KERNEL_NOSLIP (an mjh_noslip call): per environment, efc_J twice, qLD, the three row leaves, force0,
  * qacc_smooth and, with an elliptic cone, the friction of every contact slot in -- (2 nefc nv + nv^2 + 4 nefc + nv [+ 5 ncon]) reals --, efc_force, qfrc_constraint,
- * qacc and the three scalars out -- (nefc + 2 nv + 2) reals + 4 bytes; -2 for a model without dofs or rows.  Returns 0, or -2 when this model's step does not launch that kernel. */
+ * qacc and the three scalars out -- (nefc + 2 nv + 2) reals + 4 bytes; -2 for a model without dofs or rows.  MJH_KERNEL_SOLVE (an mjh_solve call with the warm start
+ * on): per environment, efc_J, qM and qLD once (qLD: counted for both solvers, Newton does not read it), efc_D and efc_frictionloss once, efc_aref twice (once per start
+ * candidate; a third time when the smooth start wins), qfrc_smooth, qacc_smooth and qacc_warmstart in -- (nefc nv + 2 nv^2 + 4 nefc + 3 nv) reals --, qacc,
+ * qacc_warmstart, qfrc_constraint, efc_force and the three scalars out -- (nefc + 3 nv + 3) reals + 4 bytes; -2 for a model without dofs or rows.  Returns 0, or -2 when this model's step does not launch that kernel. */
 int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes);
 
 /* last error message of the calling thread ("" if none) */

@@ -23,6 +23,7 @@
 #include "mjh_efc.h"
 #include "mjh_pgs.h"
 #include "mjh_noslip.h"
+#include "mjh_solve.h"
 #include "mjh_instances.h"
 
 #define MJH_CAT_(a, b) a##b
@@ -97,4 +98,7 @@ template __global__ void mjh_pgs_kernel<MJH_INST_REAL>(PgsArgs<MJH_INST_REAL>);
 #endif
 #if MJH_INST_GROUP == 35
 template __global__ void mjh_noslip_kernel<MJH_INST_REAL>(NoslipArgs<MJH_INST_REAL>);
+#endif
+#if MJH_INST_GROUP == 36
+template __global__ void mjh_solve_kernel<MJH_INST_REAL>(SolveArgs<MJH_INST_REAL>);
 #endif

@@ -34,6 +34,7 @@
 #include "mjh_ik.h"
 #include "mjh_efc.h"
 #include "mjh_pgs.h"
+#include "mjh_solve.h"
 #include "mjh_noslip.h"
 #include "mjh_instances.h"
 
@@ -106,6 +107,8 @@ EFC_(float)
 #undef EFC_
 extern template __global__ void mjh_pgs_kernel<double>(PgsArgs<double>);  // (build group 34)
 extern template __global__ void mjh_pgs_kernel<float>(PgsArgs<float>);
+extern template __global__ void mjh_solve_kernel<double>(SolveArgs<double>);  // (build group 36)
+extern template __global__ void mjh_solve_kernel<float>(SolveArgs<float>);
 extern template __global__ void mjh_noslip_kernel<double>(NoslipArgs<double>);  // (build group 35)
 extern template __global__ void mjh_noslip_kernel<float>(NoslipArgs<float>);
 #undef X_
@@ -1788,6 +1791,63 @@ int run_dual(const DevModel<REAL>& M, const X* x, void* stream, bool noslip, con
   return 0;
 }
 
+// The plan of mjh_solve (mjh_solve.h): rows of efc_J per staging step (as mjh_constraint_space stages them), the number of steps, the rows of the last one and the LDS of
+// a workgroup: two packed triangles (qM; qLD, or Newton's H and its factor), all nefc rows of J, five reals a row (D, frictionloss, jar, jv, force; Newton: and D active),
+// MJH_SOLVE_DOF_VECTORS dof vectors and 64 partial sums.  Returns 0, or -12 when that does not fit kMaxLds (out is filled all the same).
+static int solve_plan(int solver, int nv, int nefc, int real_bytes, int* out) {
+  efc_chunks(nv, nefc, nefc, real_bytes, out);
+  return efc_lds((int64_t)nv * (nv + 1) + (int64_t)nefc * (nv | 1) + (solver == MJH_SOLVER_NEWTON ? 6 : 5) * (int64_t)nefc + MJH_SOLVE_DOF_VECTORS * (int64_t)nv + MJH_WAVE,
+                 real_bytes, out);
+}
+
+// mjh_solve on a finished pass' leaves (mjh_solve.h): one wavefront per environment
+template <typename REAL>
+int run_solve(const DevModel<REAL>& M, const mjhSolveArgs* x, void* stream) {
+  const int nv = M.nv, n = M.nefc;
+  if (x->B < 0) return fail(-22, "solve: B must be >= 0");
+  if (x->solver != MJH_SOLVER_CG && x->solver != MJH_SOLVER_NEWTON) return fail(-22, "solve: solver must be 1 (CG) or 2 (Newton)");
+  if (x->iterations < 0 || x->ls_iterations < 0) return fail(-22, "solve: iterations and ls_iterations must be >= 0");
+  if (x->ne < 0 || x->nf < 0 || x->ne + x->nf > n) return fail(-22, "solve: ne + nf outside [0, nefc]");
+  if (!(x->meaninertia > 0)) return fail(-22, "solve: meaninertia must be > 0");
+  if (!(x->tolerance >= 0) || !(x->ls_tolerance >= 0)) return fail(-22, "solve: tolerance and ls_tolerance must be >= 0");
+  if (x->B == 0 || nv == 0 || n == 0) return 0;
+  const bool newton = x->solver == MJH_SOLVER_NEWTON;
+  if (!x->efc_J || !x->efc_D || !x->efc_aref || !x->efc_frictionloss || !x->qM || (!newton && !x->qLD) || !x->qfrc_smooth || !x->qacc_smooth ||
+      (x->warmstart && !x->qacc_warmstart) || !x->qacc_out || !x->qacc_warmstart_out || !x->qfrc_constraint_out || !x->efc_force_out || !x->cost || !x->improvement ||
+      !x->grad_norm || !x->niter)
+    return fail(-22, "solve: null pointer");
+  int plan[4];
+  if (solve_plan(x->solver, nv, n, (int)sizeof(REAL), plan)) {
+    char msg[240];
+    snprintf(msg, sizeof(msg), "solve: nv = %d, nefc = %d, solver = %s need %d bytes of LDS (two packed triangles and all nefc rows of nv | 1 reals); a workgroup has %d", nv, n,
+             newton ? "NEWTON" : "CG", plan[3], (int)kMaxLds);
+    return fail(-12, msg);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  timing_begin(s);
+  SolveArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+  a.J = reinterpret_cast<const REAL*>(x->efc_J); a.D = reinterpret_cast<const REAL*>(x->efc_D); a.aref = reinterpret_cast<const REAL*>(x->efc_aref);
+  a.fl = reinterpret_cast<const REAL*>(x->efc_frictionloss); a.qM = reinterpret_cast<const REAL*>(x->qM); a.qLD = reinterpret_cast<const REAL*>(x->qLD);
+  a.qfrc_smooth = reinterpret_cast<const REAL*>(x->qfrc_smooth); a.qacc_smooth = reinterpret_cast<const REAL*>(x->qacc_smooth);
+  a.qacc_warmstart = reinterpret_cast<const REAL*>(x->qacc_warmstart);
+  a.qacc = reinterpret_cast<REAL*>(x->qacc_out); a.qacc_warmstart_out = reinterpret_cast<REAL*>(x->qacc_warmstart_out);
+  a.qfrc_constraint = reinterpret_cast<REAL*>(x->qfrc_constraint_out); a.force = reinterpret_cast<REAL*>(x->efc_force_out); a.cost = reinterpret_cast<REAL*>(x->cost);
+  a.improvement = reinterpret_cast<REAL*>(x->improvement); a.grad_norm = reinterpret_cast<REAL*>(x->grad_norm); a.niter = x->niter;
+  a.tolerance = (REAL)x->tolerance; a.ls_gtol = (REAL)(x->tolerance * x->ls_tolerance); a.scale = (REAL)(x->meaninertia * std::max(1, nv));
+  a.nv = nv; a.nefc = n; a.ne_nf = x->ne + x->nf; a.floss = x->floss != 0; a.newton = newton; a.iterations = x->iterations; a.ls_iterations = x->ls_iterations;
+  a.fixed = x->fixed != 0; a.warmstart = x->warmstart != 0; a.chunk = plan[0];
+  const size_t lds = (size_t)plan[3];
+  if (lds > 64 * 1024) HIP_TRY(allow_lds(&mjh_solve_kernel<REAL>, (int)lds));
+  if (const int rc = launch_cut(x->B, 1, [&](int64_t first, int64_t, unsigned grid) {
+        a.env_base = first;
+        hipLaunchKernelGGL(mjh_solve_kernel<REAL>, dim3(grid), dim3(MJH_WAVE), lds, s, a);
+      }))
+    return rc;
+  timing_mark(s, MJH_KERNEL_SOLVE);
+  return 0;
+}
+
 // The tail of the kernels that give every workgroup a.envs environments of a.lanes lanes and a.lds_env reals of LDS each (postcon, consens, energy, integrate): the
 // batch goes out in cuts of environments [env_begin, env_begin + env_count), timed as kernel `id`.  The caller has made its last refusal.
 template <typename REAL, template <typename> class Args>
@@ -2392,6 +2452,18 @@ int mjh_pgs_plan(int nv, int nefc, int real_bytes, int* chunk_nchunk_last_lds) {
   return 0;
 }
 
+int mjh_solve(const mjhModel* m, const mjhSolveArgs* args, void* stream) {
+  if (!m || !args) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_solve<double>(m->m64, args, stream) : run_solve<float>(m->m32, args, stream);
+}
+
+int mjh_solve_plan(int solver, int nv, int nefc, int real_bytes, int* chunk_nchunk_last_lds) {
+  if ((solver != MJH_SOLVER_CG && solver != MJH_SOLVER_NEWTON) || nv < 0 || nefc < 0 || (real_bytes != 4 && real_bytes != 8) || !chunk_nchunk_last_lds)
+    return fail(-22, "solve_plan: bad argument");
+  if (solve_plan(solver, nv, nefc, real_bytes, chunk_nchunk_last_lds)) return fail(-12, "solve_plan: the model does not fit the LDS of a workgroup");
+  return 0;
+}
+
 int mjh_noslip(const mjhModel* m, const mjhNoslipArgs* args, void* stream) {
   if (!m || !args) return fail(-22, "null argument");
   return m->dtype == MJH_F64 ? run_dual<double>(m->m64, args, stream, true, args->contact_friction) : run_dual<float>(m->m32, args, stream, true, args->contact_friction);
@@ -2668,6 +2740,13 @@ static int kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes, b
     const int64_t start = kernel == MJH_KERNEL_PGS ? 0 : n + (elliptic ? 5 * ncon : 0);  // (no-slip: force0 and, with an elliptic cone, the friction)
     read_write_bytes[0] = (2 * n * nv + nv * nv + 3 * n + nv + start) * R;
     read_write_bytes[1] = (n + 2 * nv + 2) * R + 4;
+    return 0;
+  }
+  if (kernel == MJH_KERNEL_SOLVE) {  // mjh_solve with the warm start on, per environment: see include/mjhip.h
+    const int64_t R = f64 ? 8 : 4, nv = f64 ? m->m64.nv : m->m32.nv, n = f64 ? m->m64.nefc : m->m32.nefc;
+    if (nv == 0 || n == 0) return -2;
+    read_write_bytes[0] = (n * nv + 2 * nv * nv + 4 * n + 3 * nv) * R;
+    read_write_bytes[1] = (n + 3 * nv + 3) * R + 4;
     return 0;
   }
   if (kernel >= MJH_KERNEL_JACOBIAN_POINT && kernel <= MJH_KERNEL_JACOBIAN_ANGMOM_VEC) {  // mjh_jacobian, per environment for one query: see include/mjhip.h

@@ -316,6 +316,16 @@ class NoslipArgs(ctypes.Structure):
         (n, ctypes.c_void_p) for n in ("efc_force", "qfrc_constraint", "qacc", "cost", "improvement", "niter")]
 
 
+class SolveArgs(ctypes.Structure):
+    """include/mjhip.h mjhSolveArgs: one mjh_solve call (device pointers).  Bound below beside the ``ARGS`` table, like ``PgsArgs`` (tests/test_solve_host.py
+    compares it with the header)."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("ne", "nf", "floss", "solver", "iterations", "ls_iterations", "fixed", "warmstart")] + [("B", ctypes.c_int64)] + [
+        (n, ctypes.c_double) for n in ("tolerance", "ls_tolerance", "meaninertia")] + [(n, ctypes.c_void_p) for n in (
+        "efc_J", "efc_D", "efc_aref", "efc_frictionloss", "qM", "qLD", "qfrc_smooth", "qacc_smooth", "qacc_warmstart", "qacc_out", "qacc_warmstart_out",
+        "qfrc_constraint_out", "efc_force_out", "cost", "improvement", "grad_norm", "niter")]
+
+
 # the entry points that take (handle, args struct, stream): symbol -> the struct (tests/test_abi.py compares every struct with the header)
 ARGS = {"mjh_support": SupportArgs, "mjh_postconstraint": PostconArgs, "mjh_contact_sensors": ContactSensorArgs, "mjh_energy": EnergyArgs,
         "mjh_integrate": IntegrateArgs, "mjh_jacobian": JacobianArgs}
@@ -385,6 +395,11 @@ def load_library(path: str | None = None):
         lib.mjh_noslip.restype = ctypes.c_int
         lib.mjh_noslip_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         lib.mjh_noslip_plan.restype = ctypes.c_int
+    if hasattr(lib, "mjh_solve"):  # (likewise a build from before solve)
+        lib.mjh_solve.argtypes = [ctypes.c_void_p, ctypes.POINTER(SolveArgs), ctypes.c_void_p]
+        lib.mjh_solve.restype = ctypes.c_int
+        lib.mjh_solve_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        lib.mjh_solve_plan.restype = ctypes.c_int
     if hasattr(lib, "mjh_integrate_plan"):
         lib.mjh_integrate_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         lib.mjh_integrate_plan.restype = ctypes.c_int
