@@ -1,15 +1,17 @@
 // mjh_fd.h -- the kernels around the steps of a finite-difference transition Jacobian (mjh_fd_perturb, mjh_fd_difference; MuJoCo's
 // mjd_transitionFD) and of its vector-Jacobian product (mjh_fd_vjp, mjh_fd_tangent).  The steps themselves are plain mjh_step calls over the
-// perturbed environments.
+// perturbed environments.  What the family shares with the Jacobians of inverse dynamics (mjh_ifd.h) lives here too: FdCommon, the slot layout
+// (fd_unit, fd_slots) and the whole of a perturb workgroup (fd_perturb_slot, which mjh_ifd_perturb_kernel instantiates with INVERSE).
 //
 // Columns: c in [0, nv) nudges qpos along dof c (tangent space), [nv, 2 nv) qvel, [2 nv, ns) act, ns = 2 nv + na, and [ns, ns + nu) ctrl.  A call
 // serves the columns [col0, col0 + ncol) of every environment.  Column c of environment e owns nside (1, centered: 2) perturbed environments,
 // "slots", at index  w = (e * ncol + (c - col0)) * nside + side  of the scratch batch: environment-major, so every leaf of the scratch batch is
 // written and read in address order.  Which column a slot is, and which way it is nudged, is decoded from w here: there is no column list in memory.
 //
-// mjh_fd_perturb_kernel: one workgroup per slot.  It streams every listed input leaf of environment e into slot w (4-byte words, consecutive lanes on
+// mjh_fd_perturb_kernel (fd_perturb_slot): one workgroup per slot.  It streams every listed input leaf of environment e into slot w (4-byte words, consecutive lanes on
 //   consecutive addresses), then one lane nudges the slot's entry: x + h for qvel / act / ctrl and slide / hinge / free-translation dofs;
 //   quat_integrate(q, e_k, h) (mjh_device.h, forward.py:231-252) for the rotational dofs of ball / free joints; h = +eps on side 0, -eps on side 1.
+//   INVERSE changes what the columns from 2 nv on are: qacc (x + h) in place of act and ctrl.
 // ctrl (fd_ctrl_sides): with actuator_ctrllimited, a nudge is taken only when ctrl and the nudged ctrl both lie inside actuator_ctrlrange; the
 //   backward nudge only when centered or when the forward one was refused.  One-sided, the single slot carries the forward nudge, else the backward
 //   one, else the caller's ctrl unchanged; centered, a refused side carries it unchanged.  The flags depend on each environment's own ctrl and are
@@ -40,7 +42,12 @@ struct FdLeaf {
   int pad_;
 };
 
-// what both kernels read of the model and of the call
+// the units (slots / output elements / dofs) of a call, and where this launch starts among them (the host's launch_fd sets both)
+struct FdSpan {
+  int64_t first, total;
+};
+
+// what the kernels of the family read of the model and of the call; mjh_ifd.h: no act or ctrl columns, so na = nu = 0 and the ctrl fields are null
 template <typename REAL>
 struct FdCommon {
   const int *dof_jntid, *jnt_type, *jnt_qposadr, *jnt_dofadr, *act_ctrllimited;
@@ -49,15 +56,15 @@ struct FdCommon {
   REAL eps;
   int nq, nv, na, nu, nsd;
   int centered, col0, ncol;
-  int64_t first;        // first unit (slot / output element) of this launch
-  int64_t total;        // units of the call
+  FdSpan span;
 };
 
+// INVERSE reads qacc / p_qacc and leaves act / p_act / p_ctrl null; the transition kernel the other way round
 template <typename REAL>
 struct FdPerturbArgs {
   FdCommon<REAL> c;
-  const REAL *qpos, *qvel, *act;          // the caller's
-  REAL *p_qpos, *p_qvel, *p_act, *p_ctrl; // the scratch batch's
+  const REAL *qpos, *qvel, *act, *qacc;            // the caller's
+  REAL *p_qpos, *p_qvel, *p_act, *p_ctrl, *p_qacc; // the scratch batch's
   int nleaf, pad_;
   FdLeaf leaf[MJH_FD_MAX_LEAVES];
 };
@@ -91,7 +98,7 @@ struct FdTangentArgs {
   const REAL *g_in;           // pull: [B, nq], push: [B, nv]
   REAL *g_out;                // pull: [B, nv], push: [B, nq]
   int nq, nv, mode, pad_;
-  int64_t first, total;       // units (environment, dof) of this launch / of the call
+  FdSpan span;                // units: (environment, dof)
 };
 
 // bit 0: the forward nudge is taken, bit 1: the backward one
@@ -114,11 +121,29 @@ __device__ __forceinline__ void fd_dof(const int* dof_jntid, const int* jnt_type
   else { adr = qa + k; axis = -1; }
 }
 
+// The slots of column cl of the chunk in environment e: wp carries the forward nudge, wm the backward one (the same slot when not centered)
 template <typename REAL>
-__global__ __launch_bounds__(MJH_FD_PERTURB_WG) void mjh_fd_perturb_kernel(FdPerturbArgs<REAL> a) {
+__device__ __forceinline__ void fd_slots(const FdCommon<REAL>& c, int64_t e, int cl, int64_t& wp, int64_t& wm) {
+  const int nside = c.centered ? 2 : 1;
+  wp = (e * c.ncol + cl) * nside;
+  wm = wp + nside - 1;
+}
+
+// Unit g of a difference call, column fastest: environment e, row of nrow, column cl of the chunk
+template <typename REAL>
+__device__ __forceinline__ void fd_unit(const FdCommon<REAL>& c, int64_t g, int nrow, int64_t& e, int& row, int& cl) {
+  const int64_t t = g / c.ncol;
+  cl = (int)(g - t * c.ncol);
+  e = t / nrow;
+  row = (int)(t - e * nrow);
+}
+
+// One workgroup of a perturb kernel: slot w of the scratch batch, copied from its environment and nudged in its column
+template <typename REAL, bool INVERSE>
+__device__ __forceinline__ void fd_perturb_slot(const FdPerturbArgs<REAL>& a) {
   const FdCommon<REAL>& c = a.c;
-  const int64_t w = c.first + blockIdx.x;
-  if (w >= c.total) return;
+  const int64_t w = c.span.first + blockIdx.x;
+  if (w >= c.span.total) return;
   const int nside = c.centered ? 2 : 1, nslot = c.ncol * nside;
   const int64_t e = w / nslot;
   const int sl = (int)(w - e * nslot);
@@ -150,6 +175,9 @@ __global__ __launch_bounds__(MJH_FD_PERTURB_WG) void mjh_fd_perturb_kernel(FdPer
   } else if (col < 2 * nv) {
     const int d = col - nv;
     a.p_qvel[w * nv + d] = a.qvel[e * nv + d] + h;
+  } else if constexpr (INVERSE) {
+    const int d = col - 2 * nv;
+    a.p_qacc[w * nv + d] = a.qacc[e * nv + d] + h;
   } else if (col < ns) {
     const int i = col - 2 * nv;
     a.p_act[w * c.na + i] = a.act[e * c.na + i] + h;
@@ -161,6 +189,9 @@ __global__ __launch_bounds__(MJH_FD_PERTURB_WG) void mjh_fd_perturb_kernel(FdPer
     if (take) a.p_ctrl[w * c.nu + i] = c.ctrl[e * c.nu + i] + h;
   }
 }
+
+template <typename REAL>
+__global__ __launch_bounds__(MJH_FD_PERTURB_WG) void mjh_fd_perturb_kernel(FdPerturbArgs<REAL> a) { fd_perturb_slot<REAL, false>(a); }
 
 // element `row` of  y1 - y0  in tangent space
 template <typename REAL>
@@ -184,8 +215,8 @@ __device__ __forceinline__ REAL fd_sub(const FdCommon<REAL>& c, const FdState<RE
 // entry (row, col0 + cl) of environment e's A / B / C / D: `sides` is fd_ctrl_sides of a ctrl column, else 3 when centered and 1 when not
 template <typename REAL>
 __device__ __forceinline__ REAL fd_entry(const FdCommon<REAL>& c, const FdState<REAL>& y0, const FdState<REAL>& y, int64_t e, int cl, int row, bool is_ctrl, int sides) {
-  const int nside = c.centered ? 2 : 1;
-  const int64_t wp = (e * c.ncol + cl) * nside, wm = wp + nside - 1;  // the slots of the forward and of the backward nudge
+  int64_t wp, wm;
+  fd_slots(c, e, cl, wp, wm);
   const REAL h = c.eps;
   REAL v = 0;
   if (sides == 1) v = fd_sub(c, y, wp, y0, e, row) / h;
@@ -198,13 +229,13 @@ __device__ __forceinline__ REAL fd_entry(const FdCommon<REAL>& c, const FdState<
 template <typename REAL>
 __global__ __launch_bounds__(MJH_FD_DIFF_WG) void mjh_fd_difference_kernel(FdDiffArgs<REAL> a) {
   const FdCommon<REAL>& c = a.c;
-  const int64_t g = c.first + (int64_t)blockIdx.x * MJH_FD_DIFF_WG + threadIdx.x;
-  if (g >= c.total) return;
+  const int64_t g = c.span.first + (int64_t)blockIdx.x * MJH_FD_DIFF_WG + threadIdx.x;
+  if (g >= c.span.total) return;
   const int nv = c.nv, ns = 2 * nv + c.na, nrow = ns + (a.C ? c.nsd : 0);
-  const int64_t t = g / c.ncol;
-  const int cl = (int)(g - t * c.ncol);
-  const int64_t e = t / nrow;
-  const int row = (int)(t - e * nrow), col = c.col0 + cl;
+  int64_t e;
+  int row, cl;
+  fd_unit(c, g, nrow, e, row, cl);
+  const int col = c.col0 + cl;
   const bool is_ctrl = col >= ns;
   const int sides = is_ctrl ? fd_ctrl_sides(c, e, col - ns) : (c.centered ? 3 : 1);
   const REAL v = fd_entry(c, a.y0, a.y, e, cl, row, is_ctrl, sides);
@@ -221,8 +252,8 @@ template <typename REAL>
 __global__ __launch_bounds__(MJH_FD_VJP_WG) void mjh_fd_vjp_kernel(FdVjpArgs<REAL> a) {
   const FdCommon<REAL>& c = a.c;
   const int lane = threadIdx.x & (MJH_WAVE - 1);
-  const int64_t u = c.first + (int64_t)blockIdx.x * (MJH_FD_VJP_WG / MJH_WAVE) + threadIdx.x / MJH_WAVE;  // the same for all lanes of a wavefront
-  if (u >= c.total) return;
+  const int64_t u = c.span.first + (int64_t)blockIdx.x * (MJH_FD_VJP_WG / MJH_WAVE) + threadIdx.x / MJH_WAVE;  // the same for all lanes of a wavefront
+  if (u >= c.span.total) return;
   const int nv = c.nv, ns = 2 * nv + c.na, nrow = ns + (a.g_sens ? c.nsd : 0);
   const int64_t e = u / c.ncol;
   const int cl = (int)(u - e * c.ncol), col = c.col0 + cl;
@@ -255,8 +286,8 @@ __device__ __forceinline__ void fd_quat_dir(const REAL* q, int k, REAL* b) {
 // pull is g_in.  The lane of a quaternion's first rotational dof writes all four entries; every entry of qpos belongs to exactly one joint.
 template <typename REAL>
 __global__ __launch_bounds__(MJH_FD_TANGENT_WG) void mjh_fd_tangent_kernel(FdTangentArgs<REAL> a) {
-  const int64_t g = a.first + (int64_t)blockIdx.x * MJH_FD_TANGENT_WG + threadIdx.x;
-  if (g >= a.total) return;
+  const int64_t g = a.span.first + (int64_t)blockIdx.x * MJH_FD_TANGENT_WG + threadIdx.x;
+  if (g >= a.span.total) return;
   const int64_t e = g / a.nv;
   const int d = (int)(g - e * a.nv);
   int adr, axis;

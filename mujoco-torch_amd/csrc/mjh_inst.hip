@@ -75,7 +75,7 @@ template __global__ void mjh_jac_product_kernel<MJH_INST_REAL>(JacArgs<MJH_INST_
 template __global__ void mjh_quadric_kernel<MJH_INST_REAL>(KArgs<MJH_INST_REAL>);
 #endif
 #if MJH_INST_GROUP == 30
-template __global__ void mjh_ifd_perturb_kernel<MJH_INST_REAL>(IfdPerturbArgs<MJH_INST_REAL>);
+template __global__ void mjh_ifd_perturb_kernel<MJH_INST_REAL>(FdPerturbArgs<MJH_INST_REAL>);
 template __global__ void mjh_ifd_difference_kernel<MJH_INST_REAL>(IfdDiffArgs<MJH_INST_REAL>);
 #endif
 #if MJH_INST_GROUP == 31

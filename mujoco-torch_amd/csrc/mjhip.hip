@@ -82,8 +82,8 @@ extern template __global__ void mjh_integrate_kernel<double>(IntegrateArgs<doubl
 extern template __global__ void mjh_integrate_kernel<float>(IntegrateArgs<float>);
 extern template __global__ void mjh_quadric_kernel<double>(KArgs<double>);  // (build group 29)
 extern template __global__ void mjh_quadric_kernel<float>(KArgs<float>);
-extern template __global__ void mjh_ifd_perturb_kernel<double>(IfdPerturbArgs<double>);  // (build group 30)
-extern template __global__ void mjh_ifd_perturb_kernel<float>(IfdPerturbArgs<float>);
+extern template __global__ void mjh_ifd_perturb_kernel<double>(FdPerturbArgs<double>);  // (build group 30)
+extern template __global__ void mjh_ifd_perturb_kernel<float>(FdPerturbArgs<float>);
 extern template __global__ void mjh_ifd_difference_kernel<double>(IfdDiffArgs<double>);
 extern template __global__ void mjh_ifd_difference_kernel<float>(IfdDiffArgs<float>);
 extern template __global__ void mjh_geomdist_kernel<double>(GeomDistArgs<double>);  // (build group 31)
@@ -2114,7 +2114,8 @@ int run_integrate(const mjhModel* m, const DevModel<REAL>& M, const mjhIntegrate
 #undef P_
 #undef O_
 
-// ---- finite-difference transition Jacobians (mjh_fd.h): the launches on either side of the caller's mjh_step over the perturbed environments ----
+// ---- finite-difference Jacobians of a step (mjh_fd.h) and of inverse dynamics (mjh_ifd.h): the launches on either side of the caller's mjh_step / mjh_inverse
+// over the perturbed environments.  One check (fd_common), one perturb (run_fd_perturb) and one launch tail (launch_fd) serve both. ----
 
 // 4-byte words per environment of every mjhData slot, in struct order: reals, int32, int64, then the trailing input-only leaves
 template <typename REAL>
@@ -2128,56 +2129,86 @@ std::vector<int64_t> data_words(const mjhModel* m, const DevModel<REAL>& M) {
   return w;
 }
 
+// The refusals the family's entry points share, then what its kernels read of the model and of the call.  `inverse`: the columns are the 3 nv of
+// mjh_ifd.h (no act, no ctrl: na = nu = 0 in `c`), the rows counted against 2^31 its nv, and the messages say "ifd".
 template <typename REAL>
-int fd_common(const DevModel<REAL>& M, const mjhData* in, int64_t B, int col0, int ncol, double eps, int centered, FdCommon<REAL>& c) {
+int fd_common(const DevModel<REAL>& M, bool inverse, const void* ctrl, int64_t B, int col0, int ncol, double eps, int centered, FdCommon<REAL>& c) {
+  const std::string fam = inverse ? "ifd" : "fd";
   const int ns = 2 * M.nv + M.na;
-  if (B < 0) return fail(-22, "fd: B must be >= 0");
-  if (!(eps > 0) || !((REAL)eps > 0)) return fail(-22, "fd: eps must be positive in the model's dtype");
-  if (col0 < 0 || ncol < 1 || col0 + ncol > ns + M.nu) return fail(-22, "fd: columns outside [0, 2 nv + na + nu)");
-  if ((int64_t)ncol * 2 * (ns + M.nsensordata + 1) >= ((int64_t)1 << 31)) return fail(-22, "fd: too many columns in one call");
-  if (col0 + ncol > ns && !in->ctrl) return fail(-22, "fd: in.ctrl is required for the ctrl columns");
+  const int64_t cols = inverse ? 3 * (int64_t)M.nv : (int64_t)ns + M.nu, rows = inverse ? M.nv : ns;
+  if (B < 0) return fail(-22, fam + ": B must be >= 0");
+  if (!(eps > 0) || !((REAL)eps > 0)) return fail(-22, fam + ": eps must be positive in the model's dtype");
+  if (col0 < 0 || ncol < 1 || (int64_t)col0 + ncol > cols) return fail(-22, fam + ": columns outside [0, " + (inverse ? "3 nv)" : "2 nv + na + nu)"));
+  if ((int64_t)ncol * 2 * (rows + M.nsensordata + 1) >= ((int64_t)1 << 31)) return fail(-22, fam + ": too many columns in one call");
+  if (!inverse && col0 + ncol > ns && !ctrl) return fail(-22, "fd: in.ctrl is required for the ctrl columns");
   c.dof_jntid = M.dof_jntid; c.jnt_type = M.jnt_type; c.jnt_qposadr = M.jnt_qposadr; c.jnt_dofadr = M.jnt_dofadr;
-  c.act_ctrllimited = M.act_ctrllimited; c.act_ctrlrange = M.act_ctrlrange;
-  c.ctrl = reinterpret_cast<const REAL*>(in->ctrl);
+  if (!inverse) { c.act_ctrllimited = M.act_ctrllimited; c.act_ctrlrange = M.act_ctrlrange; c.ctrl = reinterpret_cast<const REAL*>(ctrl); }
   c.eps = (REAL)eps;
-  c.nq = M.nq; c.nv = M.nv; c.na = M.na; c.nu = M.nu; c.nsd = M.nsensordata;
+  c.nq = M.nq; c.nv = M.nv; c.na = inverse ? 0 : M.na; c.nu = inverse ? 0 : M.nu; c.nsd = M.nsensordata;
   c.centered = centered ? 1 : 0; c.col0 = col0; c.ncol = ncol;
   return 0;
 }
 
-template <typename REAL>
+// The tail of the family's run_* functions, after launch_envs: `units` units of the call go out `per_wg` to a workgroup of `wg` lanes, in cuts that
+// start at span.first (`span` lies inside `a`), timed as kernel `id`.  The caller has made its last refusal.
+template <typename Args>
+int launch_fd(void (*kernel)(Args), Args& a, FdSpan& span, int64_t units, int per_wg, int wg, void* stream, int id) {
+  hipStream_t s = (hipStream_t)stream;
+  span.total = units;
+  timing_begin(s);
+  if (const int rc = launch_cut(units, per_wg, [&](int64_t first, int64_t, unsigned grid) {
+        span.first = first;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(wg), 0, s, a);
+      }))
+    return rc;
+  timing_mark(s, id);
+  return 0;
+}
+
+// INVERSE: mjh_ifd_perturb, whose columns from 2 nv on are qacc; else mjh_fd_perturb (act, ctrl)
+template <typename REAL, bool INVERSE>
 int run_fd_perturb(const mjhModel* m, const DevModel<REAL>& M, const mjhData* in, mjhData* scratch, int64_t B, int col0, int ncol, double eps, int centered, void* stream) {
   static_assert(sizeof(FdPerturbArgs<REAL>) <= 4096, "kernel arguments exceed the 4 KiB kernarg segment");
+  const std::string fn = INVERSE ? "ifd_perturb" : "fd_perturb";
+  if (INVERSE && (B == 0 || M.nv == 0)) return B < 0 ? fail(-22, "ifd: B must be >= 0") : 0;
   FdPerturbArgs<REAL> a;
   memset(&a, 0, sizeof(a));
-  if (const int rc = fd_common(M, in, B, col0, ncol, eps, centered, a.c)) return rc;
+  if (const int rc = fd_common(M, INVERSE, in->ctrl, B, col0, ncol, eps, centered, a.c)) return rc;
   if (B == 0) return 0;
-  if (!in->qpos || !in->qvel || !scratch->qpos || !scratch->qvel || (M.na > 0 && !(in->act && scratch->act)) || (M.nu > 0 && !(in->ctrl && scratch->ctrl)))
+  if (INVERSE) {
+    if (!in->qpos || !in->qvel || !in->qacc || !scratch->qpos || !scratch->qvel || !scratch->qacc)
+      return fail(-22, "ifd_perturb: qpos, qvel and qacc are required in both Data");
+  } else if (!in->qpos || !in->qvel || !scratch->qpos || !scratch->qvel || (M.na > 0 && !(in->act && scratch->act)) || (M.nu > 0 && !(in->ctrl && scratch->ctrl))) {
     return fail(-22, "fd_perturb: qpos, qvel, act and ctrl are required in both Data");
+  }
   const std::vector<int64_t> words = data_words(m, M);
-  if (words.size() * sizeof(void*) != sizeof(mjhData)) return fail(-22, "fd_perturb: leaf table out of sync with mjhData");
+  if (words.size() * sizeof(void*) != sizeof(mjhData)) return fail(-22, fn + ": leaf table out of sync with mjhData");
   void* const* dp = reinterpret_cast<void* const*>(scratch);
   void* const* sp = reinterpret_cast<void* const*>(in);
   for (size_t i = 0; i < words.size(); i++) {
     if (!dp[i] || words[i] == 0) continue;
-    if (!sp[i]) return fail(-22, "fd_perturb: a leaf of the scratch Data is missing from the input Data");
-    if (a.nleaf == MJH_FD_MAX_LEAVES) return fail(-22, "fd_perturb: too many leaves in the scratch Data (input leaves only)");
+    if (!sp[i]) return fail(-22, fn + ": a leaf of the scratch Data is missing from the input Data");
+    if (a.nleaf == MJH_FD_MAX_LEAVES) return fail(-22, fn + ": too many leaves in the scratch Data (input leaves only)");
     FdLeaf& L = a.leaf[a.nleaf++];
     L.dst = (unsigned*)dp[i]; L.src = (const unsigned*)sp[i]; L.words = (int)words[i];
   }
-  a.qpos = reinterpret_cast<const REAL*>(in->qpos); a.qvel = reinterpret_cast<const REAL*>(in->qvel); a.act = reinterpret_cast<const REAL*>(in->act);
+  a.qpos = reinterpret_cast<const REAL*>(in->qpos); a.qvel = reinterpret_cast<const REAL*>(in->qvel);
   a.p_qpos = reinterpret_cast<REAL*>(scratch->qpos); a.p_qvel = reinterpret_cast<REAL*>(scratch->qvel);
-  a.p_act = reinterpret_cast<REAL*>(scratch->act); a.p_ctrl = reinterpret_cast<REAL*>(scratch->ctrl);
-  a.c.total = B * ncol * (centered ? 2 : 1);
-  hipStream_t s = (hipStream_t)stream;
-  timing_begin(s);
-  if (const int rc = launch_cut(a.c.total, 1, [&](int64_t first, int64_t, unsigned grid) {
-        a.c.first = first;
-        hipLaunchKernelGGL((mjh_fd_perturb_kernel<REAL>), dim3(grid), dim3(MJH_FD_PERTURB_WG), 0, s, a);
-      }))
-    return rc;
-  timing_mark(s, MJH_KERNEL_FD_PERTURB);
-  return 0;
+  if (INVERSE) {
+    a.qacc = reinterpret_cast<const REAL*>(in->qacc); a.p_qacc = reinterpret_cast<REAL*>(scratch->qacc);
+  } else {
+    a.act = reinterpret_cast<const REAL*>(in->act); a.p_act = reinterpret_cast<REAL*>(scratch->act); a.p_ctrl = reinterpret_cast<REAL*>(scratch->ctrl);
+  }
+  return launch_fd(INVERSE ? mjh_ifd_perturb_kernel<REAL> : mjh_fd_perturb_kernel<REAL>, a, a.c.span, B * ncol * (centered ? 2 : 1), 1, MJH_FD_PERTURB_WG, stream,
+                   INVERSE ? MJH_KERNEL_IFD_PERTURB : MJH_KERNEL_FD_PERTURB);
+}
+
+// the state (and, with `sens`, the sensordata) of a stepped Data as the difference and vjp kernels read it; false: a leaf they need is missing
+template <typename REAL>
+bool fd_state(const DevModel<REAL>& M, const mjhData* d, bool sens, FdState<REAL>& y) {
+  y.qpos = reinterpret_cast<const REAL*>(d->qpos); y.qvel = reinterpret_cast<const REAL*>(d->qvel);
+  y.act = reinterpret_cast<const REAL*>(d->act); y.sens = reinterpret_cast<const REAL*>(d->sensordata);
+  return y.qpos && y.qvel && (M.na == 0 || y.act) && (!sens || y.sens);
 }
 
 template <typename REAL>
@@ -2185,30 +2216,18 @@ int run_fd_difference(const DevModel<REAL>& M, const mjhData* in, const mjhData*
                       int centered, void* A, void* Bm, void* C, void* D, void* stream) {
   FdDiffArgs<REAL> a;
   memset(&a, 0, sizeof(a));
-  if (const int rc = fd_common(M, in, B, col0, ncol, eps, centered, a.c)) return rc;
+  if (const int rc = fd_common(M, false, in->ctrl, B, col0, ncol, eps, centered, a.c)) return rc;
   const int ns = 2 * M.nv + M.na;
   if (B == 0 || ns == 0) return 0;
   const bool sens = C != nullptr && M.nsensordata > 0;
   if ((C && !D && M.nu > 0) || (!C && D)) return fail(-22, "fd_difference: C and D go together");
   if (!A || (M.nu > 0 && !Bm)) return fail(-22, "fd_difference: A and Bm are required");
-  auto state = [&](const mjhData* d, FdState<REAL>& y) {
-    y.qpos = reinterpret_cast<const REAL*>(d->qpos); y.qvel = reinterpret_cast<const REAL*>(d->qvel);
-    y.act = reinterpret_cast<const REAL*>(d->act); y.sens = reinterpret_cast<const REAL*>(d->sensordata);
-    return y.qpos && y.qvel && (M.na == 0 || y.act) && (!sens || y.sens);
-  };
-  if (!state(nominal, a.y0) || !state(stepped, a.y)) return fail(-22, "fd_difference: qpos, qvel, act (and sensordata for C, D) are required in both stepped Data");
+  if (!fd_state(M, nominal, sens, a.y0) || !fd_state(M, stepped, sens, a.y))
+    return fail(-22, "fd_difference: qpos, qvel, act (and sensordata for C, D) are required in both stepped Data");
   a.A = reinterpret_cast<REAL*>(A); a.Bm = reinterpret_cast<REAL*>(Bm);
   a.C = sens ? reinterpret_cast<REAL*>(C) : nullptr; a.D = sens ? reinterpret_cast<REAL*>(D) : nullptr;
-  a.c.total = B * (ns + (sens ? M.nsensordata : 0)) * ncol;
-  hipStream_t s = (hipStream_t)stream;
-  timing_begin(s);
-  if (const int rc = launch_cut(a.c.total, MJH_FD_DIFF_WG, [&](int64_t first, int64_t, unsigned grid) {
-        a.c.first = first;
-        hipLaunchKernelGGL((mjh_fd_difference_kernel<REAL>), dim3(grid), dim3(MJH_FD_DIFF_WG), 0, s, a);
-      }))
-    return rc;
-  timing_mark(s, MJH_KERNEL_FD_DIFFERENCE);
-  return 0;
+  return launch_fd(mjh_fd_difference_kernel<REAL>, a, a.c.span, B * (ns + (sens ? M.nsensordata : 0)) * ncol, MJH_FD_DIFF_WG, MJH_FD_DIFF_WG, stream,
+                   MJH_KERNEL_FD_DIFFERENCE);
 }
 
 template <typename REAL>
@@ -2216,29 +2235,16 @@ int run_fd_vjp(const DevModel<REAL>& M, const mjhData* in, const mjhData* nomina
                int centered, const void* g_state, const void* g_sens, void* gx, void* gu, void* stream) {
   FdVjpArgs<REAL> a;
   memset(&a, 0, sizeof(a));
-  if (const int rc = fd_common(M, in, B, col0, ncol, eps, centered, a.c)) return rc;
+  if (const int rc = fd_common(M, false, in->ctrl, B, col0, ncol, eps, centered, a.c)) return rc;
   const int ns = 2 * M.nv + M.na;
   if (B == 0 || ns == 0) return 0;
   const bool sens = g_sens != nullptr && M.nsensordata > 0;
   if (!g_state || !gx || (M.nu > 0 && !gu)) return fail(-22, "fd_vjp: g_state, gx and gu are required");
-  auto state = [&](const mjhData* d, FdState<REAL>& y) {
-    y.qpos = reinterpret_cast<const REAL*>(d->qpos); y.qvel = reinterpret_cast<const REAL*>(d->qvel);
-    y.act = reinterpret_cast<const REAL*>(d->act); y.sens = reinterpret_cast<const REAL*>(d->sensordata);
-    return y.qpos && y.qvel && (M.na == 0 || y.act) && (!sens || y.sens);
-  };
-  if (!state(nominal, a.y0) || !state(stepped, a.y)) return fail(-22, "fd_vjp: qpos, qvel, act (and sensordata with g_sens) are required in both stepped Data");
+  if (!fd_state(M, nominal, sens, a.y0) || !fd_state(M, stepped, sens, a.y))
+    return fail(-22, "fd_vjp: qpos, qvel, act (and sensordata with g_sens) are required in both stepped Data");
   a.g_state = reinterpret_cast<const REAL*>(g_state); a.g_sens = sens ? reinterpret_cast<const REAL*>(g_sens) : nullptr;
   a.gx = reinterpret_cast<REAL*>(gx); a.gu = reinterpret_cast<REAL*>(gu);
-  a.c.total = B * ncol;
-  hipStream_t s = (hipStream_t)stream;
-  timing_begin(s);
-  if (const int rc = launch_cut(a.c.total, MJH_FD_VJP_WG / MJH_WAVE, [&](int64_t first, int64_t, unsigned grid) {
-        a.c.first = first;
-        hipLaunchKernelGGL((mjh_fd_vjp_kernel<REAL>), dim3(grid), dim3(MJH_FD_VJP_WG), 0, s, a);
-      }))
-    return rc;
-  timing_mark(s, MJH_KERNEL_FD_VJP);
-  return 0;
+  return launch_fd(mjh_fd_vjp_kernel<REAL>, a, a.c.span, B * ncol, MJH_FD_VJP_WG / MJH_WAVE, MJH_FD_VJP_WG, stream, MJH_KERNEL_FD_VJP);
 }
 
 template <typename REAL>
@@ -2252,97 +2258,29 @@ int run_fd_tangent(const DevModel<REAL>& M, const void* qpos, const void* g_in, 
   a.dof_jntid = M.dof_jntid; a.jnt_type = M.jnt_type; a.jnt_qposadr = M.jnt_qposadr; a.jnt_dofadr = M.jnt_dofadr;
   a.qpos = reinterpret_cast<const REAL*>(qpos); a.g_in = reinterpret_cast<const REAL*>(g_in); a.g_out = reinterpret_cast<REAL*>(g_out);
   a.nq = M.nq; a.nv = M.nv; a.mode = mode;
-  a.total = B * M.nv;
-  hipStream_t s = (hipStream_t)stream;
-  timing_begin(s);
-  if (const int rc = launch_cut(a.total, MJH_FD_TANGENT_WG, [&](int64_t first, int64_t, unsigned grid) {
-        a.first = first;
-        hipLaunchKernelGGL((mjh_fd_tangent_kernel<REAL>), dim3(grid), dim3(MJH_FD_TANGENT_WG), 0, s, a);
-      }))
-    return rc;
-  timing_mark(s, MJH_KERNEL_FD_TANGENT);
-  return 0;
+  return launch_fd(mjh_fd_tangent_kernel<REAL>, a, a.span, B * M.nv, MJH_FD_TANGENT_WG, MJH_FD_TANGENT_WG, stream, MJH_KERNEL_FD_TANGENT);
 }
 
-// ---- finite-difference Jacobians of inverse dynamics (mjh_ifd.h): the launches on either side of the caller's mjh_inverse over the perturbed environments ----
-
-template <typename REAL>
-int ifd_check(const DevModel<REAL>& M, int64_t B, int col0, int ncol, double eps) {
-  if (B < 0) return fail(-22, "ifd: B must be >= 0");
-  if (!(eps > 0) || !((REAL)eps > 0)) return fail(-22, "ifd: eps must be positive in the model's dtype");
-  if (col0 < 0 || ncol < 1 || (int64_t)col0 + ncol > 3 * (int64_t)M.nv) return fail(-22, "ifd: columns outside [0, 3 nv)");
-  if ((int64_t)ncol * 2 * (M.nv + M.nsensordata + 1) >= ((int64_t)1 << 31)) return fail(-22, "ifd: too many columns in one call");
-  return 0;
-}
-
-template <typename REAL>
-int run_ifd_perturb(const mjhModel* m, const DevModel<REAL>& M, const mjhData* in, mjhData* scratch, int64_t B, int col0, int ncol, double eps, int centered, void* stream) {
-  static_assert(sizeof(IfdPerturbArgs<REAL>) <= 4096, "kernel arguments exceed the 4 KiB kernarg segment");
-  if (B == 0 || M.nv == 0) return B < 0 ? fail(-22, "ifd: B must be >= 0") : 0;
-  if (const int rc = ifd_check(M, B, col0, ncol, eps)) return rc;
-  IfdPerturbArgs<REAL> a;
-  memset(&a, 0, sizeof(a));
-  if (!in->qpos || !in->qvel || !in->qacc || !scratch->qpos || !scratch->qvel || !scratch->qacc)
-    return fail(-22, "ifd_perturb: qpos, qvel and qacc are required in both Data");
-  const std::vector<int64_t> words = data_words(m, M);
-  if (words.size() * sizeof(void*) != sizeof(mjhData)) return fail(-22, "ifd_perturb: leaf table out of sync with mjhData");
-  void* const* dp = reinterpret_cast<void* const*>(scratch);
-  void* const* sp = reinterpret_cast<void* const*>(in);
-  for (size_t i = 0; i < words.size(); i++) {
-    if (!dp[i] || words[i] == 0) continue;
-    if (!sp[i]) return fail(-22, "ifd_perturb: a leaf of the scratch Data is missing from the input Data");
-    if (a.nleaf == MJH_FD_MAX_LEAVES) return fail(-22, "ifd_perturb: too many leaves in the scratch Data (input leaves only)");
-    FdLeaf& L = a.leaf[a.nleaf++];
-    L.dst = (unsigned*)dp[i]; L.src = (const unsigned*)sp[i]; L.words = (int)words[i];
-  }
-  a.dof_jntid = M.dof_jntid; a.jnt_type = M.jnt_type; a.jnt_qposadr = M.jnt_qposadr; a.jnt_dofadr = M.jnt_dofadr;
-  a.qpos = reinterpret_cast<const REAL*>(in->qpos); a.qvel = reinterpret_cast<const REAL*>(in->qvel); a.qacc = reinterpret_cast<const REAL*>(in->qacc);
-  a.p_qpos = reinterpret_cast<REAL*>(scratch->qpos); a.p_qvel = reinterpret_cast<REAL*>(scratch->qvel); a.p_qacc = reinterpret_cast<REAL*>(scratch->qacc);
-  a.eps = (REAL)eps;
-  a.nq = M.nq; a.nv = M.nv;
-  a.centered = centered ? 1 : 0; a.col0 = col0; a.ncol = ncol;
-  a.total = B * ncol * (centered ? 2 : 1);
-  hipStream_t s = (hipStream_t)stream;
-  timing_begin(s);
-  if (const int rc = launch_cut(a.total, 1, [&](int64_t first, int64_t, unsigned grid) {
-        a.first = first;
-        hipLaunchKernelGGL((mjh_ifd_perturb_kernel<REAL>), dim3(grid), dim3(MJH_IFD_PERTURB_WG), 0, s, a);
-      }))
-    return rc;
-  timing_mark(s, MJH_KERNEL_IFD_PERTURB);
-  return 0;
-}
-
+// the other end of mjh_ifd_perturb (run_fd_perturb<REAL, true>): qfrc_inverse and sensordata of the caller's mjh_inverse over the perturbed environments (mjh_ifd.h)
 template <typename REAL>
 int run_ifd_difference(const DevModel<REAL>& M, const void* f0, const void* s0, const void* f, const void* sd, int64_t B, int col0, int ncol, double eps,
                        int centered, void* DfDq, void* DfDv, void* DfDa, void* DsDq, void* DsDv, void* DsDa, void* stream) {
   if (B == 0 || M.nv == 0) return B < 0 ? fail(-22, "ifd: B must be >= 0") : 0;
-  if (const int rc = ifd_check(M, B, col0, ncol, eps)) return rc;
+  IfdDiffArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+  if (const int rc = fd_common(M, true, nullptr, B, col0, ncol, eps, centered, a.c)) return rc;
   const int given = (DsDq != nullptr) + (DsDv != nullptr) + (DsDa != nullptr);
   if (given != 0 && given != 3) return fail(-22, "ifd_difference: DsDq, DsDv and DsDa go together");
   const bool sens = given == 3 && M.nsensordata > 0;
   if (!DfDq || !DfDv || !DfDa) return fail(-22, "ifd_difference: DfDq, DfDv and DfDa are required");
   if (!f || (!centered && !f0)) return fail(-22, "ifd_difference: qfrc_inverse of the perturbed passes (and, one-sided, of the nominal pass) is required");
   if (sens && (!sd || (!centered && !s0))) return fail(-22, "ifd_difference: sensordata of the perturbed passes (and, one-sided, of the nominal pass) is required for DsD*");
-  IfdDiffArgs<REAL> a;
-  memset(&a, 0, sizeof(a));
   a.f0 = reinterpret_cast<const REAL*>(f0); a.s0 = reinterpret_cast<const REAL*>(s0);
   a.f = reinterpret_cast<const REAL*>(f); a.s = reinterpret_cast<const REAL*>(sd);
   a.DfDq = reinterpret_cast<REAL*>(DfDq); a.DfDv = reinterpret_cast<REAL*>(DfDv); a.DfDa = reinterpret_cast<REAL*>(DfDa);
   if (sens) { a.DsDq = reinterpret_cast<REAL*>(DsDq); a.DsDv = reinterpret_cast<REAL*>(DsDv); a.DsDa = reinterpret_cast<REAL*>(DsDa); }
-  a.eps = (REAL)eps;
-  a.nv = M.nv; a.nsd = sens ? M.nsensordata : 0;
-  a.centered = centered ? 1 : 0; a.col0 = col0; a.ncol = ncol;
-  a.total = B * (a.nv + a.nsd) * ncol;
-  hipStream_t s = (hipStream_t)stream;
-  timing_begin(s);
-  if (const int rc = launch_cut(a.total, MJH_IFD_DIFF_WG, [&](int64_t first, int64_t, unsigned grid) {
-        a.first = first;
-        hipLaunchKernelGGL((mjh_ifd_difference_kernel<REAL>), dim3(grid), dim3(MJH_IFD_DIFF_WG), 0, s, a);
-      }))
-    return rc;
-  timing_mark(s, MJH_KERNEL_IFD_DIFFERENCE);
-  return 0;
+  a.c.nsd = sens ? M.nsensordata : 0;
+  return launch_fd(mjh_ifd_difference_kernel<REAL>, a, a.c.span, B * (a.c.nv + a.c.nsd) * ncol, MJH_IFD_DIFF_WG, MJH_IFD_DIFF_WG, stream, MJH_KERNEL_IFD_DIFFERENCE);
 }
 
 }  // namespace
@@ -2507,8 +2445,8 @@ int mjh_integrate_plan(int nv, int nu, int ntendon, int real_bytes, int* lanes_e
 
 int mjh_fd_perturb(const mjhModel* m, const mjhData* in, mjhData* scratch, int64_t B, int col0, int ncol, double eps, int centered, void* stream) {
   if (!m || !in || !scratch) return fail(-22, "null argument");
-  return m->dtype == MJH_F64 ? run_fd_perturb<double>(m, m->m64, in, scratch, B, col0, ncol, eps, centered, stream)
-                             : run_fd_perturb<float>(m, m->m32, in, scratch, B, col0, ncol, eps, centered, stream);
+  return m->dtype == MJH_F64 ? run_fd_perturb<double, false>(m, m->m64, in, scratch, B, col0, ncol, eps, centered, stream)
+                             : run_fd_perturb<float, false>(m, m->m32, in, scratch, B, col0, ncol, eps, centered, stream);
 }
 
 int mjh_fd_difference(const mjhModel* m, const mjhData* in, const mjhData* nominal, const mjhData* stepped, int64_t B, int col0, int ncol, double eps,
@@ -2533,8 +2471,8 @@ int mjh_fd_tangent(const mjhModel* m, const void* qpos, const void* g_in, void* 
 
 int mjh_ifd_perturb(const mjhModel* m, const mjhData* in, mjhData* scratch, int64_t B, int col0, int ncol, double eps, int centered, void* stream) {
   if (!m || !in || !scratch) return fail(-22, "null argument");
-  return m->dtype == MJH_F64 ? run_ifd_perturb<double>(m, m->m64, in, scratch, B, col0, ncol, eps, centered, stream)
-                             : run_ifd_perturb<float>(m, m->m32, in, scratch, B, col0, ncol, eps, centered, stream);
+  return m->dtype == MJH_F64 ? run_fd_perturb<double, true>(m, m->m64, in, scratch, B, col0, ncol, eps, centered, stream)
+                             : run_fd_perturb<float, true>(m, m->m32, in, scratch, B, col0, ncol, eps, centered, stream);
 }
 
 int mjh_ifd_difference(const mjhModel* m, const void* nominal_f, const void* nominal_sens, const void* stepped_f, const void* stepped_sens, int64_t B,

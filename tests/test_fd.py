@@ -232,3 +232,124 @@ def test_refusals():
         torch.vmap(lambda q: mt.transition_fd(mg, dg[0].replace(qpos=q))[0])(dg.qpos)
     A, Bm, C, D = mt.transition_fd(mg, dg, sensors=True)  # no sensors: C, D with a zero first dimension
     assert C.shape == (4, 0, 4) and D.shape == (4, 0, 1)
+
+
+def test_native_refusals_of_the_fd_family():
+    """The seven entry points of the finite-difference family, called straight through the bindings with one defect each: the return code and the
+    text ``mjh_last_error`` is left with.  Every row is refused, or answered with 0, before anything is launched (all other pointers are real ones
+    of a stepped cartpole batch).  Before each row the error text is set to "null argument" by a call without a model: a row that returns 0 leaves
+    it there.  The two families order their early returns differently -- ``mjh_ifd_*`` answers ``B == 0`` before it looks at ``eps`` or the
+    columns, ``mjh_fd_*`` after -- and the rows with ``B = 0`` and ``eps = 0`` pin that.  The expected values were recorded from the library of the
+    commit before the perturb kernels were folded into one."""
+    import ctypes
+    import sys
+
+    from mujoco_torch_amd import native
+
+    fw = sys.modules["mujoco_torch_amd.forward"]
+    B = 2
+    mx, mg, dg = on_gpu("cartpole", F64, B)
+    _, mg32, _ = on_gpu("cartpole", F32, B)
+    dev = dg.qpos.device
+    nv, ns, nu = int(mx.nv), 2 * int(mx.nv) + int(mx.na), int(mx.nu)
+    assert (nv, ns, nu, int(mx.nq), int(getattr(mx, "nsensordata", 0) or 0)) == (2, 4, 1, 2, 0)
+    y0 = mt.step(mg, dg)
+    nm, nm32 = native.get_native_model(mg, dev, F64), native.get_native_model(mg32, dev, F32)
+    lib = nm.lib
+    derivative._bind(lib)
+    tab = fw._table(dg, (mg.tables.uid, F64, dev, B), nm.leaf_counts, B, F64, dev)
+    leaf_bytes = derivative._leaf_bytes(fw, nm.leaf_counts, F64)
+    slots = B * 3 * nv * 2  # room for every column of either family, centered
+    out_idx = tuple(fw._IDX[n] for n in fw._written_names(mg, True))
+    scratch = lambda names: derivative._make_scratch(fw, tuple(fw._IDX[n] for n in names if tab.arr[fw._IDX[n]] != 0), (), (), out_idx, leaf_bytes, slots, dev)
+    scr, iscr = scratch(derivative._INPUT_LEAVES), scratch(derivative._INVERSE_INPUT_LEAVES)
+    for s in (scr, iscr):
+        s.slab.zero_()
+    buf = lambda *shape: torch.zeros(shape, dtype=F64, device=dev)
+    bufs = {k: buf(*shape) for k, shape in dict(A=(B, ns, ns), Bm=(B, ns, nu), C=(64,), D=(64,), g=(B, ns), gx=(B, ns), gu=(B, nu), gq=(B, 2), gt=(B, nv), f0=(B, nv),
+                                                f=(slots, nv), Dq=(B, nv, nv), Dv=(B, nv, nv), Da=(B, nv, nv), S0=(64,), S1=(64,), S2=(64,)).items()}
+    P = {k: ctypes.c_void_p(t.data_ptr()) for k, t in bufs.items()}
+    keep = []
+
+    def without(struct, *names):  # the pointer struct with these leaves NULL
+        s = native.DataPtrs.from_buffer_copy(struct)
+        for n in names:
+            setattr(s, n, None)
+        keep.append(s)
+        return ctypes.byref(s)
+
+    st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    h, h32 = nm.handle, nm32.handle
+    pin, py0, pout = ctypes.byref(tab.struct), ctypes.byref(y0.__dict__["_ptab"].struct), ctypes.byref(scr.out)
+    eps = 1e-6
+    ORDER = {"fd_perturb": "m in scratch B col0 ncol eps centered", "fd_difference": "m in nominal stepped B col0 ncol eps centered A Bm C D",
+             "fd_vjp": "m in nominal stepped B col0 ncol eps centered g_state g_sens gx gu", "fd_tangent": "m qpos g_in g_out B mode",
+             "ifd_perturb": "m in scratch B col0 ncol eps centered",
+             "ifd_difference": "m f0 s0 f s B col0 ncol eps centered DfDq DfDv DfDa DsDq DsDv DsDa"}
+    common = {"m": h, "in": pin, "B": B, "col0": 0, "ncol": 1, "eps": eps, "centered": 0}
+    BASE = {"fd_perturb": dict(common, scratch=ctypes.byref(scr.inp)),
+            "fd_difference": dict(common, nominal=py0, stepped=pout, A=P["A"], Bm=P["Bm"], C=None, D=None),
+            "fd_vjp": dict(common, nominal=py0, stepped=pout, g_state=P["g"], g_sens=None, gx=P["gx"], gu=P["gu"]),
+            "fd_tangent": {"m": h, "qpos": ctypes.c_void_p(dg.qpos.data_ptr()), "g_in": P["gq"], "g_out": P["gt"], "B": B, "mode": 0},
+            "ifd_perturb": dict(common, scratch=ctypes.byref(iscr.inp)),
+            "ifd_difference": dict(common, f0=P["f0"], s0=None, f=P["f"], s=None, DfDq=P["Dq"], DfDv=P["Dv"], DfDa=P["Da"], DsDq=None, DsDv=None, DsDa=None)}
+    NAN, BIG = float("nan"), 1 << 30
+    E_B, E_EPS, E_COL, E_CTRL = "fd: B must be >= 0", "fd: eps must be positive in the model's dtype", "fd: columns outside [0, 2 nv + na + nu)", \
+        "fd: in.ctrl is required for the ctrl columns"
+    I_B, I_EPS, I_COL = "ifd: B must be >= 0", "ifd: eps must be positive in the model's dtype", "ifd: columns outside [0, 3 nv)"
+    E_PERT, I_PERT = "fd_perturb: qpos, qvel, act and ctrl are required in both Data", "ifd_perturb: qpos, qvel and qacc are required in both Data"
+    E_DIFF = "fd_difference: qpos, qvel, act (and sensordata for C, D) are required in both stepped Data"
+    E_VJP = "fd_vjp: qpos, qvel, act (and sensordata with g_sens) are required in both stepped Data"
+    I_F = "ifd_difference: qfrc_inverse of the perturbed passes (and, one-sided, of the nominal pass) is required"
+    NONE = "null argument"  # (what the priming call leaves: the row left nothing)
+    no_ctrl = without(tab.struct, "ctrl")
+    ROWS = [
+        ("fd_perturb", dict(B=-1), -22, E_B), ("fd_perturb", dict(eps=0.0), -22, E_EPS), ("fd_perturb", dict(eps=NAN), -22, E_EPS),
+        ("fd_perturb", dict(m=h32, eps=1e-60), -22, E_EPS), ("fd_perturb", dict(col0=-1), -22, E_COL), ("fd_perturb", dict(ncol=0), -22, E_COL),
+        ("fd_perturb", dict(ncol=ns + nu + 1), -22, E_COL), ("fd_perturb", dict(col0=ns + nu, ncol=1), -22, E_COL), ("fd_perturb", dict(ncol=BIG), -22, E_COL),
+        ("fd_perturb", {"in": no_ctrl, "col0": ns}, -22, E_CTRL), ("fd_perturb", dict(scratch=without(scr.inp, "qpos")), -22, E_PERT),
+        ("fd_perturb", {"in": without(tab.struct, "qvel")}, -22, E_PERT), ("fd_perturb", dict(B=0, eps=0.0), -22, E_EPS), ("fd_perturb", dict(B=0), 0, NONE),
+        ("fd_perturb", dict(B=0, scratch=without(scr.inp, "qpos")), 0, NONE),
+        ("fd_difference", dict(B=-1), -22, E_B), ("fd_difference", dict(eps=0.0), -22, E_EPS), ("fd_difference", dict(m=h32, eps=1e-60), -22, E_EPS),
+        ("fd_difference", dict(col0=-1), -22, E_COL), ("fd_difference", dict(ncol=0), -22, E_COL), ("fd_difference", dict(ncol=ns + nu + 1), -22, E_COL),
+        ("fd_difference", dict(ncol=BIG), -22, E_COL), ("fd_difference", {"in": no_ctrl, "col0": ns}, -22, E_CTRL),
+        ("fd_difference", dict(C=P["C"]), -22, "fd_difference: C and D go together"), ("fd_difference", dict(D=P["D"]), -22, "fd_difference: C and D go together"),
+        ("fd_difference", dict(A=None), -22, "fd_difference: A and Bm are required"), ("fd_difference", dict(Bm=None), -22, "fd_difference: A and Bm are required"),
+        ("fd_difference", dict(stepped=without(scr.out, "qpos")), -22, E_DIFF), ("fd_difference", dict(nominal=without(y0.__dict__["_ptab"].struct, "qvel")), -22, E_DIFF),
+        ("fd_difference", dict(B=0, eps=0.0), -22, E_EPS), ("fd_difference", dict(B=0), 0, NONE), ("fd_difference", dict(B=0, A=None), 0, NONE),
+        ("fd_vjp", dict(B=-1), -22, E_B), ("fd_vjp", dict(eps=NAN), -22, E_EPS), ("fd_vjp", dict(col0=ns + nu, ncol=1), -22, E_COL),
+        ("fd_vjp", {"in": no_ctrl, "col0": ns}, -22, E_CTRL), ("fd_vjp", dict(g_state=None), -22, "fd_vjp: g_state, gx and gu are required"),
+        ("fd_vjp", dict(gu=None), -22, "fd_vjp: g_state, gx and gu are required"), ("fd_vjp", dict(stepped=without(scr.out, "qvel")), -22, E_VJP),
+        ("fd_vjp", dict(B=0, eps=0.0), -22, E_EPS), ("fd_vjp", dict(B=0), 0, NONE), ("fd_vjp", dict(B=0, g_state=None), 0, NONE),
+        ("fd_tangent", dict(B=-1), -22, "fd_tangent: B must be >= 0"),
+        ("fd_tangent", dict(mode=2), -22, "fd_tangent: mode must be MJH_FD_TANGENT_PULL or MJH_FD_TANGENT_PUSH"),
+        ("fd_tangent", dict(B=0, mode=2), -22, "fd_tangent: mode must be MJH_FD_TANGENT_PULL or MJH_FD_TANGENT_PUSH"),
+        ("fd_tangent", dict(g_in=None), -22, "fd_tangent: qpos, g_in and g_out are required"), ("fd_tangent", dict(mode=1, qpos=None), -22, "fd_tangent: qpos, g_in and g_out are required"),
+        ("fd_tangent", dict(B=0), 0, NONE), ("fd_tangent", dict(B=0, g_out=None), 0, NONE),
+        ("ifd_perturb", dict(B=-1), -22, I_B), ("ifd_perturb", dict(eps=0.0), -22, I_EPS), ("ifd_perturb", dict(eps=NAN), -22, I_EPS),
+        ("ifd_perturb", dict(m=h32, eps=1e-60), -22, I_EPS), ("ifd_perturb", dict(col0=-1), -22, I_COL), ("ifd_perturb", dict(ncol=0), -22, I_COL),
+        ("ifd_perturb", dict(ncol=3 * nv + 1), -22, I_COL), ("ifd_perturb", dict(col0=3 * nv, ncol=1), -22, I_COL), ("ifd_perturb", dict(ncol=BIG), -22, I_COL),
+        ("ifd_perturb", dict(scratch=without(iscr.inp, "qpos")), -22, I_PERT), ("ifd_perturb", {"in": without(tab.struct, "qacc")}, -22, I_PERT),
+        ("ifd_perturb", dict(B=0, eps=0.0), 0, NONE), ("ifd_perturb", dict(B=0, ncol=0), 0, NONE), ("ifd_perturb", dict(B=0), 0, NONE),
+        ("ifd_difference", dict(B=-1), -22, I_B), ("ifd_difference", dict(eps=0.0), -22, I_EPS), ("ifd_difference", dict(m=h32, eps=1e-60), -22, I_EPS),
+        ("ifd_difference", dict(col0=-1), -22, I_COL), ("ifd_difference", dict(ncol=0), -22, I_COL), ("ifd_difference", dict(ncol=3 * nv + 1), -22, I_COL),
+        ("ifd_difference", dict(ncol=BIG), -22, I_COL),
+        ("ifd_difference", dict(DsDq=P["S0"], DsDv=P["S1"]), -22, "ifd_difference: DsDq, DsDv and DsDa go together"),
+        ("ifd_difference", dict(DsDa=P["S2"]), -22, "ifd_difference: DsDq, DsDv and DsDa go together"),
+        ("ifd_difference", dict(DfDv=None), -22, "ifd_difference: DfDq, DfDv and DfDa are required"), ("ifd_difference", dict(f0=None), -22, I_F),
+        ("ifd_difference", dict(f=None, centered=1), -22, I_F), ("ifd_difference", dict(B=0, eps=0.0), 0, NONE), ("ifd_difference", dict(B=0, col0=-1), 0, NONE),
+        ("ifd_difference", dict(B=0), 0, NONE),
+    ]
+    assert {r[0] for r in ROWS} == set(ORDER)
+    got = []
+    for name, over, _, _ in ROWS:
+        assert lib.mjh_fd_tangent(None, None, None, None, 0, 0, st) == -22 and lib.mjh_last_error() == b"null argument"
+        a = dict(BASE[name], **over)
+        rc = getattr(lib, "mjh_" + name)(*[a[k] for k in ORDER[name].split()], st)
+        got.append((rc, lib.mjh_last_error().decode()))
+    torch.cuda.synchronize()
+    for (name, over, rc, text), g in zip(ROWS, got):
+        shown = {k: v for k, v in over.items() if isinstance(v, (int, float))}
+        print(f"{name} {shown} {sorted(set(over) - set(shown))}: {g}")
+    wrong = [(name, sorted(over), g, (rc, text)) for (name, over, rc, text), g in zip(ROWS, got) if g != (rc, text)]
+    assert not wrong, wrong

@@ -288,3 +288,62 @@ def test_refusals():
     six = mt.inverse_fd(mgo, dgo, sensors=True)
     nsd = int(off.nsensordata)
     assert nsd > 0 and all(t.shape == (2, nsd, off.nv) and not bool(t.any()) for t in six[3:]) and all(bool(t.any()) for t in six[:3])
+
+
+def test_the_two_perturb_entry_points_agree_where_their_columns_coincide():
+    """Columns [0, 2 nv) mean the same to ``mjh_fd_perturb`` and ``mjh_ifd_perturb``: a nudge of qpos in tangent space, then of qvel.  Over the
+    same input leaves, the leaves both scratch batches carry come out equal bit for bit -- in a model with a ball joint, a free joint and ctrl
+    (it has no act: that leaf is empty in both batches), for windows whose slot counts are no multiple of a workgroup's 64 lanes (leaves of 1, nq and nv words end inside the streaming loop's
+    last trip)."""
+    import ctypes
+    import sys
+
+    from mujoco_torch_amd import derivative, native
+
+    fw = sys.modules["mujoco_torch_amd.forward"]
+    B, eps = 3, 1e-6
+    mx, mg, dg = on_gpu("ball_free_actuators", F64, B)
+    dev = dg.qpos.device
+    nq, nv, na, nu = int(mx.nq), int(mx.nv), int(mx.na), int(mx.nu)
+    types, qadr = mx.jnt_type.data.cpu().numpy(), np.asarray(mx.jnt_qposadr)
+    quat = np.zeros(nq, dtype=bool)
+    for t, a in zip(types, qadr):
+        if t == 0:    # free: the quaternion follows the translation
+            quat[a + 3:a + 7] = True
+        elif t == 1:  # ball
+            quat[a:a + 4] = True
+    assert nu > 0 and (types == 0).any() and (types == 1).any()
+    nm = native.get_native_model(mg, dev, F64)
+    lib, h = nm.lib, nm.handle
+    derivative._bind(lib)
+    tab = fw._table(dg, (mg.tables.uid, F64, dev, B), nm.leaf_counts, B, F64, dev)
+    leaf_bytes = derivative._leaf_bytes(fw, nm.leaf_counts, F64)
+    slots = B * 2 * nv * 2
+    scratch = lambda names: derivative._make_scratch(fw, tuple(fw._IDX[n] for n in names if tab.arr[fw._IDX[n]] != 0), (), (), (), leaf_bytes, slots, dev)
+    fd, ifd = scratch(derivative._INPUT_LEAVES), scratch(derivative._INVERSE_INPUT_LEAVES)
+
+    def view(scr, name, n):
+        off = int(np.frombuffer(scr.inp, dtype=np.uint64)[fw._IDX[name]]) - scr.slab.data_ptr()
+        assert 0 <= off and off + slots * n * 8 <= scr.slab.numel()
+        return scr.slab[off:off + slots * n * 8].view(F64).reshape(slots, n)
+
+    st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    for centered in (False, True):
+        nside = 2 if centered else 1
+        for c0, n in ((0, 2 * nv), (1, 2 * nv - 2)):
+            used = B * n * nside
+            assert used % 64 != 0
+            fd.slab.zero_()
+            ifd.slab.zero_()
+            for fn, scr in ((lib.mjh_fd_perturb, fd), (lib.mjh_ifd_perturb, ifd)):
+                rc = fn(h, ctypes.byref(tab.struct), ctypes.byref(scr.inp), B, c0, n, eps, int(centered), st)
+                assert rc == 0, lib.mjh_last_error().decode()
+            for name, w in (("qpos", nq), ("qvel", nv), ("act", na), ("ctrl", nu), ("qacc_warmstart", nv)):
+                if w == 0:
+                    assert tab.arr[fw._IDX[name]] == 0
+                    continue
+                assert torch.equal(view(fd, name, w), view(ifd, name, w)), (centered, c0, name)
+            qpos = view(ifd, "qpos", nq)[:used].reshape(B, n * nside, nq)
+            qvel = view(ifd, "qvel", nv)[:used].reshape(B, n * nside, nv)
+            assert bool((qpos != dg.qpos[:, None, :])[..., torch.tensor(quat, device=dev)].any()) and bool((qvel != dg.qvel[:, None, :]).any())
+            assert not bool(view(ifd, "qpos", nq)[used:].any())  # nothing past the call's slots
