@@ -281,8 +281,11 @@ __device__ __forceinline__ const KArgs<REAL>& kargs() {
     __builtin_amdgcn_sched_barrier(0);                                                               \
   } while (0)
 #define STAMP0() do { stamp_prev = __builtin_amdgcn_s_memtime(); } while (0)
+// a sub-stamp that first waits for every load in flight (vmcnt and lgkmcnt at 0): splits a section into "what it waits for" and "what it computes"
+#define STAMPW(slot) do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0x0070); STAMP(slot); } while (0)
 #else
 #define STAMP(slot) do {} while (0)
+#define STAMPW(slot) do {} while (0)
 #define STAMP0() do {} while (0)
 #endif
 
@@ -3888,7 +3891,7 @@ struct Env {
   //  * the efc_J leaf, efc_frictionloss and the constant contact leaves NOT stored here: cs_deferred_stores() writes them behind the solve, where nothing waits for them
   //    (vmcnt is in order: 11 KB of row stores per environment in front of the solve's qM reads made every wave wait for its own stores to land).
   // Arithmetic and operation order per value as in make_constraint().
-  template <int NMAX>
+  template <int NMAX, bool BATCH = false>
   __device__ __forceinline__ void make_constraint_cs(Sol2Pre<REAL, NMAX>& pre, Sol2Con<REAL>& C) {
     const int l = lane_here();
 #if MJH_CS_PF >= 2
@@ -3945,17 +3948,11 @@ struct Env {
     STAMP(23);
     // ---- rows of the active contacts, compact: _instantiate_contact_* :409-583 ----
     REAL* const Jc = S.efc_Jc();  // (the geom frames under it are dead: the narrow phase is over)
-    for (int w = l; w < nact * nv; w += W) {
-      int a, d;
-      split_index(w, nv, M.inv_nv, a, d);
-      const int c = act_list[a];
-      const int dim = M.con_dim[c];
-      const int* cb = M.con_body + 4 * c;
-      const int root1 = cb[2], root2 = cb[3];
-      const REAL on1 = (REAL)((M.con_dmask[2 * c] >> d) & 1ull), on2 = (REAL)((M.con_dmask[2 * c + 1] >> d) & 1ull);
+    // one (active contact a, dof d) item: the row entries of contact c = act_list[a] in column d.  f0, f1: the contact's first two friction coefficients when PREF (read ahead by the caller)
+    auto contact_item = [&](int a, int d, int c, int dim, int root1, int root2, REAL on1, REAL on2, bool PREF, REAL f0, REAL f1) {
+      const REAL* fric = M.con_friction + 5 * c;
       const REAL* fr = S.con_frame() + 9 * c;
       const REAL* cpos = S.con_pos() + 3 * c;
-      const REAL* fric = M.con_friction + 5 * c;
       REAL jp1[3], jr1[3], jp2[3], jr2[3];
       jac_dof_root(cpos, root2, on2, d, jp2, jr2);
       jac_dof_root(cpos, root1, on1, d, jp1, jr1);
@@ -3973,11 +3970,68 @@ struct Env {
       } else if (!elliptic) {  // _instantiate_contact_pyramidal :454-516
         const int nedge = 2 * (dim - 1);
         for (int ed = 0; ed < nedge; ed++) {
-          const REAL f = fric[ed >> 1] * ((ed & 1) ? (REAL)-1 : (REAL)1);
+          const int fi = ed >> 1;
+          const REAL fv = (PREF && fi < 2) ? (fi == 0 ? f0 : f1) : fric[fi];
+          const REAL f = fv * ((ed & 1) ? (REAL)-1 : (REAL)1);
           dst[ed * nv] = diff[0] + diff[1 + (ed >> 1)] * f;
         }
       } else {  // _instantiate_contact_elliptic :519-583
         for (int r = 0; r < dim; r++) dst[r * nv] = diff[r];
+      }
+    };
+    const int nitem = nact * nv;
+    if constexpr (BATCH) {
+      // BATCH: a trip of the rolled loop below is an arena read (the contact of the item) and a round trip through L2 (its tables) in front of its arithmetic, and one more round
+      // trip for each pair of pyramid edges (the friction coefficient).  Here the items and contacts of CT trips are formed first, then the table entries of all of them are
+      // requested -- they depend on the compact list only -- and the trips compute behind ONE wait: the humanoid's eight pyramidal contacts (7 trips) are two such blocks, 32
+      // frictionless contacts (27 trips) seven.  A trip no lane of the wave has an item for is skipped (the two environments of a wave run their own counts).  Per value the
+      // same operations in the same order.  (profiles/r09/notes.md: blocks of 2, 4 and 8 trips, and 8 trips with the rolled loop behind them)
+      constexpr int CT = 4;
+      const unsigned* dm32 = reinterpret_cast<const unsigned*>(M.con_dmask);  // (little-endian halves of the 64-bit dof masks: the half that holds bit d)
+      for (int base = 0; base < nitem; base += CT * W) {
+        int ta[CT], td[CT], tc[CT], tdim[CT], tr1[CT], tr2[CT];
+        unsigned tm1[CT], tm2[CT];
+        REAL tf[CT][2];  // (the first two friction coefficients: condim <= 3; further ones are read at their use)
+#pragma unroll
+        for (int t = 0; t < CT; t++) {
+          const int w = base + l + t * W;
+          if (w < nitem) { split_index(w, nv, M.inv_nv, ta[t], td[t]); tc[t] = act_list[ta[t]]; }
+        }
+#pragma unroll
+        for (int t = 0; t < CT; t++) {
+          const int w = base + l + t * W;
+          if (w < nitem) {
+            const int c = tc[t], hw = td[t] >> 5;
+            tdim[t] = M.con_dim[c];
+            tr1[t] = M.con_body[4 * c + 2]; tr2[t] = M.con_body[4 * c + 3];
+            tm1[t] = dm32[4 * c + hw]; tm2[t] = dm32[4 * c + 2 + hw];
+            tf[t][0] = 0; tf[t][1] = 0;
+            if (!elliptic) { tf[t][0] = M.con_friction[5 * c]; tf[t][1] = M.con_friction[5 * c + 1]; }
+          }
+        }
+        STAMPW(100);
+#pragma unroll
+        for (int t = 0; t < CT; t++) {
+          const int w = base + l + t * W;
+          if (w < nitem) {
+            const int sh = td[t] & 31;
+            contact_item(ta[t], td[t], tc[t], tdim[t], tr1[t], tr2[t], (REAL)((tm1[t] >> sh) & 1u), (REAL)((tm2[t] >> sh) & 1u), true, tf[t][0], tf[t][1]);
+          }
+        }
+        STAMP(101);
+      }
+    } else {
+      for (int w = l; w < nitem; w += W) {
+        int a, d;
+        split_index(w, nv, M.inv_nv, a, d);
+        const int c = act_list[a];
+        const int dim = M.con_dim[c];
+        const int* cb = M.con_body + 4 * c;
+        const int root1 = cb[2], root2 = cb[3];
+        const REAL on1 = (REAL)((M.con_dmask[2 * c] >> d) & 1ull), on2 = (REAL)((M.con_dmask[2 * c + 1] >> d) & 1ull);
+        STAMPW(100);
+        contact_item(a, d, c, dim, root1, root2, on1, on2, false, (REAL)0, (REAL)0);
+        STAMP(101);
       }
     }
 #if MJH_CS_PF == 2
@@ -3986,6 +4040,7 @@ struct Env {
     wave_sync();
     STAMP(25);
     // ---- efc_aref / efc_D of every row (:683-693): lane idx <-> Data row ----
+    // (reading both trips' tables ahead of the first trip's leaf stores, in the whole-pass forms, was measured: no change -- profiles/r09/notes.md)
     C.Dl = 0; C.arl = 0;
     for (int r = l; r < nefc; r += W) {
       REAL solref[2], solimp[5];
@@ -4015,11 +4070,13 @@ struct Env {
           jv = dot_seq(Jc + crow * nv, 1, S.qvel(), 1, nv);
         }  // (an inactive contact's row is all zeros: its product with the finite qvel is 0)
       }
+      STAMPW(102);
       REAL k, b, imp;
       kbi(solref, solimp, pos_norm, k, b, imp);
       REAL rr = invweight * (1 - imp) / imp;
       rr = rr > (REAL)MINVAL_CACHED ? rr : (REAL)MINVAL_CACHED;
       const REAL aref_r = -b * jv - k * imp * pos, D_r = 1 / rr;
+      STAMP(103);
       if (out.efc_aref) MJH_NT_STORE(aref_r, &out.efc_aref[e * nefc + r]);  // (fused kernels: the solve takes both from the arena / registers)
       if (out.efc_D) MJH_NT_STORE(D_r, &out.efc_D[e * nefc + r]);
       if (r < nl) { C.Dl = D_r; C.arl = aref_r; }
@@ -4071,7 +4128,7 @@ struct Env {
 #if MJH_CS_PF == 1
     sol2_prefetch<NMAX>(pre);
 #endif
-    make_constraint_cs<NMAX>(pre, con);
+    make_constraint_cs<NMAX, HANDOFF>(pre, con);  // (BATCH: the whole-pass forms, as for com_pos / crb_factor / velocity)
 #if MJH_CS_PF == 3
     if (HANDOFF && ho_on_) {  // what the solver reads back of the first half's leaves (factor rows, qfrc_smooth, qpos, act_dot; qM later): its stores landed while the constraint stage ran
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -4480,6 +4537,7 @@ struct Env {
       const REAL* Jc = S.efc_Jc();
       // o1 = M a, o2 = M b for vectors staged in LDS (lane d: element d).  Newton models: row d of qM is in registers; otherwise qM is
       // read from L2 -- it is symmetric, so row d is read as column d, coalesced -- nine rows in flight per trip.  Terms in column order.
+      // (the whole-pass forms with the lane's column requested ahead of the qacc_smooth substitution and both products from registers: 28 VGPRs more and 3 us slower, profiles/r09/notes.md)
       auto mul_M2 = [&](const REAL* a, const REAL* b, REAL& o1, REAL& o2, bool two) {
         REAL s1 = 0, s2 = 0;
         if (MROW) {
@@ -4576,7 +4634,9 @@ struct Env {
       wave_sync();
       REAL Ma_s, Ma_w, jal_s, jal_w, jad_s[RPL], jad_w[RPL];
       mul_M2(vs, vs2, Ma_s, Ma_w, warm_on);
+      STAMP(104);
       mul_J2(vs, vs2, jad_s, jad_w, warm_on);
+      STAMP(105);
       {
         const REAL a = lim ? vs[ldof] : (REAL)0, b = lim ? vs2[ldof] : (REAL)0;
         jal_s = Jl * a - arl; jal_w = Jl * b - arl;
@@ -4829,6 +4889,7 @@ struct Env {
         const bool need_grad = ONE ? false : !(it + 1 >= M.iterations);
         {  // search direction of this iteration: -H^-1 grad (Newton), -M^-1 grad at the start, Polak-Ribiere afterwards (CG, :519-523)
           const REAL Mg = precondition(grad);
+          STAMP(106);
           if (first_dir || newton) {
             search = -Mg;
           } else {
@@ -4847,6 +4908,7 @@ struct Env {
           wave_sync();
           REAL mv, unused, jvd[RPL], unused_d[RPL];
           mul_M2(vs, vs, mv, unused, false);
+          STAMP(107);
           mul_J2(vs, vs, jvd, unused_d, false);
           const REAL jvl = lim ? Jl * vs[ldof] : (REAL)0;
           wave_sync();

@@ -46,8 +46,10 @@ names.update({70: "sol2: J rows gather (+ rest of the loads)", 71: "sol2: qacc_s
 names.update({80: "sol2 loads: qfrc_smooth, factor rows (T.t), qM rows", 81: "sol2 loads: state, limit rows", 82: "sol2 loads: contact_dist + compaction", 83: "sol2 loads: D / aref of the dense rows"})
 names.update({99: "convex pair: wave start -> convex_convex", 90: "convex_convex: frames into LDS", 91: "SAT axes", 92: "best axis, support faces", 93: "polygons, side planes", 94: "edge clipping, reference points", 95: "manifold points", 96: "contacts out"})
 names.update({63: "newton: H build", 64: "newton: factor H", 65: "newton: solve", 66: "J^T force", 67: "update_constraint", 68: "context init (mulJ, mulM) / loop head"})
+names.update({100: "sub [25]: table entries requested + waited", 101: "sub [25]: row arithmetic + arena stores", 102: "sub [26]: tables waited (+ J qvel)", 103: "sub [26]: kbi, aref, D",
+              104: "sub [72]: mul_M2", 105: "sub [72]: mul_J2", 106: "sub [76]: preconditioner (tri_solve2)", 107: "sub [76]: mul_M2"})  # (sub-stamps: their cycles are NOT in the section they sit in)
 # every slot holds the cycles ACCUMULATED in the section that ends at that stamp (loops add up), summed over RK stages
-for lo, hi in [(0, 9), (10, 18), (19, 29), (30, 49), (50, 89), (90, 99)]:
+for lo, hi in [(0, 9), (10, 18), (19, 29), (30, 49), (50, 89), (90, 99), (100, 127)]:
     tot = 0
     for k in range(lo, hi + 1):
         v = st[:, k].mean()
