@@ -25,6 +25,7 @@
  *   mjh_pgs            <- MuJoCo's mj_solPGS for rows of dimension one, on the dual problem of a finished pass (the reference's solvers are CG and Newton alone)
  *   mjh_noslip         <- MuJoCo's mj_solNoSlip (noslip_iterations): Gauss-Seidel on the friction dimensions with the unregularised matrix, after the main solver (the reference has no counterpart)
  *   mjh_solve          <- solver.solve(m, d, fixed_iterations) on a caller's Data: the CG / Newton primal solver with its exact line search (_src/solver.py:244-553)
+ *   mjh_smooth         <- smooth.com_pos, crb, tendon_armature, factor_m, com_vel and rne on a caller's Data (_src/smooth.py:210-332, 385-467, 500-521)
  *   mjh_jacobian       <- MuJoCo's mj_jacBody .. mj_jacGeom (as products), mj_jacDot, mj_jacSubtreeCom, mj_angmomMat (the reference has support.jac alone)
  *   mjh_integrate      <- derivative.deriv_smooth_vel, forward._implicit (implicitfast), forward._euler and their _advance, on a finished pass (_src/derivative.py:22-68, forward.py:255-328, 404-416)
  *
@@ -52,7 +53,7 @@
 extern "C" {
 #endif
 
-#define MJH_ABI_VERSION 26
+#define MJH_ABI_VERSION 27
 
 /* ---- dtype / flags ------------------------------------------------------------------- */
 #define MJH_F64 0
@@ -129,6 +130,12 @@ extern "C" {
 #define MJH_KERNEL_PGS 54        /* mjh_pgs: projected Gauss-Seidel sweeps on the dual problem (one wavefront per environment) */
 #define MJH_KERNEL_NOSLIP 55     /* mjh_noslip: no-slip sweeps on the friction dimensions, pyramidal pairs and elliptic QCQPs (one wavefront per environment) */
 #define MJH_KERNEL_SOLVE 56      /* mjh_solve: the CG / Newton primal solver with its exact line search on a finished pass (one wavefront per environment) */
+#define MJH_KERNEL_SMOOTH_COM_POS 57          /* mjh_smooth, MJH_SMOOTH_COM_POS: subtree_com, cinert, cdof (the ids are 57 + op)       */
+#define MJH_KERNEL_SMOOTH_CRB 58              /* ... MJH_SMOOTH_CRB: crb and the dense qM                                              */
+#define MJH_KERNEL_SMOOTH_TENDON_ARMATURE 59  /* ... MJH_SMOOTH_TENDON_ARMATURE: qM + ten_J^T diag(armature) ten_J                     */
+#define MJH_KERNEL_SMOOTH_FACTOR_M 60         /* ... MJH_SMOOTH_FACTOR_M: qLD, the Cholesky factor of qM                               */
+#define MJH_KERNEL_SMOOTH_COM_VEL 61          /* ... MJH_SMOOTH_COM_VEL: cvel, cdof_dot                                                */
+#define MJH_KERNEL_SMOOTH_RNE 62              /* ... MJH_SMOOTH_RNE: qfrc_bias                                                         */
 
 /* pair-function ids of the static collision table (collision_driver.py:106-125) */
 #define MJH_FN_PLANE_SPHERE 0
@@ -740,6 +747,69 @@ int mjh_integrate(const mjhModel* m, const mjhIntegrateArgs* args, void* hip_str
  * fit a workgroup's LDS (mjh_integrate refuses such a model), -22 for a bad argument. */
 int mjh_integrate_plan(int nv, int nu, int ntendon, int real_bytes, int* lanes_envs_chunk_lds);
 
+/* mjh_smooth operations (mjhSmoothArgs.op); MJH_KERNEL_SMOOTH_COM_POS + op is the kernel id the timing aid reports */
+#define MJH_SMOOTH_COM_POS 0
+#define MJH_SMOOTH_CRB 1
+#define MJH_SMOOTH_TENDON_ARMATURE 2
+#define MJH_SMOOTH_FACTOR_M 3
+#define MJH_SMOOTH_COM_VEL 4
+#define MJH_SMOOTH_RNE 5
+
+/* one mjh_smooth call (definitions and the order of every sum: csrc/mjh_smooth.h; the functions are the reference's smooth.com_pos, crb, tendon_armature, factor_m,
+ * com_vel and rne).  Every pointer is device memory, reals of the model's dtype, batch-major over B environments; the leaves are the caller's, read as they are.
+ * Read / written per op (everything else may be NULL):
+ *   COM_POS          xipos [B, nbody, 3], ximat, xmat [B, nbody, 9], xanchor, xaxis [B, njnt, 3], body_mass [nbody], body_inertia [nbody, 3]
+ *                    -> subtree_com_out [B, nbody, 3], cinert_out [B, nbody, 10], cdof_out [B, nv, 6]
+ *   CRB              cinert [B, nbody, 10], cdof [B, nv, 6], dof_armature [nv] -> crb_out [B, nbody, 10] (row 0 zero), qM_out [B, nv, nv] (dense, symmetric)
+ *   TENDON_ARMATURE  qM [B, nv, nv], ten_J [B, ntendon, nv], tendon_armature [ntendon] -> qM_out
+ *   FACTOR_M         qM (its lower triangle) -> qLD_out [B, nv, nv] (the lower triangle L, zeros above the diagonal)
+ *   COM_VEL          cdof, qvel [B, nv] -> cvel_out [B, nbody, 6], cdof_dot_out [B, nv, 6]
+ *   RNE              cdof, cdof_dot, cvel [B, nbody, 6], cinert, qvel, qacc [B, nv] (flg_acc only) -> qfrc_bias_out [B, nv]
+ * gravity_x .. z and disableflags (DisableBit.GRAVITY) are the caller's options, read by RNE.  No output may alias an input. */
+typedef struct mjhSmoothArgs {
+  int32_t op, flg_acc, disableflags, reserved;
+  int64_t B;
+  double gravity_x, gravity_y, gravity_z;
+  const void* xipos;
+  const void* ximat;
+  const void* xmat;
+  const void* xanchor;
+  const void* xaxis;
+  const void* cinert;
+  const void* cdof;
+  const void* cdof_dot;
+  const void* cvel;
+  const void* qvel;
+  const void* qacc;
+  const void* qM;
+  const void* ten_J;
+  const void* body_mass;
+  const void* body_inertia;
+  const void* dof_armature;
+  const void* tendon_armature;
+  void* subtree_com_out;
+  void* cinert_out;
+  void* cdof_out;
+  void* crb_out;
+  void* qM_out;
+  void* qLD_out;
+  void* cvel_out;
+  void* cdof_dot_out;
+  void* qfrc_bias_out;
+} mjhSmoothArgs;
+
+/* one smooth-dynamics stage on a caller's Data (see mjhSmoothArgs).  One launch of the op's kernel (timing id MJH_KERNEL_SMOOTH_COM_POS + op), several environments per
+ * workgroup, cut at the launch cap like mjh_postconstraint; runs on hip_stream without host synchronisation.  Returns 0 or a negative code (-12 when one environment
+ * does not fit the LDS of a CU: mjh_last_error names the sizes; -22 for an unknown op, a null pointer or B < 0, before anything is launched).  B == 0 is a no-op, and
+ * so is an op whose outputs are all empty for this model (nv == 0 for TENDON_ARMATURE .. RNE; ntendon == 0 for TENDON_ARMATURE). */
+int mjh_smooth(const mjhModel* m, const mjhSmoothArgs* args, void* hip_stream);
+
+/* the plan mjh_smooth uses for `op` on a model of nbody bodies, nv dofs and ntendon tendons in reals of real_bytes (4 / 8) bytes, a host computation (no device is
+ * touched): out = {lanes per environment (16 / 32 / 64: from nbody, FACTOR_M from nv), environments per workgroup, reals of LDS per environment}.  Per environment the
+ * LDS holds 10 nbody (COM_POS), 20 nbody + 12 nv (CRB), ntendon nv (TENDON_ARMATURE), nv (nv + 1) / 2 + nv (FACTOR_M), 13 nv (COM_VEL), 24 nbody + 6 nv (RNE) reals,
+ * rounded up to a multiple of 4.  Returns 0, -12 when one environment does not fit the LDS of a CU (out is filled all the same), -22 for a bad argument. */
+int mjh_smooth_plan(int op, int nbody, int nv, int ntendon, int real_bytes, int* lanes_envs_lds);
+
 /* mjh_constraint_space operations (mjhConstraintSpaceArgs.op); MJH_KERNEL_EFC_MUL_J + op is the kernel id the timing aid reports */
 #define MJH_EFC_MUL_J 0
 #define MJH_EFC_MUL_JT 1
@@ -1038,7 +1108,7 @@ int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsi
 int mjh_model_lds_bytes(const mjhModel* m, int arena);
 
 /* measurement aid used by bench.py for the per-kernel roofline: while enabled, every kernel launch of mjh_step / mjh_forward is
- * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_ifd_perturb, mjh_ifd_difference, mjh_postconstraint, mjh_contact_sensors, mjh_energy, mjh_integrate, mjh_jacobian, mjh_geom_distance, mjh_qpos_arith, mjh_ik_site_step, mjh_constraint_space, mjh_pgs, mjh_noslip and mjh_solve too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
+ * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_ifd_perturb, mjh_ifd_difference, mjh_postconstraint, mjh_contact_sensors, mjh_energy, mjh_integrate, mjh_jacobian, mjh_geom_distance, mjh_qpos_arith, mjh_ik_site_step, mjh_constraint_space, mjh_pgs, mjh_noslip, mjh_solve and mjh_smooth too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
  * the elapsed milliseconds and the kernel id (MJH_KERNEL_*).  Returns the number of launches (<= max) or a negative code. */
 int mjh_debug_phase_timing(int enable);
 int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
@@ -1076,7 +1146,10 @@ void mjh_debug_set_stamps(void* dev_ptr);
  * qacc and the three scalars out -- (nefc + 2 nv + 2) reals + 4 bytes; -2 for a model without dofs or rows.  MJH_KERNEL_SOLVE (an mjh_solve call with the warm start
  * on): per environment, efc_J, qM and qLD once (qLD: counted for both solvers, Newton does not read it), efc_D and efc_frictionloss once, efc_aref twice (once per start
  * candidate; a third time when the smooth start wins), qfrc_smooth, qacc_smooth and qacc_warmstart in -- (nefc nv + 2 nv^2 + 4 nefc + 3 nv) reals --, qacc,
- * qacc_warmstart, qfrc_constraint, efc_force and the three scalars out -- (nefc + 3 nv + 3) reals + 4 bytes; -2 for a model without dofs or rows.  Returns 0, or -2 when this model's step does not launch that kernel. */
+ * qacc_warmstart, qfrc_constraint, efc_force and the three scalars out -- (nefc + 3 nv + 3) reals + 4 bytes; -2 for a model without dofs or rows.  MJH_KERNEL_SMOOTH_COM_POS + op (an mjh_smooth call), per environment, every leaf the op
+ * reads once, from the leaf extents, and what it writes, in reals: COM_POS 21 nbody + 6 njnt in, 13 nbody + 6 nv out; CRB 10 nbody + 6 nv in, 10 nbody + nv^2 out;
+ * TENDON_ARMATURE nv^2 + ntendon nv in, nv^2 out (-2 without tendons); FACTOR_M nv (nv + 1) / 2 in, nv^2 out; COM_VEL 7 nv in, 6 nbody + 6 nv out; RNE (with flg_acc)
+ * 14 nv + 16 nbody in, nv out; -2 for a model without dofs, COM_POS and CRB apart.  Returns 0, or -2 when this model's step does not launch that kernel. */
 int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes);
 
 /* last error message of the calling thread ("" if none) */

@@ -24,6 +24,7 @@
 #include "mjh_pgs.h"
 #include "mjh_noslip.h"
 #include "mjh_solve.h"
+#include "mjh_smooth.h"
 #include "mjh_instances.h"
 
 #define MJH_CAT_(a, b) a##b
@@ -101,4 +102,12 @@ template __global__ void mjh_noslip_kernel<MJH_INST_REAL>(NoslipArgs<MJH_INST_RE
 #endif
 #if MJH_INST_GROUP == 36
 template __global__ void mjh_solve_kernel<MJH_INST_REAL>(SolveArgs<MJH_INST_REAL>);
+#endif
+#if MJH_INST_GROUP == 37
+template __global__ void mjh_smooth_kernel<MJH_INST_REAL, MJH_SMOOTH_COM_POS>(SmoothArgs<MJH_INST_REAL>);
+template __global__ void mjh_smooth_kernel<MJH_INST_REAL, MJH_SMOOTH_CRB>(SmoothArgs<MJH_INST_REAL>);
+template __global__ void mjh_smooth_kernel<MJH_INST_REAL, MJH_SMOOTH_TENDON_ARMATURE>(SmoothArgs<MJH_INST_REAL>);
+template __global__ void mjh_smooth_kernel<MJH_INST_REAL, MJH_SMOOTH_FACTOR_M>(SmoothArgs<MJH_INST_REAL>);
+template __global__ void mjh_smooth_kernel<MJH_INST_REAL, MJH_SMOOTH_COM_VEL>(SmoothArgs<MJH_INST_REAL>);
+template __global__ void mjh_smooth_kernel<MJH_INST_REAL, MJH_SMOOTH_RNE>(SmoothArgs<MJH_INST_REAL>);
 #endif

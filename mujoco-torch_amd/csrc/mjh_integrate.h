@@ -52,6 +52,34 @@ struct IntegrateArgs {
 
 __device__ __forceinline__ int itg_tri(int r, int c) { return (r * (r + 1)) / 2 + c; }  // packed lower rows, c <= r
 
+// math.small_cholesky (math.py:87-129) in place on the packed lower triangle A of an environment in LDS, by the environment's L lanes (lane l owns rows l, l + L, ..);
+// v: nv reals of LDS for the scaled column.  Right-looking: column j is scaled by its pivot (clamped at 1e-12 up to INLINE_CHOL_MAX dofs, + 1e-10 above), then every
+// later entry (r, c) loses L[r][j] L[c][j], i.e. the products leave an entry in j order.  Shared by mjh_integrate_kernel (qM - h qDeriv) and mjh_smooth.h's factor_m (qM).
+template <typename REAL>
+__device__ __forceinline__ void itg_cholesky(REAL* A, REAL* v, int nv, int l, int L) {
+  const bool big = nv > INLINE_CHOL_MAX;
+  for (int j = 0; j < nv; j++) {
+    REAL s = A[itg_tri(j, j)];
+    if (big) s = s + (REAL)1e-10;  // (A + 1e-10 I, applied at the pivot)
+    else s = s > (REAL)1e-12 ? s : (REAL)1e-12;
+    const REAL d = r_sqrt<REAL>(s);
+    wave_sync();  // every lane has read the pivot before its owner overwrites it
+    for (int r = l; r < nv; r += L) {  // (the scaled column also goes to v, a buffer of its own: the sweep below then reads no entry of A another lane writes)
+      if (r > j) { const REAL q = A[itg_tri(r, j)] / d; A[itg_tri(r, j)] = q; v[r] = q; }
+      else if (r == j) A[itg_tri(j, j)] = d;
+    }
+    wave_sync();
+    for (int r = l; r < nv; r += L) {
+      if (r <= j) continue;
+      const REAL* __restrict__ col = v;
+      REAL* __restrict__ Ar = A + itg_tri(r, 0);
+      const REAL lr = col[r];
+      for (int c = j + 1; c <= r; c++) Ar[c] = Ar[c] - lr * col[c];
+    }
+    wave_sync();
+  }
+}
+
 template <typename REAL>
 __global__ __launch_bounds__(MJH_INTEGRATE_WG) void mjh_integrate_kernel(IntegrateArgs<REAL> a) {
   extern __shared__ __attribute__((aligned(16))) double itg_lds_raw[];
@@ -150,28 +178,8 @@ __global__ __launch_bounds__(MJH_INTEGRATE_WG) void mjh_integrate_kernel(Integra
     for (int i = l; i < nv; i += L) x[i] = a.qfrc_smooth[e * nv + i] + a.qfrc_constraint[e * nv + i];
     wave_sync();
 
-    // Cholesky in place, right-looking: column j is scaled by its pivot, then every later entry (r, c) loses L[r][j] L[c][j]; lane l owns rows l, l + L, ..
     const bool big = nv > INLINE_CHOL_MAX;
-    for (int j = 0; j < nv; j++) {
-      REAL s = A[itg_tri(j, j)];
-      if (big) s = s + (REAL)1e-10;  // (A + 1e-10 I, applied at the pivot)
-      else s = s > (REAL)1e-12 ? s : (REAL)1e-12;
-      const REAL d = r_sqrt<REAL>(s);
-      wave_sync();  // every lane has read the pivot before its owner overwrites it
-      for (int r = l; r < nv; r += L) {  // (the scaled column also goes to v, a buffer of its own until the advance: the sweep below then reads no entry of A another lane writes)
-        if (r > j) { const REAL q = A[itg_tri(r, j)] / d; A[itg_tri(r, j)] = q; v[r] = q; }
-        else if (r == j) A[itg_tri(j, j)] = d;
-      }
-      wave_sync();
-      for (int r = l; r < nv; r += L) {
-        if (r <= j) continue;
-        const REAL* __restrict__ col = v;
-        REAL* __restrict__ Ar = A + itg_tri(r, 0);
-        const REAL lr = col[r];
-        for (int c = j + 1; c <= r; c++) Ar[c] = Ar[c] - lr * col[c];
-      }
-      wave_sync();
-    }
+    itg_cholesky<REAL>(A, v, nv, l, L);
     // L y = b, column by column: element r loses L[r][k] y[k] in k order, as the reference's row loop does
     // (every lane reads x[k] and its owner overwrites it in the same trip with no barrier between: an environment's lanes share a wavefront, which issues the read
     // for all of them before the write, and LDS operations complete in issue order.  The same holds for the column-wise backward substitution below.)

@@ -28,6 +28,7 @@
 #include "mjh_energy.h"
 #include "mjh_jacobian.h"
 #include "mjh_integrate.h"
+#include "mjh_smooth.h"
 #include "mjh_quadric.h"
 #include "mjh_geomdist.h"
 #include "mjh_qpos.h"
@@ -80,6 +81,16 @@ extern template __global__ void mjh_jac_product_kernel<double>(JacArgs<double>);
 extern template __global__ void mjh_jac_product_kernel<float>(JacArgs<float>);
 extern template __global__ void mjh_integrate_kernel<double>(IntegrateArgs<double>);  // (build group 27)
 extern template __global__ void mjh_integrate_kernel<float>(IntegrateArgs<float>);
+#define SM_(R)                                                                                  \
+  extern template __global__ void mjh_smooth_kernel<R, MJH_SMOOTH_COM_POS>(SmoothArgs<R>);         \
+  extern template __global__ void mjh_smooth_kernel<R, MJH_SMOOTH_CRB>(SmoothArgs<R>);             \
+  extern template __global__ void mjh_smooth_kernel<R, MJH_SMOOTH_TENDON_ARMATURE>(SmoothArgs<R>); \
+  extern template __global__ void mjh_smooth_kernel<R, MJH_SMOOTH_FACTOR_M>(SmoothArgs<R>);        \
+  extern template __global__ void mjh_smooth_kernel<R, MJH_SMOOTH_COM_VEL>(SmoothArgs<R>);         \
+  extern template __global__ void mjh_smooth_kernel<R, MJH_SMOOTH_RNE>(SmoothArgs<R>);
+SM_(double)  // (build group 37)
+SM_(float)
+#undef SM_
 extern template __global__ void mjh_quadric_kernel<double>(KArgs<double>);  // (build group 29)
 extern template __global__ void mjh_quadric_kernel<float>(KArgs<float>);
 extern template __global__ void mjh_ifd_perturb_kernel<double>(FdPerturbArgs<double>);  // (build group 30)
@@ -2111,6 +2122,89 @@ int run_integrate(const mjhModel* m, const DevModel<REAL>& M, const mjhIntegrate
   return launch_envs(mjh_integrate_kernel<REAL>, a, x->B, (hipStream_t)stream, MJH_KERNEL_INTEGRATE);
 }
 
+// mjh_smooth's launch plan, from the model alone: lanes per environment (from nbody; FACTOR_M: from nv), environments per workgroup, reals of LDS per environment
+// (mjh_smooth.h names the arrays).  A workgroup is planned for kLdsWg bytes; an environment that needs more runs alone.  Returns 0, or -12 when one environment does
+// not fit kLdsCu (out is filled all the same).
+static int smooth_plan(int op, int nb, int nv, int nt, int real_bytes, int* out) {
+  const int n = op == MJH_SMOOTH_FACTOR_M ? nv : nb;
+  const int lanes = n <= 16 ? 16 : (n <= 32 ? 32 : 64);
+  const int64_t reals[6] = {10 * (int64_t)nb, 20 * (int64_t)nb + 12 * (int64_t)nv, (int64_t)nt * nv, ((((int64_t)nv * (nv + 1)) / 2 + 3) & ~(int64_t)3) + nv,
+                            13 * (int64_t)nv, 24 * (int64_t)nb + 6 * (int64_t)nv};
+  const int64_t lds_env = std::max<int64_t>(4, (reals[op] + 3) & ~(int64_t)3), env_bytes = lds_env * real_bytes;
+  out[0] = lanes;
+  out[1] = (int)std::max<int64_t>(1, std::min<int64_t>(MJH_SMOOTH_WG / lanes, kLdsWg / env_bytes));
+  out[2] = (int)std::min<int64_t>(lds_env, INT32_MAX);
+  return env_bytes > kLdsCu ? -12 : 0;
+}
+
+template <typename REAL, int OP>
+int launch_smooth(SmoothArgs<REAL>& a, int64_t B, hipStream_t s) {
+  const size_t lds = (size_t)a.envs * a.lds_env * sizeof(REAL);
+  if (lds > (size_t)kLdsWg) HIP_TRY(allow_lds(&mjh_smooth_kernel<REAL, OP>, (int)lds));
+  return launch_envs(mjh_smooth_kernel<REAL, OP>, a, B, s, MJH_KERNEL_SMOOTH_COM_POS + OP);
+}
+
+// the smooth-dynamics stages on a caller's Data (mjh_smooth.h), one launch
+template <typename REAL>
+int run_smooth(const mjhModel* m, const DevModel<REAL>& M, const mjhSmoothArgs* x, void* stream) {
+  const int op = x->op;
+  if (op < MJH_SMOOTH_COM_POS || op > MJH_SMOOTH_RNE) return fail(-22, "smooth: unknown op");
+  if (x->B < 0) return fail(-22, "smooth: B must be >= 0");
+  const int nb = M.nbody, nv = M.nv, nj = M.njnt, nt = M.ntendon;
+  if (x->B == 0 || (op != MJH_SMOOTH_COM_POS && op != MJH_SMOOTH_CRB && nv == 0) || (op == MJH_SMOOTH_TENDON_ARMATURE && nt == 0)) return 0;  // (crb is per body)
+  switch (op) {
+    case MJH_SMOOTH_COM_POS:
+      if (!x->xipos || !x->ximat || !x->xmat || !x->body_mass || !x->body_inertia || !x->subtree_com_out || !x->cinert_out || (nj > 0 && (!x->xanchor || !x->xaxis)) ||
+          (nv > 0 && !x->cdof_out))
+        return fail(-22, "smooth: null pointer (com_pos)");
+      break;
+    case MJH_SMOOTH_CRB:
+      if (!x->cinert || !x->crb_out || (nv > 0 && (!x->cdof || !x->dof_armature || !x->qM_out))) return fail(-22, "smooth: null pointer (crb)");
+      break;
+    case MJH_SMOOTH_TENDON_ARMATURE:
+      if (!x->qM || !x->ten_J || !x->tendon_armature || !x->qM_out) return fail(-22, "smooth: null pointer (tendon_armature)");
+      break;
+    case MJH_SMOOTH_FACTOR_M:
+      if (!x->qM || !x->qLD_out) return fail(-22, "smooth: null pointer (factor_m)");
+      break;
+    case MJH_SMOOTH_COM_VEL:
+      if (!x->cdof || !x->qvel || !x->cvel_out || !x->cdof_dot_out) return fail(-22, "smooth: null pointer (com_vel)");
+      break;
+    default:
+      if (!x->cdof || !x->cdof_dot || !x->cvel || !x->cinert || !x->qvel || (x->flg_acc && !x->qacc) || !x->qfrc_bias_out) return fail(-22, "smooth: null pointer (rne)");
+  }
+  int plan[3];
+  if (smooth_plan(op, nb, nv, nt, (int)sizeof(REAL), plan)) {
+    char msg[200];
+    snprintf(msg, sizeof(msg), "smooth: op %d with nbody = %d, nv = %d, ntendon = %d needs %lld bytes of LDS per environment; a CU has %d", op, nb, nv, nt,
+             (long long)plan[2] * (long long)sizeof(REAL), (int)kLdsCu);
+    return fail(-12, msg);
+  }
+  SmoothArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+  P_(xipos) P_(ximat) P_(xmat) P_(xanchor) P_(xaxis) P_(cinert) P_(cdof) P_(cdof_dot) P_(cvel) P_(qvel) P_(qacc) P_(qM) P_(ten_J)
+  P_(body_mass) P_(body_inertia) P_(dof_armature) P_(tendon_armature)
+  a.subtree_com = reinterpret_cast<REAL*>(x->subtree_com_out); a.cinert_out = reinterpret_cast<REAL*>(x->cinert_out); a.cdof_out = reinterpret_cast<REAL*>(x->cdof_out);
+  a.crb = reinterpret_cast<REAL*>(x->crb_out); a.qM_out = reinterpret_cast<REAL*>(x->qM_out); a.qLD = reinterpret_cast<REAL*>(x->qLD_out);
+  a.cvel_out = reinterpret_cast<REAL*>(x->cvel_out); a.cdof_dot_out = reinterpret_cast<REAL*>(x->cdof_dot_out); a.qfrc_bias = reinterpret_cast<REAL*>(x->qfrc_bias_out);
+  a.body_rootid = M.body_rootid; a.body_jntadr = M.body_jntadr; a.body_jntnum = M.body_jntnum; a.body_dofadr = M.body_dofadr; a.body_dofnum = M.body_dofnum;
+  a.body_depth = M.body_depth; a.body_chain = M.body_chain; a.body_subtree_end = M.body_subtree_end; a.jnt_type = M.jnt_type; a.jnt_dofadr = M.jnt_dofadr;
+  a.jnt_bodyid = M.jnt_bodyid; a.dof_bodyid = M.dof_bodyid; a.body_dofmask = M.body_dofmask;
+  const bool nograv = x->disableflags & DSBL_GRAVITY;
+  a.cacc0[0] = nograv ? (REAL)0 : -(REAL)x->gravity_x; a.cacc0[1] = nograv ? (REAL)0 : -(REAL)x->gravity_y; a.cacc0[2] = nograv ? (REAL)0 : -(REAL)x->gravity_z;
+  a.nbody = nb; a.njnt = nj; a.nv = nv; a.ntendon = nt; a.max_depth = M.max_depth; a.mask_words = M.mask_words; a.flg_acc = x->flg_acc != 0;
+  a.lanes = plan[0]; a.envs = plan[1]; a.lds_env = plan[2];
+  hipStream_t s = (hipStream_t)stream;
+  switch (op) {
+    case MJH_SMOOTH_COM_POS: return launch_smooth<REAL, MJH_SMOOTH_COM_POS>(a, x->B, s);
+    case MJH_SMOOTH_CRB: return launch_smooth<REAL, MJH_SMOOTH_CRB>(a, x->B, s);
+    case MJH_SMOOTH_TENDON_ARMATURE: return launch_smooth<REAL, MJH_SMOOTH_TENDON_ARMATURE>(a, x->B, s);
+    case MJH_SMOOTH_FACTOR_M: return launch_smooth<REAL, MJH_SMOOTH_FACTOR_M>(a, x->B, s);
+    case MJH_SMOOTH_COM_VEL: return launch_smooth<REAL, MJH_SMOOTH_COM_VEL>(a, x->B, s);
+    default: return launch_smooth<REAL, MJH_SMOOTH_RNE>(a, x->B, s);
+  }
+}
+
 #undef P_
 #undef O_
 
@@ -2438,6 +2532,18 @@ int mjh_integrate(const mjhModel* m, const mjhIntegrateArgs* args, void* stream)
   return m->dtype == MJH_F64 ? run_integrate<double>(m, m->m64, args, stream) : run_integrate<float>(m, m->m32, args, stream);
 }
 
+int mjh_smooth(const mjhModel* m, const mjhSmoothArgs* args, void* stream) {
+  if (!m || !args) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_smooth<double>(m, m->m64, args, stream) : run_smooth<float>(m, m->m32, args, stream);
+}
+
+int mjh_smooth_plan(int op, int nbody, int nv, int ntendon, int real_bytes, int* lanes_envs_lds) {
+  if (op < MJH_SMOOTH_COM_POS || op > MJH_SMOOTH_RNE || nbody < 1 || nv < 0 || ntendon < 0 || (real_bytes != 4 && real_bytes != 8) || !lanes_envs_lds)
+    return fail(-22, "smooth_plan: bad argument");
+  if (smooth_plan(op, nbody, nv, ntendon, real_bytes, lanes_envs_lds)) return fail(-12, "smooth_plan: one environment does not fit the LDS of a CU");
+  return 0;
+}
+
 int mjh_integrate_plan(int nv, int nu, int ntendon, int real_bytes, int* lanes_envs_chunk_lds) {
   if (nv < 0 || nu < 0 || ntendon < 0 || (real_bytes != 4 && real_bytes != 8) || !lanes_envs_chunk_lds) return fail(-22, "integrate_plan: bad argument");
   return integrate_plan(nv, nu, ntendon, real_bytes, lanes_envs_chunk_lds);
@@ -2696,6 +2802,17 @@ static int kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes, b
     const int64_t rd[4] = {6 * nv + 3 + 3, 12 * nv + 3 + 3 + 6 * nb, 6 * nv + 6 * nb, 6 * nv + 15 * nb}, wr[4] = {6 * nv, 6 * nv, 3 * nv, 3 * nv};
     read_write_bytes[0] = (rd[op] + (vec ? nv : 0)) * R;
     read_write_bytes[1] = (vec ? wr[op] / nv : wr[op]) * R;
+    return 0;
+  }
+  if (kernel >= MJH_KERNEL_SMOOTH_COM_POS && kernel <= MJH_KERNEL_SMOOTH_RNE) {  // mjh_smooth, per environment: see include/mjhip.h
+    const int64_t R = f64 ? 8 : 4, nb = f64 ? m->m64.nbody : m->m32.nbody, nv = f64 ? m->m64.nv : m->m32.nv, nj = f64 ? m->m64.njnt : m->m32.njnt,
+                  nt = f64 ? m->m64.ntendon : m->m32.ntendon;
+    const int op = kernel - MJH_KERNEL_SMOOTH_COM_POS;
+    if ((op != MJH_SMOOTH_COM_POS && op != MJH_SMOOTH_CRB && nv == 0) || (op == MJH_SMOOTH_TENDON_ARMATURE && nt == 0)) return -2;
+    const int64_t rd[6] = {21 * nb + 6 * nj, 10 * nb + 6 * nv, nv * nv + nt * nv, (nv * (nv + 1)) / 2, 7 * nv, 14 * nv + 16 * nb};
+    const int64_t wr[6] = {13 * nb + 6 * nv, 10 * nb + nv * nv, nv * nv, nv * nv, 6 * nb + 6 * nv, nv};
+    read_write_bytes[0] = rd[op] * R;
+    read_write_bytes[1] = wr[op] * R;
     return 0;
   }
   if (kernel == MJH_KERNEL_INTEGRATE) {  // an implicit step (mjh_integrate, QDERIV | IMPLICIT | STATE): the leaves it reads once (qM in full), the four state leaves out

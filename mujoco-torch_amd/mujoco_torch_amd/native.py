@@ -326,6 +326,16 @@ class SolveArgs(ctypes.Structure):
         "qfrc_constraint_out", "efc_force_out", "cost", "improvement", "grad_norm", "niter")]
 
 
+class SmoothArgs(ctypes.Structure):
+    """include/mjhip.h mjhSmoothArgs: one mjh_smooth call (device pointers).  Bound below beside the ``ARGS`` table, like ``SolveArgs`` (tests/test_smooth_host.py
+    compares it with the header, field by field, with tests/test_abi.py's own parser)."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("op", "flg_acc", "disableflags", "reserved")] + [("B", ctypes.c_int64)] + [
+        (n, ctypes.c_double) for n in ("gravity_x", "gravity_y", "gravity_z")] + [(n, ctypes.c_void_p) for n in (
+        "xipos", "ximat", "xmat", "xanchor", "xaxis", "cinert", "cdof", "cdof_dot", "cvel", "qvel", "qacc", "qM", "ten_J", "body_mass", "body_inertia", "dof_armature",
+        "tendon_armature", "subtree_com_out", "cinert_out", "cdof_out", "crb_out", "qM_out", "qLD_out", "cvel_out", "cdof_dot_out", "qfrc_bias_out")]
+
+
 # the entry points that take (handle, args struct, stream): symbol -> the struct (tests/test_abi.py compares every struct with the header)
 ARGS = {"mjh_support": SupportArgs, "mjh_postconstraint": PostconArgs, "mjh_contact_sensors": ContactSensorArgs, "mjh_energy": EnergyArgs,
         "mjh_integrate": IntegrateArgs, "mjh_jacobian": JacobianArgs}
@@ -400,6 +410,11 @@ def load_library(path: str | None = None):
         lib.mjh_solve.restype = ctypes.c_int
         lib.mjh_solve_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         lib.mjh_solve_plan.restype = ctypes.c_int
+    if hasattr(lib, "mjh_smooth"):  # (likewise a build from before the smooth-dynamics functions)
+        lib.mjh_smooth.argtypes = [ctypes.c_void_p, ctypes.POINTER(SmoothArgs), ctypes.c_void_p]
+        lib.mjh_smooth.restype = ctypes.c_int
+        lib.mjh_smooth_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        lib.mjh_smooth_plan.restype = ctypes.c_int
     if hasattr(lib, "mjh_integrate_plan"):
         lib.mjh_integrate_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         lib.mjh_integrate_plan.restype = ctypes.c_int
