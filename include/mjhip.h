@@ -26,6 +26,7 @@
  *   mjh_noslip         <- MuJoCo's mj_solNoSlip (noslip_iterations): Gauss-Seidel on the friction dimensions with the unregularised matrix, after the main solver (the reference has no counterpart)
  *   mjh_solve          <- solver.solve(m, d, fixed_iterations) on a caller's Data: the CG / Newton primal solver with its exact line search (_src/solver.py:244-553)
  *   mjh_smooth         <- smooth.com_pos, crb, tendon_armature, factor_m, com_vel and rne on a caller's Data (_src/smooth.py:210-332, 385-467, 500-521)
+ *   mjh_dynamics       <- smooth.tendon, transmission, passive.passive and forward's _velocity products, _actuation, _acceleration on a caller's Data (_src/smooth.py:470-497, 535-591, passive.py, forward.py:87-228)
  *   mjh_jacobian       <- MuJoCo's mj_jacBody .. mj_jacGeom (as products), mj_jacDot, mj_jacSubtreeCom, mj_angmomMat (the reference has support.jac alone)
  *   mjh_integrate      <- derivative.deriv_smooth_vel, forward._implicit (implicitfast), forward._euler and their _advance, on a finished pass (_src/derivative.py:22-68, forward.py:255-328, 404-416)
  *
@@ -53,7 +54,7 @@
 extern "C" {
 #endif
 
-#define MJH_ABI_VERSION 27
+#define MJH_ABI_VERSION 28
 
 /* ---- dtype / flags ------------------------------------------------------------------- */
 #define MJH_F64 0
@@ -136,6 +137,12 @@ extern "C" {
 #define MJH_KERNEL_SMOOTH_FACTOR_M 60         /* ... MJH_SMOOTH_FACTOR_M: qLD, the Cholesky factor of qM                               */
 #define MJH_KERNEL_SMOOTH_COM_VEL 61          /* ... MJH_SMOOTH_COM_VEL: cvel, cdof_dot                                                */
 #define MJH_KERNEL_SMOOTH_RNE 62              /* ... MJH_SMOOTH_RNE: qfrc_bias                                                         */
+#define MJH_KERNEL_DYNAMICS_TENDON 63        /* mjh_dynamics, MJH_DYNAMICS_TENDON: ten_length, ten_J (the ids are 63 + op)            */
+#define MJH_KERNEL_DYNAMICS_TRANSMISSION 64  /* ... MJH_DYNAMICS_TRANSMISSION: actuator_length, actuator_moment                       */
+#define MJH_KERNEL_DYNAMICS_VELOCITY 65      /* ... MJH_DYNAMICS_VELOCITY: actuator_velocity, ten_velocity                            */
+#define MJH_KERNEL_DYNAMICS_PASSIVE 66       /* ... MJH_DYNAMICS_PASSIVE: qfrc_passive, qfrc_gravcomp                                 */
+#define MJH_KERNEL_DYNAMICS_ACTUATION 67     /* ... MJH_DYNAMICS_ACTUATION: act_dot, actuator_force, qfrc_actuator                    */
+#define MJH_KERNEL_DYNAMICS_ACCELERATION 68  /* ... MJH_DYNAMICS_ACCELERATION: qfrc_smooth, qacc_smooth                               */
 
 /* pair-function ids of the static collision table (collision_driver.py:106-125) */
 #define MJH_FN_PLANE_SPHERE 0
@@ -810,6 +817,111 @@ int mjh_smooth(const mjhModel* m, const mjhSmoothArgs* args, void* hip_stream);
  * rounded up to a multiple of 4.  Returns 0, -12 when one environment does not fit the LDS of a CU (out is filled all the same), -22 for a bad argument. */
 int mjh_smooth_plan(int op, int nbody, int nv, int ntendon, int real_bytes, int* lanes_envs_lds);
 
+/* mjh_dynamics operations (mjhDynamicsArgs.op); MJH_KERNEL_DYNAMICS_TENDON + op is the kernel id the timing aid reports */
+#define MJH_DYNAMICS_TENDON 0
+#define MJH_DYNAMICS_TRANSMISSION 1
+#define MJH_DYNAMICS_VELOCITY 2
+#define MJH_DYNAMICS_PASSIVE 3
+#define MJH_DYNAMICS_ACTUATION 4
+#define MJH_DYNAMICS_ACCELERATION 5
+
+/* one mjh_dynamics call (definitions and the order of every sum: csrc/mjh_dynamics.h; the functions are the reference's smooth.tendon, smooth.transmission, the two
+ * products of forward._velocity, passive.passive, forward._actuation and forward._acceleration).  Every pointer is device memory, reals of the model's dtype; the leaves
+ * are batch-major over B environments and the caller's, read as they are; the model values are the caller's Model's.  Read / written per op (everything else may be NULL):
+ *   TENDON        qpos [B, nq] -> ten_length_out [B, ntendon], ten_J_out [B, ntendon, nv] (the joint terms and their coefficients are the compiled model's)
+ *   TRANSMISSION  qpos, ten_length, ten_J (tendon transmissions), gear [nu, 6] -> actuator_length_out [B, nu], actuator_moment_out [B, nu, nv]
+ *   VELOCITY      qvel [B, nv], actuator_moment [B, nu, nv], ten_J -> actuator_velocity_out [B, nu], ten_velocity_out [B, ntendon]
+ *   PASSIVE       qpos, qvel, jnt_stiffness [njnt], qpos_spring [nq], dof_damping [nv]; with tendons ten_length, ten_velocity, ten_J, tendon_stiffness, tendon_damping
+ *                 [ntendon], tendon_lengthspring [ntendon, 2]; with has_gravcomp or has_fluid xipos [B, nbody, 3], subtree_com, cdof [B, nv, 6], body_mass [nbody]; with
+ *                 has_gravcomp body_gravcomp [nbody], jnt_actgravcomp [njnt] (reals, 0 / 1), gravity_x .. z; with has_fluid ximat [B, nbody, 9], cvel [B, nbody, 6],
+ *                 body_inertia [nbody, 3], wind_x .. z, density, viscosity -> qfrc_passive_out [B, nv], with has_gravcomp qfrc_gravcomp_out [B, nv].
+ *                 has_gravcomp here: the term is computed (the model has it and GRAVITY is not disabled).  SPRING or DAMPER disabled: -22 (both outputs are zero;
+ *                 the caller makes them).
+ *   ACTUATION     ctrl [B, nu], act [B, na] (stateful actuators), actuator_length, actuator_velocity, actuator_moment, gainprm [nu, gain_stride >= 3; 9 for a muscle
+ *                 gain], biasprm [nu, bias_stride], dynprm [nu, dyn_stride >= 1; 3 for muscle dynamics], ctrlrange, forcerange, lengthrange [nu, 2], acc0 [nu],
+ *                 jnt_actfrcrange [njnt, 2]; with has_gravcomp (the model has it) qfrc_gravcomp [B, nv], jnt_actgravcomp
+ *                 -> act_dot_out [B, na], actuator_force_out [B, nu], qfrc_actuator_out [B, nv].  nu == 0 or ACTUATION disabled: -22 (the caller makes the zeros).
+ *   ACCELERATION  qfrc_applied [B, nv], xfrc_applied [B, nbody, 6], xipos, subtree_com, cdof, qfrc_passive, qfrc_bias, qfrc_actuator [B, nv], qLD [B, nv, nv] (its lower
+ *                 triangle) -> qfrc_smooth_out, qacc_smooth_out [B, nv]
+ * disableflags are the caller's (SPRING, DAMPER, CLAMPCTRL, ACTUATION are read).  No output may alias an input. */
+typedef struct mjhDynamicsArgs {
+  int32_t op, disableflags, has_gravcomp, has_fluid;
+  int32_t gain_stride, bias_stride, dyn_stride, reserved;
+  int64_t B;
+  double gravity_x, gravity_y, gravity_z;
+  double wind_x, wind_y, wind_z;
+  double density, viscosity;
+  const void* qpos;
+  const void* qvel;
+  const void* ctrl;
+  const void* act;
+  const void* ten_length;
+  const void* ten_velocity;
+  const void* ten_J;
+  const void* actuator_length;
+  const void* actuator_velocity;
+  const void* actuator_moment;
+  const void* xipos;
+  const void* ximat;
+  const void* subtree_com;
+  const void* cdof;
+  const void* cvel;
+  const void* qfrc_gravcomp;
+  const void* qfrc_applied;
+  const void* xfrc_applied;
+  const void* qfrc_passive;
+  const void* qfrc_bias;
+  const void* qfrc_actuator;
+  const void* qLD;
+  const void* jnt_stiffness;
+  const void* qpos_spring;
+  const void* dof_damping;
+  const void* tendon_stiffness;
+  const void* tendon_damping;
+  const void* tendon_lengthspring;
+  const void* body_mass;
+  const void* body_inertia;
+  const void* body_gravcomp;
+  const void* jnt_actgravcomp;
+  const void* jnt_actfrcrange;
+  const void* gainprm;
+  const void* biasprm;
+  const void* dynprm;
+  const void* ctrlrange;
+  const void* forcerange;
+  const void* gear;
+  const void* lengthrange;
+  const void* acc0;
+  void* ten_length_out;
+  void* ten_J_out;
+  void* actuator_length_out;
+  void* actuator_moment_out;
+  void* actuator_velocity_out;
+  void* ten_velocity_out;
+  void* qfrc_passive_out;
+  void* qfrc_gravcomp_out;
+  void* act_dot_out;
+  void* qfrc_actuator_out;
+  void* actuator_force_out;
+  void* qfrc_smooth_out;
+  void* qacc_smooth_out;
+} mjhDynamicsArgs;
+
+/* one stage of the smooth dynamics on a caller's Data (see mjhDynamicsArgs).  One launch of the op's kernel (timing id MJH_KERNEL_DYNAMICS_TENDON + op), several
+ * environments per workgroup, cut at the launch cap like mjh_smooth; runs on hip_stream without host synchronisation.  Returns 0 or a negative code (-12 when one
+ * environment does not fit the LDS of a CU: mjh_last_error names the sizes; -22 for an unknown op, a null pointer, a parameter row that is too short, B < 0 or a
+ * branch that launches nothing (see the struct), before anything is launched).  B == 0 is a no-op, and so is an op whose outputs are all empty for this model
+ * (ntendon == 0 for TENDON; nu == 0 for TRANSMISSION; nu == 0 and ntendon == 0, or nv == 0, for VELOCITY; nv == 0 for PASSIVE and ACCELERATION). */
+int mjh_dynamics(const mjhModel* m, const mjhDynamicsArgs* args, void* hip_stream);
+
+/* the plan mjh_dynamics uses for `op` on a model of nq positions, nv dofs, nu actuators, nbody bodies and ntendon tendons in reals of real_bytes (4 / 8) bytes, a host
+ * computation (no device is touched): out = {lanes per environment (16 / 32 / 64: from nv for TENDON, PASSIVE and ACCELERATION, from nu for TRANSMISSION, VELOCITY and
+ * ACTUATION), environments per workgroup, reals of LDS per environment}.  Per environment the LDS holds nq (TENDON), nq + ntendon + 3 nu (TRANSMISSION),
+ * nv + (nu + ntendon) (nv | 1) (VELOCITY: an odd row stride), nv + ntendon + 12 nbody (PASSIVE), nu (ACTUATION), nv (nv + 1) / 2 rounded up to a multiple of 4 + nv + 6 nbody (ACCELERATION)
+ * reals, rounded up to a multiple of 4, at least 4.  Returns 0, -12 when one environment does not fit the LDS of a CU (out is filled all the same), -22 for a bad
+ * argument. */
+int mjh_dynamics_plan(int op, int nq, int nv, int nu, int nbody, int ntendon, int real_bytes, int* lanes_envs_lds);
+
 /* mjh_constraint_space operations (mjhConstraintSpaceArgs.op); MJH_KERNEL_EFC_MUL_J + op is the kernel id the timing aid reports */
 #define MJH_EFC_MUL_J 0
 #define MJH_EFC_MUL_JT 1
@@ -1108,7 +1220,7 @@ int mjh_reset_where(const mjhModel* m, mjhData* d, const mjhData* d0, const unsi
 int mjh_model_lds_bytes(const mjhModel* m, int arena);
 
 /* measurement aid used by bench.py for the per-kernel roofline: while enabled, every kernel launch of mjh_step / mjh_forward is
- * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_ifd_perturb, mjh_ifd_difference, mjh_postconstraint, mjh_contact_sensors, mjh_energy, mjh_integrate, mjh_jacobian, mjh_geom_distance, mjh_qpos_arith, mjh_ik_site_step, mjh_constraint_space, mjh_pgs, mjh_noslip, mjh_solve and mjh_smooth too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
+ * bracketed by HIP events on the launch stream (mjh_inverse, mjh_ray, mjh_render, mjh_support, mjh_fd_perturb, mjh_fd_difference, mjh_fd_vjp, mjh_fd_tangent, mjh_ifd_perturb, mjh_ifd_difference, mjh_postconstraint, mjh_contact_sensors, mjh_energy, mjh_integrate, mjh_jacobian, mjh_geom_distance, mjh_qpos_arith, mjh_ik_site_step, mjh_constraint_space, mjh_pgs, mjh_noslip, mjh_solve, mjh_smooth and mjh_dynamics too); mjh_debug_phase_times() waits for the most recent call and returns, per launch,
  * the elapsed milliseconds and the kernel id (MJH_KERNEL_*).  Returns the number of launches (<= max) or a negative code. */
 int mjh_debug_phase_timing(int enable);
 int mjh_debug_phase_times(float* ms, int* kernel_ids, int max);
@@ -1149,7 +1261,8 @@ void mjh_debug_set_stamps(void* dev_ptr);
  * qacc_warmstart, qfrc_constraint, efc_force and the three scalars out -- (nefc + 3 nv + 3) reals + 4 bytes; -2 for a model without dofs or rows.  MJH_KERNEL_SMOOTH_COM_POS + op (an mjh_smooth call), per environment, every leaf the op
  * reads once, from the leaf extents, and what it writes, in reals: COM_POS 21 nbody + 6 njnt in, 13 nbody + 6 nv out; CRB 10 nbody + 6 nv in, 10 nbody + nv^2 out;
  * TENDON_ARMATURE nv^2 + ntendon nv in, nv^2 out (-2 without tendons); FACTOR_M nv (nv + 1) / 2 in, nv^2 out; COM_VEL 7 nv in, 6 nbody + 6 nv out; RNE (with flg_acc)
- * 14 nv + 16 nbody in, nv out; -2 for a model without dofs, COM_POS and CRB apart.  Returns 0, or -2 when this model's step does not launch that kernel. */
+ * 14 nv + 16 nbody in, nv out; -2 for a model without dofs, COM_POS and CRB apart.  MJH_KERNEL_DYNAMICS_TENDON + op (an mjh_dynamics call) is not accounted: -2.
+ * Returns 0, or -2 when this model's step does not launch that kernel. */
 int mjh_model_kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes);
 
 /* last error message of the calling thread ("" if none) */

@@ -2,7 +2,7 @@
 # Builds libmjhip.so for gfx950 in-tree (mujoco-torch_amd/lib/).
 #  -ffp-contract=off : keep the reference's separate multiply/add rounding (no FMA contraction) so results
 #                      track the float64 oracle to ~1e-15.
-# The kernels are compiled as 76 translation units (mjh_instances.h: 38 groups x 2 dtypes) by parallel hipcc processes
+# The kernels are compiled as 78 translation units (mjh_instances.h: 39 groups x 2 dtypes) by parallel hipcc processes
 # (MJH_BUILD_JOBS, default: the number of CPUs), objects cached under csrc/build/ by a hash of the sources and flags; mjhip.hip
 # is the host side.  `build.sh -DFOO` passes extra flags to every compile.  MJH_BUILD_ONLY="3d 7f" rebuilds only those groups
 # (d = double, f = float) and relinks with the cached rest -- for iterating on one kernel.
@@ -35,7 +35,7 @@ export HERE OBJ HIPCC FLAGS SRC_HASH FLAG_HASH MJH_BUILD_ONLY
 
 LIST=""
 # the heavy groups (register solver: 7 8 9, fused kinematics + velocity: 3) start first
-for g in 16 18 7 8 10 13 11 14 9 15 3 12 17 4 5 0 1 2 6 19 20 21 22 23 24 25 26 27 28 29 30 31 32 33 34 35 36 37; do [ "$g" -lt "$NG" ] && LIST="$LIST $g:d $g:f"; done
+for g in 16 18 7 8 10 13 11 14 9 15 3 12 17 4 5 0 1 2 6 19 20 21 22 23 24 25 26 27 28 29 30 31 32 33 34 35 36 37 38; do [ "$g" -lt "$NG" ] && LIST="$LIST $g:d $g:f"; done
 echo $LIST | tr ' ' '\n' | xargs -P "$JOBS" -I{} bash -c 'IFS=: read g t <<< "{}"; compile_one $g $t'
 $HIPCC $FLAGS -c -o "$OBJ/mjhip.o" "$HERE/mjhip.hip" 2> "$OBJ/mjhip.log" || { cat "$OBJ/mjhip.log" >&2; exit 1; }
 OBJS="$OBJ/mjhip.o"
@@ -46,10 +46,10 @@ LOG="$(mktemp)"
 cat "$OBJ"/inst_*.log "$OBJ/mjhip.log" > "$LOG"
 grep -E "error|warning: " "$LOG" || true
 NFUNC=$(grep -c "Function Name:" "$LOG" || true)
-NKERN=$(grep "Function Name:" "$LOG" | grep -cE "mjh_phase_kernel|mjh_sol2_kernel|mjh_convex_kernel|mjh_sensor_kernel|mjh_reset_kernel|mjh_inverse_kernel|mjh_ray_kernel|mjh_render_kernel|mjh_sup_point_kernel|mjh_sup_xfrc_kernel|mjh_sup_mulm_kernel|mjh_sup_solvem_kernel|mjh_fd_perturb_kernel|mjh_fd_difference_kernel|mjh_fd_vjp_kernel|mjh_fd_tangent_kernel|mjh_ifd_perturb_kernel|mjh_ifd_difference_kernel|mjh_postcon_kernel|mjh_consens_kernel|mjh_energy_kernel|mjh_integrate_kernel|mjh_jac_matrix_kernel|mjh_jac_product_kernel|mjh_quadric_kernel|mjh_geomdist_kernel|mjh_qpos_arith_kernel|mjh_ik_site_kernel|mjh_efc_mulj_kernel|mjh_efc_muljt_kernel|mjh_efc_update_kernel|mjh_efc_ar_kernel|mjh_pgs_kernel|mjh_noslip_kernel|mjh_solve_kernel|mjh_smooth_kernel" || true)
+NKERN=$(grep "Function Name:" "$LOG" | grep -cE "mjh_phase_kernel|mjh_sol2_kernel|mjh_convex_kernel|mjh_sensor_kernel|mjh_reset_kernel|mjh_inverse_kernel|mjh_ray_kernel|mjh_render_kernel|mjh_sup_point_kernel|mjh_sup_xfrc_kernel|mjh_sup_mulm_kernel|mjh_sup_solvem_kernel|mjh_fd_perturb_kernel|mjh_fd_difference_kernel|mjh_fd_vjp_kernel|mjh_fd_tangent_kernel|mjh_ifd_perturb_kernel|mjh_ifd_difference_kernel|mjh_postcon_kernel|mjh_consens_kernel|mjh_energy_kernel|mjh_integrate_kernel|mjh_jac_matrix_kernel|mjh_jac_product_kernel|mjh_quadric_kernel|mjh_geomdist_kernel|mjh_qpos_arith_kernel|mjh_ik_site_kernel|mjh_efc_mulj_kernel|mjh_efc_muljt_kernel|mjh_efc_update_kernel|mjh_efc_ar_kernel|mjh_pgs_kernel|mjh_noslip_kernel|mjh_solve_kernel|mjh_smooth_kernel|mjh_dynamics_kernel" || true)
 if [ "$NFUNC" != "$NKERN" ]; then
   echo "build.sh: device functions were not inlined into the kernels:" >&2
-  grep "Function Name:" "$LOG" | grep -vE "mjh_phase_kernel|mjh_sol2_kernel|mjh_convex_kernel|mjh_sensor_kernel|mjh_reset_kernel|mjh_inverse_kernel|mjh_ray_kernel|mjh_render_kernel|mjh_sup_point_kernel|mjh_sup_xfrc_kernel|mjh_sup_mulm_kernel|mjh_sup_solvem_kernel|mjh_fd_perturb_kernel|mjh_fd_difference_kernel|mjh_fd_vjp_kernel|mjh_fd_tangent_kernel|mjh_ifd_perturb_kernel|mjh_ifd_difference_kernel|mjh_postcon_kernel|mjh_consens_kernel|mjh_energy_kernel|mjh_integrate_kernel|mjh_jac_matrix_kernel|mjh_jac_product_kernel|mjh_quadric_kernel|mjh_geomdist_kernel|mjh_qpos_arith_kernel|mjh_ik_site_kernel|mjh_efc_mulj_kernel|mjh_efc_muljt_kernel|mjh_efc_update_kernel|mjh_efc_ar_kernel|mjh_pgs_kernel|mjh_noslip_kernel|mjh_solve_kernel|mjh_smooth_kernel" >&2
+  grep "Function Name:" "$LOG" | grep -vE "mjh_phase_kernel|mjh_sol2_kernel|mjh_convex_kernel|mjh_sensor_kernel|mjh_reset_kernel|mjh_inverse_kernel|mjh_ray_kernel|mjh_render_kernel|mjh_sup_point_kernel|mjh_sup_xfrc_kernel|mjh_sup_mulm_kernel|mjh_sup_solvem_kernel|mjh_fd_perturb_kernel|mjh_fd_difference_kernel|mjh_fd_vjp_kernel|mjh_fd_tangent_kernel|mjh_ifd_perturb_kernel|mjh_ifd_difference_kernel|mjh_postcon_kernel|mjh_consens_kernel|mjh_energy_kernel|mjh_integrate_kernel|mjh_jac_matrix_kernel|mjh_jac_product_kernel|mjh_quadric_kernel|mjh_geomdist_kernel|mjh_qpos_arith_kernel|mjh_ik_site_kernel|mjh_efc_mulj_kernel|mjh_efc_muljt_kernel|mjh_efc_update_kernel|mjh_efc_ar_kernel|mjh_pgs_kernel|mjh_noslip_kernel|mjh_solve_kernel|mjh_smooth_kernel|mjh_dynamics_kernel" >&2
   exit 1
 fi
 grep -E "Function Name|VGPRs:|ScratchSize|Occupancy" "$LOG" | sed 's/.*remark: *//' | paste - - - - | sed 's/\[-Rpass[^]]*\]//g' | sort > "${OUT%.so}.resource_usage.txt"

@@ -25,6 +25,7 @@
 #include "mjh_noslip.h"
 #include "mjh_solve.h"
 #include "mjh_smooth.h"
+#include "mjh_dynamics.h"
 #include "mjh_instances.h"
 
 #define MJH_CAT_(a, b) a##b
@@ -110,4 +111,12 @@ template __global__ void mjh_smooth_kernel<MJH_INST_REAL, MJH_SMOOTH_TENDON_ARMA
 template __global__ void mjh_smooth_kernel<MJH_INST_REAL, MJH_SMOOTH_FACTOR_M>(SmoothArgs<MJH_INST_REAL>);
 template __global__ void mjh_smooth_kernel<MJH_INST_REAL, MJH_SMOOTH_COM_VEL>(SmoothArgs<MJH_INST_REAL>);
 template __global__ void mjh_smooth_kernel<MJH_INST_REAL, MJH_SMOOTH_RNE>(SmoothArgs<MJH_INST_REAL>);
+#endif
+#if MJH_INST_GROUP == 38
+template __global__ void mjh_dynamics_kernel<MJH_INST_REAL, MJH_DYNAMICS_TENDON>(DynArgs<MJH_INST_REAL>);
+template __global__ void mjh_dynamics_kernel<MJH_INST_REAL, MJH_DYNAMICS_TRANSMISSION>(DynArgs<MJH_INST_REAL>);
+template __global__ void mjh_dynamics_kernel<MJH_INST_REAL, MJH_DYNAMICS_VELOCITY>(DynArgs<MJH_INST_REAL>);
+template __global__ void mjh_dynamics_kernel<MJH_INST_REAL, MJH_DYNAMICS_PASSIVE>(DynArgs<MJH_INST_REAL>);
+template __global__ void mjh_dynamics_kernel<MJH_INST_REAL, MJH_DYNAMICS_ACTUATION>(DynArgs<MJH_INST_REAL>);
+template __global__ void mjh_dynamics_kernel<MJH_INST_REAL, MJH_DYNAMICS_ACCELERATION>(DynArgs<MJH_INST_REAL>);
 #endif

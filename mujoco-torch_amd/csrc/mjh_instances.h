@@ -45,8 +45,9 @@
 #define MJH_INST_G35(X, S, C, N, R)  /* the no-slip friction post-solver (mjh_noslip_kernel, mjh_noslip.h): instantiated by mjh_inst.hip for this group */
 #define MJH_INST_G36(X, S, C, N, R)  /* the CG / Newton primal solver on a finished pass (mjh_solve_kernel, mjh_solve.h): instantiated by mjh_inst.hip for this group */
 #define MJH_INST_G37(X, S, C, N, R)  /* the smooth-dynamics stages on a caller's Data (mjh_smooth_kernel, mjh_smooth.h): instantiated by mjh_inst.hip for this group */
-#define MJH_INST_NGROUPS 38
+#define MJH_INST_G38(X, S, C, N, R)  /* tendon, transmission, passive and the forward stages on a caller's Data (mjh_dynamics_kernel, mjh_dynamics.h): instantiated by mjh_inst.hip for this group */
+#define MJH_INST_NGROUPS 39
 
 #define MJH_INST_ALL(X, S, C, N, R)                                                                                            \
   MJH_INST_G0(X, S, C, N, R) MJH_INST_G1(X, S, C, N, R) MJH_INST_G2(X, S, C, N, R) MJH_INST_G3(X, S, C, N, R) MJH_INST_G4(X, S, C, N, R) \
-  MJH_INST_G5(X, S, C, N, R) MJH_INST_G6(X, S, C, N, R) MJH_INST_G7(X, S, C, N, R) MJH_INST_G8(X, S, C, N, R) MJH_INST_G9(X, S, C, N, R) MJH_INST_G10(X, S, C, N, R) MJH_INST_G11(X, S, C, N, R) MJH_INST_G12(X, S, C, N, R) MJH_INST_G13(X, S, C, N, R) MJH_INST_G14(X, S, C, N, R) MJH_INST_G15(X, S, C, N, R) MJH_INST_G16(X, S, C, N, R) MJH_INST_G17(X, S, C, N, R) MJH_INST_G18(X, S, C, N, R) MJH_INST_G19(X, S, C, N, R) MJH_INST_G20(X, S, C, N, R) MJH_INST_G21(X, S, C, N, R) MJH_INST_G22(X, S, C, N, R) MJH_INST_G23(X, S, C, N, R) MJH_INST_G24(X, S, C, N, R) MJH_INST_G25(X, S, C, N, R) MJH_INST_G26(X, S, C, N, R) MJH_INST_G27(X, S, C, N, R) MJH_INST_G28(X, S, C, N, R) MJH_INST_G29(X, S, C, N, R) MJH_INST_G30(X, S, C, N, R) MJH_INST_G31(X, S, C, N, R) MJH_INST_G32(X, S, C, N, R) MJH_INST_G33(X, S, C, N, R) MJH_INST_G34(X, S, C, N, R) MJH_INST_G35(X, S, C, N, R) MJH_INST_G36(X, S, C, N, R) MJH_INST_G37(X, S, C, N, R)
+  MJH_INST_G5(X, S, C, N, R) MJH_INST_G6(X, S, C, N, R) MJH_INST_G7(X, S, C, N, R) MJH_INST_G8(X, S, C, N, R) MJH_INST_G9(X, S, C, N, R) MJH_INST_G10(X, S, C, N, R) MJH_INST_G11(X, S, C, N, R) MJH_INST_G12(X, S, C, N, R) MJH_INST_G13(X, S, C, N, R) MJH_INST_G14(X, S, C, N, R) MJH_INST_G15(X, S, C, N, R) MJH_INST_G16(X, S, C, N, R) MJH_INST_G17(X, S, C, N, R) MJH_INST_G18(X, S, C, N, R) MJH_INST_G19(X, S, C, N, R) MJH_INST_G20(X, S, C, N, R) MJH_INST_G21(X, S, C, N, R) MJH_INST_G22(X, S, C, N, R) MJH_INST_G23(X, S, C, N, R) MJH_INST_G24(X, S, C, N, R) MJH_INST_G25(X, S, C, N, R) MJH_INST_G26(X, S, C, N, R) MJH_INST_G27(X, S, C, N, R) MJH_INST_G28(X, S, C, N, R) MJH_INST_G29(X, S, C, N, R) MJH_INST_G30(X, S, C, N, R) MJH_INST_G31(X, S, C, N, R) MJH_INST_G32(X, S, C, N, R) MJH_INST_G33(X, S, C, N, R) MJH_INST_G34(X, S, C, N, R) MJH_INST_G35(X, S, C, N, R) MJH_INST_G36(X, S, C, N, R) MJH_INST_G37(X, S, C, N, R) MJH_INST_G38(X, S, C, N, R)

@@ -80,6 +80,44 @@ __device__ __forceinline__ void itg_cholesky(REAL* A, REAL* v, int nv, int l, in
   }
 }
 
+// math.small_cholesky_solve (math.py:132-168) in place on x, nv reals of an environment in LDS, with the packed factor A that itg_cholesky left (or a caller's qLD packed
+// the same way): L y = b by columns, then L^T z = y as the reference's row loop up to INLINE_CHOL_MAX dofs and by columns above.  Shared by mjh_integrate_kernel and
+// mjh_dynamics.h's ACCELERATION (qacc_smooth from the caller's qLD).
+template <typename REAL>
+__device__ __forceinline__ void itg_chol_solve(REAL* A, REAL* x, int nv, int l, int L) {
+  const bool big = nv > INLINE_CHOL_MAX;
+  // L y = b, column by column: element r loses L[r][k] y[k] in k order, as the reference's row loop does
+  // (every lane reads x[k] and its owner overwrites it in the same trip with no barrier between: an environment's lanes share a wavefront, which issues the read
+  // for all of them before the write, and LDS operations complete in issue order.  The same holds for the column-wise backward substitution below.)
+  for (int k = 0; k < nv; k++) {
+    const REAL yk = x[k] / A[itg_tri(k, k)];
+    for (int r = l; r < nv; r += L) {
+      if (r > k) x[r] = x[r] - A[itg_tri(r, k)] * yk;
+      else if (r == k) x[k] = yk;
+    }
+    wave_sync();
+  }
+  if (!big) {  // L^T z = y, the reference's row loop: k ascending inside a row, rows descending -- a serial chain, run by every lane alike
+    for (int i = nv - 1; i >= 0; i--) {
+      REAL s = x[i];
+      for (int k = i + 1; k < nv; k++) s = s - A[itg_tri(k, i)] * x[k];
+      s = s / A[itg_tri(i, i)];
+      wave_sync();
+      if (l == 0) x[i] = s;
+      wave_sync();
+    }
+  } else {
+    for (int k = nv - 1; k >= 0; k--) {
+      const REAL zk = x[k] / A[itg_tri(k, k)];
+      for (int r = l; r < nv; r += L) {
+        if (r < k) x[r] = x[r] - A[itg_tri(k, r)] * zk;
+        else if (r == k) x[k] = zk;
+      }
+      wave_sync();
+    }
+  }
+}
+
 template <typename REAL>
 __global__ __launch_bounds__(MJH_INTEGRATE_WG) void mjh_integrate_kernel(IntegrateArgs<REAL> a) {
   extern __shared__ __attribute__((aligned(16))) double itg_lds_raw[];
@@ -178,38 +216,8 @@ __global__ __launch_bounds__(MJH_INTEGRATE_WG) void mjh_integrate_kernel(Integra
     for (int i = l; i < nv; i += L) x[i] = a.qfrc_smooth[e * nv + i] + a.qfrc_constraint[e * nv + i];
     wave_sync();
 
-    const bool big = nv > INLINE_CHOL_MAX;
     itg_cholesky<REAL>(A, v, nv, l, L);
-    // L y = b, column by column: element r loses L[r][k] y[k] in k order, as the reference's row loop does
-    // (every lane reads x[k] and its owner overwrites it in the same trip with no barrier between: an environment's lanes share a wavefront, which issues the read
-    // for all of them before the write, and LDS operations complete in issue order.  The same holds for the column-wise backward substitution below.)
-    for (int k = 0; k < nv; k++) {
-      const REAL yk = x[k] / A[itg_tri(k, k)];
-      for (int r = l; r < nv; r += L) {
-        if (r > k) x[r] = x[r] - A[itg_tri(r, k)] * yk;
-        else if (r == k) x[k] = yk;
-      }
-      wave_sync();
-    }
-    if (!big) {  // L^T z = y, the reference's row loop: k ascending inside a row, rows descending -- a serial chain, run by every lane alike
-      for (int i = nv - 1; i >= 0; i--) {
-        REAL s = x[i];
-        for (int k = i + 1; k < nv; k++) s = s - A[itg_tri(k, i)] * x[k];
-        s = s / A[itg_tri(i, i)];
-        wave_sync();
-        if (l == 0) x[i] = s;
-        wave_sync();
-      }
-    } else {
-      for (int k = nv - 1; k >= 0; k--) {
-        const REAL zk = x[k] / A[itg_tri(k, k)];
-        for (int r = l; r < nv; r += L) {
-          if (r < k) x[r] = x[r] - A[itg_tri(k, r)] * zk;
-          else if (r == k) x[k] = zk;
-        }
-        wave_sync();
-      }
-    }
+    itg_chol_solve<REAL>(A, x, nv, l, L);
   } else if (a.flags & (MJH_INTEGRATE_STATE | MJH_INTEGRATE_WRITE_QACC)) {
     for (int i = l; i < nv; i += L) x[i] = a.qacc[e * nv + i];
     wave_sync();

@@ -29,6 +29,7 @@
 #include "mjh_jacobian.h"
 #include "mjh_integrate.h"
 #include "mjh_smooth.h"
+#include "mjh_dynamics.h"
 #include "mjh_quadric.h"
 #include "mjh_geomdist.h"
 #include "mjh_qpos.h"
@@ -91,6 +92,16 @@ extern template __global__ void mjh_integrate_kernel<float>(IntegrateArgs<float>
 SM_(double)  // (build group 37)
 SM_(float)
 #undef SM_
+#define DY_(R)                                                                                    \
+  extern template __global__ void mjh_dynamics_kernel<R, MJH_DYNAMICS_TENDON>(DynArgs<R>);        \
+  extern template __global__ void mjh_dynamics_kernel<R, MJH_DYNAMICS_TRANSMISSION>(DynArgs<R>);  \
+  extern template __global__ void mjh_dynamics_kernel<R, MJH_DYNAMICS_VELOCITY>(DynArgs<R>);      \
+  extern template __global__ void mjh_dynamics_kernel<R, MJH_DYNAMICS_PASSIVE>(DynArgs<R>);       \
+  extern template __global__ void mjh_dynamics_kernel<R, MJH_DYNAMICS_ACTUATION>(DynArgs<R>);     \
+  extern template __global__ void mjh_dynamics_kernel<R, MJH_DYNAMICS_ACCELERATION>(DynArgs<R>);
+DY_(double)  // (build group 38)
+DY_(float)
+#undef DY_
 extern template __global__ void mjh_quadric_kernel<double>(KArgs<double>);  // (build group 29)
 extern template __global__ void mjh_quadric_kernel<float>(KArgs<float>);
 extern template __global__ void mjh_ifd_perturb_kernel<double>(FdPerturbArgs<double>);  // (build group 30)
@@ -2205,6 +2216,113 @@ int run_smooth(const mjhModel* m, const DevModel<REAL>& M, const mjhSmoothArgs* 
   }
 }
 
+// mjh_dynamics's launch plan, from the model alone: lanes per environment (from nv: TENDON, PASSIVE, ACCELERATION; from nu: TRANSMISSION, VELOCITY, ACTUATION),
+// environments per workgroup, reals of LDS per environment (mjh_dynamics.h names the arrays).  A workgroup is planned for kLdsWg bytes; an environment that needs more
+// runs alone.  Returns 0, or -12 when one environment does not fit kLdsCu (out is filled all the same).
+static int dynamics_plan(int op, int nq, int nv, int nu, int nb, int nt, int real_bytes, int* out) {
+  const int n = (op == MJH_DYNAMICS_TENDON || op == MJH_DYNAMICS_PASSIVE || op == MJH_DYNAMICS_ACCELERATION) ? nv : nu;
+  const int lanes = n <= 16 ? 16 : (n <= 32 ? 32 : 64);
+  const int64_t reals[6] = {(int64_t)nq, (int64_t)nq + nt + 3 * (int64_t)nu, (int64_t)nv + ((int64_t)nu + nt) * (nv | 1), (int64_t)nv + nt + 12 * (int64_t)nb, (int64_t)nu,
+                            ((((int64_t)nv * (nv + 1)) / 2 + 3) & ~(int64_t)3) + nv + 6 * (int64_t)nb};
+  const int64_t lds_env = std::max<int64_t>(4, (reals[op] + 3) & ~(int64_t)3), env_bytes = lds_env * real_bytes;
+  out[0] = lanes;
+  out[1] = (int)std::max<int64_t>(1, std::min<int64_t>(MJH_DYNAMICS_WG / lanes, kLdsWg / env_bytes));
+  out[2] = (int)std::min<int64_t>(lds_env, INT32_MAX);
+  return env_bytes > kLdsCu ? -12 : 0;
+}
+
+template <typename REAL, int OP>
+int launch_dynamics(DynArgs<REAL>& a, int64_t B, hipStream_t s) {
+  const size_t lds = (size_t)a.envs * a.lds_env * sizeof(REAL);
+  if (lds > (size_t)kLdsWg) HIP_TRY(allow_lds(&mjh_dynamics_kernel<REAL, OP>, (int)lds));
+  return launch_envs(mjh_dynamics_kernel<REAL, OP>, a, B, s, MJH_KERNEL_DYNAMICS_TENDON + OP);
+}
+
+// tendon, transmission, passive and the forward stages on a caller's Data (mjh_dynamics.h), one launch
+template <typename REAL>
+int run_dynamics(const mjhModel* m, const DevModel<REAL>& M, const mjhDynamicsArgs* x, void* stream) {
+  const int op = x->op;
+  if (op < MJH_DYNAMICS_TENDON || op > MJH_DYNAMICS_ACCELERATION) return fail(-22, "dynamics: unknown op");
+  if (x->B < 0) return fail(-22, "dynamics: B must be >= 0");
+  const int nq = M.nq, nv = M.nv, nu = M.nu, na = M.na, nb = M.nbody, nj = M.njnt, nt = M.ntendon;
+  const int flags = x->disableflags;
+  if (x->B == 0) return 0;
+  switch (op) {
+    case MJH_DYNAMICS_TENDON:
+      if (nt == 0) return 0;
+      if (!x->qpos || !x->ten_length_out || (nv > 0 && !x->ten_J_out)) return fail(-22, "dynamics: null pointer (tendon)");
+      break;
+    case MJH_DYNAMICS_TRANSMISSION:
+      if (nu == 0) return 0;
+      if (!x->qpos || !x->gear || !x->actuator_length_out || (nv > 0 && !x->actuator_moment_out) || (nt > 0 && (!x->ten_length || (nv > 0 && !x->ten_J))))
+        return fail(-22, "dynamics: null pointer (transmission)");
+      break;
+    case MJH_DYNAMICS_VELOCITY:
+      if (nu + nt == 0 || nv == 0) return 0;
+      if (!x->qvel || (nu > 0 && (!x->actuator_moment || !x->actuator_velocity_out)) || (nt > 0 && (!x->ten_J || !x->ten_velocity_out)))
+        return fail(-22, "dynamics: null pointer (velocity)");
+      break;
+    case MJH_DYNAMICS_PASSIVE:
+      if (flags & (DSBL_SPRING | DSBL_DAMPER)) return fail(-22, "dynamics: passive with SPRING or DAMPER disabled is all zeros: nothing to launch");
+      if (nv == 0) return 0;
+      if (!x->qpos || !x->qvel || !x->jnt_stiffness || !x->qpos_spring || !x->dof_damping || !x->qfrc_passive_out ||
+          (nt > 0 && (!x->ten_length || !x->ten_velocity || !x->ten_J || !x->tendon_stiffness || !x->tendon_damping || !x->tendon_lengthspring)) ||
+          ((x->has_gravcomp || x->has_fluid) && (!x->xipos || !x->subtree_com || !x->cdof || !x->body_mass)) ||
+          (x->has_gravcomp && (!x->body_gravcomp || !x->jnt_actgravcomp || !x->qfrc_gravcomp_out)) || (x->has_fluid && (!x->ximat || !x->cvel || !x->body_inertia)))
+        return fail(-22, "dynamics: null pointer (passive)");
+      break;
+    case MJH_DYNAMICS_ACTUATION:
+      if (nu == 0 || (flags & DSBL_ACTUATION)) return fail(-22, "dynamics: actuation without actuators or with ACTUATION disabled is all zeros: nothing to launch");
+      if (!x->ctrl || (na > 0 && (!x->act || !x->act_dot_out || !x->dynprm)) || !x->actuator_length || !x->actuator_velocity || !x->gainprm || !x->biasprm ||
+          !x->ctrlrange || !x->forcerange || !x->lengthrange || !x->acc0 || !x->actuator_force_out ||
+          (nv > 0 && (!x->actuator_moment || !x->qfrc_actuator_out || !x->jnt_actfrcrange || (x->has_gravcomp && (!x->qfrc_gravcomp || !x->jnt_actgravcomp)))))
+        return fail(-22, "dynamics: null pointer (actuation)");
+      if (x->gain_stride < 3 || x->bias_stride < 3 || (na > 0 && x->dyn_stride < 1))  // (9 / 9 / 3 for muscle gains, biases and dynamics: the Python layer's check)
+        return fail(-22, "dynamics: gainprm / biasprm rows need 3 entries, dynprm rows 1");
+      break;
+    default:
+      if (nv == 0) return 0;
+      if (!x->qfrc_applied || !x->xfrc_applied || !x->xipos || !x->subtree_com || !x->cdof || !x->qfrc_passive || !x->qfrc_bias || !x->qfrc_actuator || !x->qLD ||
+          !x->qfrc_smooth_out || !x->qacc_smooth_out)
+        return fail(-22, "dynamics: null pointer (acceleration)");
+  }
+  int plan[3];
+  if (dynamics_plan(op, nq, nv, nu, nb, nt, (int)sizeof(REAL), plan)) {
+    char msg[240];
+    snprintf(msg, sizeof(msg), "dynamics: op %d with nq = %d, nv = %d, nu = %d, nbody = %d, ntendon = %d needs %lld bytes of LDS per environment; a CU has %d", op, nq, nv,
+             nu, nb, nt, (long long)plan[2] * (long long)sizeof(REAL), (int)kLdsCu);
+    return fail(-12, msg);
+  }
+  DynArgs<REAL> a;
+  memset(&a, 0, sizeof(a));
+  P_(qpos) P_(qvel) P_(ctrl) P_(act) P_(ten_length) P_(ten_velocity) P_(ten_J) P_(actuator_length) P_(actuator_velocity) P_(actuator_moment) P_(xipos) P_(ximat)
+  P_(subtree_com) P_(cdof) P_(cvel) P_(qfrc_gravcomp) P_(qfrc_applied) P_(xfrc_applied) P_(qfrc_passive) P_(qfrc_bias) P_(qfrc_actuator) P_(qLD)
+  P_(jnt_stiffness) P_(qpos_spring) P_(dof_damping) P_(tendon_stiffness) P_(tendon_damping) P_(tendon_lengthspring) P_(body_mass) P_(body_inertia) P_(body_gravcomp)
+  P_(jnt_actgravcomp) P_(jnt_actfrcrange) P_(gainprm) P_(biasprm) P_(dynprm) P_(ctrlrange) P_(forcerange) P_(gear) P_(lengthrange) P_(acc0)
+  O_(ten_length_out) O_(ten_J_out) O_(actuator_length_out) O_(actuator_moment_out) O_(actuator_velocity_out) O_(ten_velocity_out) O_(qfrc_passive_out)
+  O_(qfrc_gravcomp_out) O_(act_dot_out) O_(qfrc_actuator_out) O_(actuator_force_out) O_(qfrc_smooth_out) O_(qacc_smooth_out)
+  a.body_rootid = M.body_rootid; a.body_subtree_end = M.body_subtree_end; a.jnt_type = M.jnt_type; a.jnt_qposadr = M.jnt_qposadr; a.jnt_dofadr = M.jnt_dofadr;
+  a.jnt_actfrclimited = M.jnt_actfrclimited; a.dof_bodyid = M.dof_bodyid; a.dof_jntid = M.dof_jntid; a.ten_adr = M.ten_adr; a.ten_qposadr = M.ten_qposadr;
+  a.act_trntype = M.act_trntype; a.act_trnid = M.act_trnid; a.act_jnttype = M.act_jnttype; a.act_dofadr = M.act_dofadr; a.act_qposadr = M.act_qposadr;
+  a.act_gaintype = M.act_gaintype; a.act_biastype = M.act_biastype; a.act_dyntype = M.act_dyntype; a.act_ctrllimited = M.act_ctrllimited;
+  a.act_forcelimited = M.act_forcelimited; a.act_actadr = M.act_actadr; a.act_actnum = M.act_actnum; a.ten_coef = M.ten_coef; a.ten_J0 = M.ten_J0;
+  a.gravity[0] = (REAL)x->gravity_x; a.gravity[1] = (REAL)x->gravity_y; a.gravity[2] = (REAL)x->gravity_z;
+  a.wind[0] = (REAL)x->wind_x; a.wind[1] = (REAL)x->wind_y; a.wind[2] = (REAL)x->wind_z; a.density = (REAL)x->density; a.viscosity = (REAL)x->viscosity;
+  a.nq = nq; a.nv = nv; a.nu = nu; a.na = na; a.nbody = nb; a.njnt = nj; a.ntendon = nt;
+  a.gain_stride = x->gain_stride; a.bias_stride = x->bias_stride; a.dyn_stride = x->dyn_stride;
+  a.gravcomp = x->has_gravcomp != 0; a.fluid = x->has_fluid != 0; a.clampctrl = !(flags & DSBL_CLAMPCTRL);
+  a.lanes = plan[0]; a.envs = plan[1]; a.lds_env = plan[2];
+  hipStream_t s = (hipStream_t)stream;
+  switch (op) {
+    case MJH_DYNAMICS_TENDON: return launch_dynamics<REAL, MJH_DYNAMICS_TENDON>(a, x->B, s);
+    case MJH_DYNAMICS_TRANSMISSION: return launch_dynamics<REAL, MJH_DYNAMICS_TRANSMISSION>(a, x->B, s);
+    case MJH_DYNAMICS_VELOCITY: return launch_dynamics<REAL, MJH_DYNAMICS_VELOCITY>(a, x->B, s);
+    case MJH_DYNAMICS_PASSIVE: return launch_dynamics<REAL, MJH_DYNAMICS_PASSIVE>(a, x->B, s);
+    case MJH_DYNAMICS_ACTUATION: return launch_dynamics<REAL, MJH_DYNAMICS_ACTUATION>(a, x->B, s);
+    default: return launch_dynamics<REAL, MJH_DYNAMICS_ACCELERATION>(a, x->B, s);
+  }
+}
+
 #undef P_
 #undef O_
 
@@ -2537,6 +2655,19 @@ int mjh_smooth(const mjhModel* m, const mjhSmoothArgs* args, void* stream) {
   return m->dtype == MJH_F64 ? run_smooth<double>(m, m->m64, args, stream) : run_smooth<float>(m, m->m32, args, stream);
 }
 
+int mjh_dynamics(const mjhModel* m, const mjhDynamicsArgs* args, void* stream) {
+  if (!m || !args) return fail(-22, "null argument");
+  return m->dtype == MJH_F64 ? run_dynamics<double>(m, m->m64, args, stream) : run_dynamics<float>(m, m->m32, args, stream);
+}
+
+int mjh_dynamics_plan(int op, int nq, int nv, int nu, int nbody, int ntendon, int real_bytes, int* lanes_envs_lds) {
+  if (op < MJH_DYNAMICS_TENDON || op > MJH_DYNAMICS_ACCELERATION || nq < 0 || nv < 0 || nu < 0 || nbody < 1 || ntendon < 0 || (real_bytes != 4 && real_bytes != 8) ||
+      !lanes_envs_lds)
+    return fail(-22, "dynamics_plan: bad argument");
+  if (dynamics_plan(op, nq, nv, nu, nbody, ntendon, real_bytes, lanes_envs_lds)) return fail(-12, "dynamics_plan: one environment does not fit the LDS of a CU");
+  return 0;
+}
+
 int mjh_smooth_plan(int op, int nbody, int nv, int ntendon, int real_bytes, int* lanes_envs_lds) {
   if (op < MJH_SMOOTH_COM_POS || op > MJH_SMOOTH_RNE || nbody < 1 || nv < 0 || ntendon < 0 || (real_bytes != 4 && real_bytes != 8) || !lanes_envs_lds)
     return fail(-22, "smooth_plan: bad argument");
@@ -2815,6 +2946,7 @@ static int kernel_io(const mjhModel* m, int kernel, int64_t* read_write_bytes, b
     read_write_bytes[1] = wr[op] * R;
     return 0;
   }
+  if (kernel >= MJH_KERNEL_DYNAMICS_TENDON && kernel <= MJH_KERNEL_DYNAMICS_ACCELERATION) return -2;  // mjh_dynamics: not accounted (include/mjhip.h)
   if (kernel == MJH_KERNEL_INTEGRATE) {  // an implicit step (mjh_integrate, QDERIV | IMPLICIT | STATE): the leaves it reads once (qM in full), the four state leaves out
     const int64_t R = f64 ? 8 : 4, nq = f64 ? m->m64.nq : m->m32.nq, nv = f64 ? m->m64.nv : m->m32.nv, nu = f64 ? m->m64.nu : m->m32.nu, na = f64 ? m->m64.na : m->m32.na,
                   nt = f64 ? m->m64.ntendon : m->m32.ntendon;

@@ -2,7 +2,7 @@
 
 Drop-in for the hot path of vmoens/mujoco-torch (``mujoco_torch/__init__.py:41-136``):
 ``step``, ``forward``, ``inverse``, ``transition_fd``, ``inverse_fd``, ``transition_vjp``, ``differentiable_step``, ``tangent_pull``, ``tangent_push``, ``ray``, ``ray_geom``, ``render``, ``render_batch``, ``precompute_render_data``,
-``rne_postconstraint``, ``subtree_vel``, ``fwd_postconstraint``, ``contact_force``, ``sensor_postconstraint``, ``energy``, ``energy_pos``, ``energy_vel``, ``geom_distance``, ``integrate_pos``, ``differentiate_pos``, ``normalize_quat``, ``state_sub``, ``state_add``, ``ik_site``, ``mul_jac_vec``, ``mul_jac_t_vec``, ``constraint_update``, ``efc_ar``, ``solve_pgs``, ``solve_noslip``, ``solve``, ``kinematics``, ``com_pos``, ``crb``, ``tendon_armature``, ``factor_m``, ``com_vel``, ``rne``, ``deriv_smooth_vel``, ``implicit``, ``euler``, ``jac``, ``jac_body``, ``jac_body_com``, ``jac_site``, ``jac_geom``, ``jac_subtree_com``, ``jac_dot``, ``angmom_mat``, ``apply_ft``, ``xfrc_accumulate``, ``mul_m``, ``solve_m``, ``full_m``, ``device_put``, ``make_data`` and the ``Model`` / ``Data`` / ``Contact`` /
+``rne_postconstraint``, ``subtree_vel``, ``fwd_postconstraint``, ``contact_force``, ``sensor_postconstraint``, ``energy``, ``energy_pos``, ``energy_vel``, ``geom_distance``, ``integrate_pos``, ``differentiate_pos``, ``normalize_quat``, ``state_sub``, ``state_add``, ``ik_site``, ``mul_jac_vec``, ``mul_jac_t_vec``, ``constraint_update``, ``efc_ar``, ``solve_pgs``, ``solve_noslip``, ``solve``, ``kinematics``, ``com_pos``, ``crb``, ``tendon_armature``, ``factor_m``, ``com_vel``, ``rne``, ``tendon``, ``transmission``, ``passive``, ``fwd_velocity``, ``fwd_actuation``, ``fwd_acceleration``, ``deriv_smooth_vel``, ``implicit``, ``euler``, ``jac``, ``jac_body``, ``jac_body_com``, ``jac_site``, ``jac_geom``, ``jac_subtree_com``, ``jac_dot``, ``angmom_mat``, ``apply_ft``, ``xfrc_accumulate``, ``mul_m``, ``solve_m``, ``full_m``, ``device_put``, ``make_data`` and the ``Model`` / ``Data`` / ``Contact`` /
 ``Option`` schema.  Use as ``import mujoco_torch_amd as mujoco_torch``.
 """
 
@@ -41,6 +41,7 @@ from .pgs import PGSResult, solve_pgs  # noqa: F401
 from .noslip import NoslipResult, solve_noslip  # noqa: F401
 from .solver import SolveStats, solve  # noqa: F401
 from .smooth import com_pos, com_vel, crb, factor_m, kinematics, rne, tendon_armature  # noqa: F401
+from .dynamics import fwd_acceleration, fwd_actuation, fwd_velocity, passive, tendon, transmission  # noqa: F401
 from .derivative import differentiable_step, inverse_fd, tangent_pull, tangent_push, transition_fd, transition_vjp  # noqa: F401
 from .io import make_data  # noqa: F401
 from .jacobian import angmom_mat, jac_body, jac_body_com, jac_dot, jac_geom, jac_site, jac_subtree_com  # noqa: F401

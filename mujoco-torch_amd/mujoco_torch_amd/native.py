@@ -336,6 +336,21 @@ class SmoothArgs(ctypes.Structure):
         "tendon_armature", "subtree_com_out", "cinert_out", "cdof_out", "crb_out", "qM_out", "qLD_out", "cvel_out", "cdof_dot_out", "qfrc_bias_out")]
 
 
+class DynamicsArgs(ctypes.Structure):
+    """include/mjhip.h mjhDynamicsArgs: one mjh_dynamics call (device pointers).  Bound below beside the ``ARGS`` table, like ``SmoothArgs`` (tests/test_dynamics_host.py
+    compares it with the header, field by field, with tests/test_abi.py's own parser)."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("op", "disableflags", "has_gravcomp", "has_fluid", "gain_stride", "bias_stride", "dyn_stride", "reserved")] + [
+        ("B", ctypes.c_int64)] + [(n, ctypes.c_double) for n in ("gravity_x", "gravity_y", "gravity_z", "wind_x", "wind_y", "wind_z", "density", "viscosity")] + [
+        (n, ctypes.c_void_p) for n in (
+            "qpos", "qvel", "ctrl", "act", "ten_length", "ten_velocity", "ten_J", "actuator_length", "actuator_velocity", "actuator_moment", "xipos", "ximat", "subtree_com",
+            "cdof", "cvel", "qfrc_gravcomp", "qfrc_applied", "xfrc_applied", "qfrc_passive", "qfrc_bias", "qfrc_actuator", "qLD", "jnt_stiffness", "qpos_spring",
+            "dof_damping", "tendon_stiffness", "tendon_damping", "tendon_lengthspring", "body_mass", "body_inertia", "body_gravcomp", "jnt_actgravcomp", "jnt_actfrcrange",
+            "gainprm", "biasprm", "dynprm", "ctrlrange", "forcerange", "gear", "lengthrange", "acc0", "ten_length_out", "ten_J_out", "actuator_length_out",
+            "actuator_moment_out", "actuator_velocity_out", "ten_velocity_out", "qfrc_passive_out", "qfrc_gravcomp_out", "act_dot_out", "qfrc_actuator_out",
+            "actuator_force_out", "qfrc_smooth_out", "qacc_smooth_out")]
+
+
 # the entry points that take (handle, args struct, stream): symbol -> the struct (tests/test_abi.py compares every struct with the header)
 ARGS = {"mjh_support": SupportArgs, "mjh_postconstraint": PostconArgs, "mjh_contact_sensors": ContactSensorArgs, "mjh_energy": EnergyArgs,
         "mjh_integrate": IntegrateArgs, "mjh_jacobian": JacobianArgs}
@@ -415,6 +430,11 @@ def load_library(path: str | None = None):
         lib.mjh_smooth.restype = ctypes.c_int
         lib.mjh_smooth_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         lib.mjh_smooth_plan.restype = ctypes.c_int
+    if hasattr(lib, "mjh_dynamics"):  # (likewise a build from before tendon .. fwd_acceleration)
+        lib.mjh_dynamics.argtypes = [ctypes.c_void_p, ctypes.POINTER(DynamicsArgs), ctypes.c_void_p]
+        lib.mjh_dynamics.restype = ctypes.c_int
+        lib.mjh_dynamics_plan.argtypes = [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_int)]
+        lib.mjh_dynamics_plan.restype = ctypes.c_int
     if hasattr(lib, "mjh_integrate_plan"):
         lib.mjh_integrate_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         lib.mjh_integrate_plan.restype = ctypes.c_int
